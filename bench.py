@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the atmosphere -> TOD hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config atlast_10k] [--scaling strong|weak]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config atlast_10k] [--scaling strong|weak] [--dump-outputs DIR]
 
 One step = one full pass of the path over one observation's worth of synthetic
 input for this rank's detectors: generate + smooth the turbulent screens
@@ -96,7 +96,72 @@ def parse_args(argv=None):
                     help="development, N = 1 only: run alone on this GPU the rows rank 0 of a run on this many GPUs would take "
                          "(the per-rank step of an N-GPU run, rehearsed on one; the line says so in config.workload)")
     ap.add_argument("--print-launch", action="store_true", help="print the child launch command of --gpus N as JSON and exit (no GPU needed)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all: a fixed, seeded sample of the TOD's rows and of every screen; see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be at least 0")
+    return args
+
+
+# ---- --dump-outputs ----------------------------------------------------------------------
+
+DUMP_SEED = 20240601  # fixed: the same rows and pixels on every run and every build
+DUMP_TOD_BYTES = 48 << 20
+DUMP_SCREEN_BYTES = 8 << 20
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_selection(n_rows, n_samples, screen_sizes, seed=DUMP_SEED):
+    """The TOD rows (and samples, when a whole row would not fit) and the flat pixel indices per screen that
+    --dump-outputs keeps: seeded, sorted, within DUMP_TOD_BYTES / DUMP_SCREEN_BYTES of float32, and a function
+    of the shapes alone -- two builds run with the same arguments keep the same elements."""
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    per_row = DUMP_TOD_BYTES // 4
+    if n_samples <= per_row:
+        rows = np.sort(rng.choice(n_rows, size=min(n_rows, per_row // n_samples), replace=False))
+        cols = None
+    else:  # one row; its kept samples' float32 values and float64 indices share the budget
+        rows = np.sort(rng.choice(n_rows, size=1, replace=False))
+        cols = np.sort(rng.choice(n_samples, size=DUMP_TOD_BYTES // 12, replace=False))
+    k = min([DUMP_SCREEN_BYTES // (4 * len(screen_sizes))] + list(screen_sizes)) if screen_sizes else 0
+    pixels = [np.sort(rng.choice(n, size=k, replace=False)) for n in screen_sizes]
+    return rows, cols, pixels
+
+
+def dump_outputs(dirname, tod, screens, row_offset=0):
+    """Write what the timed path computed in its last step: tod.npy (float32 [rows, samples], the sampled
+    detector rows of this rank's TOD), tod_rows.npy (float64, their detector indices in the whole
+    configuration), tod_samples.npy (float64, only when the samples were sampled too) and screens.npy
+    (float32 [layers, pixels], the same seeded pixels of every screen's flattened grid).  Returns
+    {name: shape}."""
+    import numpy as np
+    import torch
+
+    D, T = tod.shape
+    rows, cols, pixels = dump_selection(D, T, [s.numel() for s in screens])
+    dev = tod.device
+    sample = tod.index_select(0, torch.as_tensor(rows, device=dev))
+    if cols is not None:
+        sample = sample.index_select(1, torch.as_tensor(cols, device=dev))
+    arrays = {"tod": sample.cpu().numpy(), "tod_rows": (rows + row_offset).astype(np.float64)}
+    if cols is not None:
+        arrays["tod_samples"] = cols.astype(np.float64)
+    if screens:
+        arrays["screens"] = torch.stack([s.reshape(-1).index_select(0, torch.as_tensor(p, device=s.device))
+                                         for s, p in zip(screens, pixels)]).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} B over the {DUMP_MAX_BYTES} B limit"
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 # ---- self-launch -----------------------------------------------------------------------
@@ -546,6 +611,8 @@ def run(args):
     elapsed = time.perf_counter() - t_start
     gc.enable()
     flags = path.check_flags()
+    # what the last timed step computed, before the passes below write the same buffers again
+    dumped = dump_outputs(args.dump_outputs, tod, path._gen_screens, row_offset=lo) if args.dump_outputs and rank == 0 else None
 
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=red_device)
@@ -676,6 +743,8 @@ def run(args):
     }
     if weak_unit:
         result["config"]["weak_unit"] = weak_unit
+    if dumped is not None:
+        result["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped, "seed": DUMP_SEED}
 
     # HBM bytes per launch of the dominant kernel from the PMC counters: collected in
     # separate rocprofv3 --pmc passes (gpurun refuses --pmc inside an ordinary run), stored

@@ -261,12 +261,12 @@ def test_beam_folded_into_the_spectrum_equals_the_stencil_inside(gpu_ctx, ny, nx
             assert np.abs(a - b).max() <= 2e-5 * np.abs(b).max()
 
 
-def test_tap_cache_eviction_spares_the_batch_under_assembly():
+def test_tap_cache_eviction_spares_the_batch_under_assembly(gpu_ctx):
     """The fused stencils' Gaussian taps are cached per (sigma, radius) in the context.  A batch whose
     first layers HIT cached slots and whose later layers MISS must not have the hit slots evicted
     before its single launch: fill and wrap the cache with 140 distinct sigmas, then
     run a batch that mixes the oldest cached sigmas with new ones and compare every layer with the
-    same layer generated on its own."""
+    same layer generated on its own.  (gpu_ctx only for its device set-up and its skip without a GPU.)"""
     from maria_amd import Context
 
     ctx = Context(0)  # a cache of its own
