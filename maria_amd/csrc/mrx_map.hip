@@ -1337,6 +1337,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kChain ?
     bool done = false;
     if constexpr (kCal && kLdsSc) {
       if (coef_ok && __builtin_amdgcn_readfirstlane(bad_row[dl]) == 0) {  // (uniform)
+        // the halo's place in the thread's samples: one before the first, one after the last -- or, where that index is
+        // clamped to the run's ends (the per-sample form's rule, scipy's 'reflect'), the end sample itself
+        const float q_halo = first ? (s_tile > 0 ? -1.0f : 0.0f) : (s_tile + kTileSamples < g.T ? 4.0f : 3.0f);
         batched(std::true_type{}, [&](int c, auto& f) {
           const float* cf = coef + (c * kTileDet + dl) * coef_pitch + 3 * rb;
           constexpr int n = sizeof(f) / sizeof(f[0]);
@@ -1344,9 +1347,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kChain ?
           for (int q = 0; q < n; ++q) {
             // the sample's place in its coarse step: v counts from the start of the thread's first step; past 1 it is the
             // next step's (one record on).  (The halo sample, q = 4: one sample before the first thread's first, or one
-            // after the last thread's last.)
-            const float v = fmaf(q == 4 ? (first ? -1.0f : 4.0f) : (float)q, dvt, v0);
-            const bool next = v >= lim;
+            // after the last thread's last.)  The tile has n_int records: a v that float32 rounds up to 1 in the last step
+            // (a float64 u of 1 - 1e-14) keeps that step's record, whose parabola at w = 1 is the next step's start.
+            const float v = fmaf(q == 4 ? q_halo : (float)q, dvt, v0);
+            const bool next = v >= lim && rb + 1 < n_int;
             const float w = next ? v - 1.0f : v;
             const float* rec = next ? cf + 3 : cf;
             f[q] = fmaf(w, fmaf(w, rec[2], rec[1]), rec[0]);
@@ -1510,10 +1514,16 @@ static int map_sample(mrx_ctx* ctx, const mrx_sky_map* map, const mrx_map_cal* c
   if (cal->d_table) {
     lds = sizeof(float) * ((size_t)cal->n_pwv + cal->n_el + (size_t)map->n_channels * cal->n_pwv * cal->n_el);
     MRX_REQUIRE(ctx, lds <= 48 * 1024, "calibration tables of all channels must fit in 48 KiB");
-    if (map->n_channels <= kCalFastChannels && T >= 2) {  // the interval table of the per-sample calibration behind them
-      g.coef_cap = cal->steps_per_tile > 0 ? std::min(cal->steps_per_tile, kMaxSteps) : kDefaultSteps;
+    // the interval table of the per-sample calibration behind them -- not where no tile can use it (a tile that meets more
+    // than kMaxSteps steps takes the per-sample form), nor where it would push the K_RJ form's tables past their 60 KiB
+    const int cap = cal->steps_per_tile > 0 ? std::min(cal->steps_per_tile, kMaxSteps) : kDefaultSteps;
+    const size_t coef_bytes = sizeof(float) * (size_t)map->n_channels * kTileDet * (3 * cap + 1);
+    const size_t krj_bytes = krj ? sizeof(float4) * (size_t)(krj->n_el - 1) * krj->n_bands : 0;
+    if (map->n_channels <= kCalFastChannels && T >= 2 && cal->steps_per_tile <= kMaxSteps &&
+        (!krj || (lds + coef_bytes + 15) / 16 * 16 + krj_bytes <= 60 * 1024)) {
+      g.coef_cap = cap;
       g.coef_offset = (int)(lds / sizeof(float));
-      lds += sizeof(float) * (size_t)map->n_channels * kTileDet * (3 * g.coef_cap + 1);
+      lds += coef_bytes;
     }
   } else {
     lds = sizeof(float) * (size_t)map->n_channels;  // the channels' scalar factors

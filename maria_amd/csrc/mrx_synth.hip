@@ -247,6 +247,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MRX_SYNT
             // (the integer divisions of this decode are a few dozen vector instructions each -- there is no scalar one)
             int blk, sx, rg;
             tile_of(te - 1, blk, sx, rg);
+            // Row group by row group the units do not rise along the queue: a batch that holds a row group's last time
+            // tile and the next row group's first reads its latest chunks in that last time tile (sx = nsx - 1).  (A batch
+            // that reaches into the next block: the block's units come after all of the one before.)
+            if (tile_order != 0 && rg > 0 && sx < te - 1 - tl) sx = nsx - 1;
             int lo, hi;
             fused_tile_knots(t, T, Ta, ta0, inv_dta, sx, lo, hi);
             need = blk * nby + hi / chunk;  // the last unit the batch reads (a tile's knots lie in one block)

@@ -506,3 +506,124 @@ def test_the_writer_on_its_own_takes_tiles_from_a_queue(gpu_ctx):
             assert float((out - ref).abs().max()) <= 2e-6 * float(ref.abs().max())
         else:
             assert torch.equal(out, first)
+
+
+def _row_group_order_straddles(path, block_rows, per_cu):
+    """MRX_OPT_SYNTH_TILE_ORDER = 1's tile queue as the launcher cuts it (atm_synthesize, atm_tod_kernel's tile_of): the
+    queue's time tiles ``nsx`` and the batches of two tiles -- a row group's last time tile and the next row group's first,
+    in one block -- that are certain to be drawn together.  Below ``n_tiles - 4 * grid`` every ticket takes two tiles (the
+    tail takes single ones), so the counter stays even there; the grid is at most ``per_cu`` workgroups a CU."""
+    import torch
+
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    D, T, Ta = path.D, path.T, path.Ta
+    nsx = -(-T // 1024)
+    rows_per_tile = 32 if 1024.0 * Ta / T + 6.0 <= 58 else 16  # (kSmallKnots: two 16-row groups a tile; no MRX_OPT_UPSAMPLE_GROUPS)
+    br = min(-(-block_rows // 256) * 256, -(-D // 32) * 32)
+    n_blocks = -(-D // br)
+    nrg_full, nrg_last = -(-br // rows_per_tile), -(-(D - (n_blocks - 1) * br) // rows_per_tile)
+    tiles_full = nsx * nrg_full
+    n_tiles = tiles_full * (n_blocks - 1) + nsx * nrg_last
+    first = np.arange(0, max(n_tiles - 4 * per_cu * n_cu, 0), 2)  # the batches' first tiles
+    blk = np.minimum(first // tiles_full, n_blocks - 1)
+    rem = first - blk * tiles_full
+    nrg = np.where(blk == n_blocks - 1, nrg_last, nrg_full)
+    straddle = (rem % nsx == nsx - 1) & (rem // nsx + 1 < nrg)
+    return nsx, int(straddle.sum())
+
+
+def test_row_group_order_hands_over_every_tile(gpu_ctx):
+    """MRX_OPT_SYNTH_TILE_ORDER = 1 (row group by row group): a writer draws two tiles at a time and waits for the chunks
+    of both.  Where the number of time tiles is odd the queue holds batches of a row group's LAST time tile and the next
+    row group's FIRST -- the first tile reads the later chunks, and a poll for the batch's last tile alone lets the writer
+    read chunks the samplers have not written yet (the launch before's: the data change every launch).  Small shapes with
+    an odd and an even number of time tiles and atlast_10k at 4 000 detectors (235 time tiles), in blocks of 512 rows,
+    one to five resident workgroups a CU, none to two dedicated samplers, chunks of 16 and 64, both hand-over forms: every
+    word equals the two calls of that launch's data, and no hand-over timed out."""
+    import torch
+
+    from maria_amd import _lib
+
+    gpu_ctx.set_option(_lib.OPT_SYNTH_TILE_ORDER, 1)
+    try:
+        shapes = [
+            (small_problem(n_det=2000, n_layers=2, n_bands=1, fs=400.0, duration=62.5), [(1, 0, 16, 0), (1, 2, 64, 1), (2, 1, 64, 0), (3, 0, 16, 1)]),
+            (small_problem(n_det=2000, n_layers=2, n_bands=1, fs=400.0, duration=60.0), [(1, 1, 16, 1), (1, 0, 64, 0), (4, 2, 16, 0), (5, 1, 64, 1)]),
+            (config_problem("atlast_10k", n_det=4000), [(1, 0, 16, 0), (2, 1, 64, 1), (3, 2, 16, 0), (4, 0, 64, 1), (5, 1, 16, 1),
+                                                        (1, 2, 64, 1), (2, 0, 16, 0), (5, 2, 64, 0)]),
+        ]
+        block_rows = 512
+        for i, (p, launches) in enumerate(shapes):
+            path = _path(p, gpu_ctx)
+            generated = i == 2
+            if generated:
+                path.generate_screens()
+            path.clear_flags()
+            alt = _Alternating(path, generated=generated, keep_coarse=False)
+            nsx, straddles = _row_group_order_straddles(path, block_rows, 1)
+            assert nsx % 2 == (0 if i == 1 else 1), nsx  # the case is what it says
+            if i != 1:
+                assert straddles > 0, "some batch holds a row group's last time tile and the next one's first"
+            if i == 2:
+                assert nsx == 235
+            got = torch.empty_like(alt.want[0])
+            for rep, (per_cu, samplers, chunk, acquire) in enumerate(launches):
+                v = (rep // 2 + rep) % 2
+                alt.select(v)
+                got.fill_(float("nan"))
+                gpu_ctx.set_option(_lib.OPT_SYNTH_WGS_PER_CU, per_cu)
+                gpu_ctx.set_option(_lib.OPT_SYNTH_ACQUIRE, acquire)
+                path.synthesize(got, block_rows=block_rows, sampler_wgs_per_cu=8 if samplers == 0 else min(samplers, per_cu), chunk=chunk)
+                alt.check(v, got, (i, nsx, rep, per_cu, samplers, chunk, acquire))
+                assert path.check_flags() == 0, (i, rep)
+            del path, alt, got
+            torch.cuda.empty_cache()
+    finally:
+        gpu_ctx.set_option(_lib.OPT_SYNTH_TILE_ORDER, 0)
+        gpu_ctx.set_option(_lib.OPT_SYNTH_WGS_PER_CU, 0)
+        gpu_ctx.set_option(_lib.OPT_SYNTH_ACQUIRE, 0)
+
+
+def test_random_shapes_in_row_group_order(gpu_ctx):
+    """test_random_shapes' draw in MRX_OPT_SYNTH_TILE_ORDER = 1 (16 shapes, a seed of their own): detectors, layers, bands,
+    sample rate, duration and time step, gain, block size (never the library's choice: the order wants blocks), chunk
+    length, dedicated samplers and resident workgroups per CU at random; every shape launched twice on alternating data,
+    every word against the two calls."""
+    import torch
+
+    from maria_amd import _lib, synthetic
+
+    rng = np.random.default_rng(20261015)
+    gpu_ctx.set_option(_lib.OPT_SYNTH_TILE_ORDER, 1)
+    try:
+        for trial in range(16):
+            n_det = int(np.exp(rng.uniform(np.log(20), np.log(3000))))
+            n_layers = int(rng.integers(1, 17))
+            n_bands = int(rng.integers(1, 4))
+            fs = float(rng.choice([20.0, 50.0, 100.0, 400.0]))
+            timestep = float(rng.choice([0.1, 0.2, 0.5]))
+            duration = float(rng.uniform(4 * timestep + 0.3, 60.0 if fs < 200 else 25.0))
+            p = attach_numpy_screens(synthetic.make_problem(
+                n_det=n_det, n_bands=min(n_bands, n_det), fov_deg=float(rng.uniform(0.05, 1.0)), fs=fs, duration=duration,
+                n_layers=n_layers, side=int(rng.choice([64, 128, 256])), timestep=timestep, seed=int(rng.integers(1 << 30)),
+                gain=bool(rng.random() < 0.5)))
+            path = _path(p, gpu_ctx)
+            path.clear_flags()
+            alt = _Alternating(path)
+            flags0 = int(path.d_flags.item())
+            block_rows = int(rng.choice([256, 512, 768, 1024, 4096]))
+            chunk = int(rng.choice([1, 4, 8, 16, 32, 64]))
+            samplers = int(rng.integers(0, 9))
+            gpu_ctx.set_option(_lib.OPT_SYNTH_WGS_PER_CU, int(rng.integers(0, 6)))
+            got = torch.empty_like(alt.want[0])
+            for rep in range(2):
+                alt.select(rep)
+                got.fill_(float("nan"))
+                path.synthesize(got, block_rows=block_rows, sampler_wgs_per_cu=samplers, chunk=chunk)
+                alt.check(rep, got, (trial, rep, path.D, path.Ta, path.T, n_layers, block_rows, chunk, samplers))
+                assert int(path.d_flags.item()) == flags0, (trial, rep)  # (no MRX_FLAG_HANDOVER among them)
+            path.clear_flags()
+            del path, alt, got
+    finally:
+        gpu_ctx.set_option(_lib.OPT_SYNTH_TILE_ORDER, 0)
+        gpu_ctx.set_option(_lib.OPT_SYNTH_WGS_PER_CU, 0)
