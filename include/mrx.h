@@ -716,6 +716,55 @@ int mrx_bin_map_bucketed(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_to
                          const double* d_stokes_w, const int32_t* d_channel, int D, double* d_sum,
                          double* d_wgt, void* d_work, size_t work_bytes);
 
+/* ---- maximum-likelihood map-making (white-noise GLS, MaximumLikelihoodMapper) ---------- */
+
+/* The operators of  (P^T W P) m = P^T W d.  P is the Stokes-weighted pointing matrix that mrx_bin_map transposes, signed
+ * (no |.|): row (d, s) holds w_k(d) b_c at pixel c of plane (k, channel(d)), with the binning's pixels and float32 corner
+ * weights b_c (bit for bit: the same device code).  W is diagonal: d_weight[d][s] (or 1) times d_det_weight[d] (or 1).
+ * Maps are [n_stokes][n_channels][n_eta][n_xi] float64, the layout of mrx_bin_map's d_sum; `map` gives the grid
+ * (d_values is not read).  Pointing arguments as mrx_bin_map; MRX_OPT_POINTING_CHAIN selects the float32 chain.
+ *
+ * The forward operator, the exact transpose of mrx_bin_map's d_sum (no calibration, no time kernel: not mrx_map_sample):
+ *   d_out[d][s] = beta d_out[d][s] + alpha sum_k w_k(d) sum_c b_c d_x[k][channel(d)][pix_c(d, s)]
+ * accumulated in float64 and rounded once to float32.  beta = 0: d_out is not read.
+ *  d_x    [n_stokes][n_channels][n_eta][n_xi] float64
+ *  d_out  [D][ld_out] float32 */
+int mrx_map_project(mrx_ctx* ctx, const mrx_sky_map* map, const double* d_x, const float* d_az, const float* d_el, int T,
+                    const double* d_transform, const float* d_dx, const float* d_dy, const double* d_stokes_w,
+                    const int32_t* d_channel, int D, double alpha, double beta, float* d_out, size_t ld_out);
+
+/* The normal operator:  d_y += P^T W P d_x,  with no TOD-sized intermediate: (P x)_s is gathered per sample in float64
+ * and W (P x)_s b_c is routed to map regions and summed as mrx_bin_map_bucketed routes W D b_c.  Maps of more than 2048
+ * regions, or d_work = NULL, take float64 atomics with run merging instead.  The result equals P^T W P x to float64
+ * rounding (the order of the sums differs between the forms).
+ *  d_weight      [D][ld_weight] float32 per-sample weights, or NULL (ones)
+ *  d_det_weight  [D] float64 per-detector weights, or NULL (ones)
+ *  d_work        16-byte aligned, at least mrx_map_normal_work_bytes' minimum (one column of tiles); with less than its
+ *                full size the call walks the time axis in chunks.  The query gives 0 and 0 for maps the routed form does
+ *                not take. */
+int mrx_map_normal_work_bytes(const mrx_sky_map* map, int D, int T, size_t* min_bytes, size_t* full_bytes);
+int mrx_map_normal_apply(mrx_ctx* ctx, const mrx_sky_map* map, const double* d_x, const float* d_weight, size_t ld_weight,
+                         const double* d_det_weight, const float* d_az, const float* d_el, int T, const double* d_transform,
+                         const float* d_dx, const float* d_dy, const double* d_stokes_w, const int32_t* d_channel, int D,
+                         double* d_y, void* d_work, size_t work_bytes);
+
+/* The block diagonal of P^T W P: per pixel and channel the n_stokes x n_stokes block
+ *   d_blocks[idx(k, l)][c][p] += sum over samples at p of W b_c^2 w_k w_l,   k <= l, idx row-major over the upper triangle
+ * (n_stokes (n_stokes + 1) / 2 planes per channel: I,I  I,Q  I,U  Q,Q  Q,U  U,U for IQU), float64 atomics with run
+ * merging into the caller's (zeroed or running) planes.  Weights as mrx_map_normal_apply. */
+int mrx_bin_map_blocks(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_weight, size_t ld_weight,
+                       const double* d_det_weight, const float* d_az, const float* d_el, int T, const double* d_transform,
+                       const float* d_dx, const float* d_dy, const double* d_stokes_w, const int32_t* d_channel, int D,
+                       double* d_blocks);
+
+/* Per pixel and channel, z = H^-1 r in float64 (n_stokes <= 3, by H = L D L^T), H from mrx_bin_map_blocks' layout.
+ * A block with a pivot <= 0 (H[0][0] among them), or a reciprocal condition number 1 / (|H|_1 |H^-1|_1) below `rcond`
+ * is not solved: z = NaN there when nan_invalid, else 0 (the preconditioner's form).  d_z may be d_rhs.
+ *  d_blocks  [n_stokes (n_stokes + 1) / 2][n_channels][n_pix],  d_rhs, d_z  [n_stokes][n_channels][n_pix] float64
+ *  d_mask    [n_channels][n_pix] uint8: 1 where solved, or NULL */
+int mrx_map_block_solve(mrx_ctx* ctx, int n_stokes, int n_channels, long long n_pix, const double* d_blocks,
+                        const double* d_rhs, double rcond, int nan_invalid, double* d_z, uint8_t* d_mask);
+
 /* ---- TOD pre-processing for the mappers (tod/processing.py:91-204) --------------------- */
 
 /* remove_slope (D -= linspace(D[:, 0], D[:, -1], T), processing.py:99-105) and / or window

@@ -210,6 +210,11 @@ SIGNATURES = {
     "mrx_bin_map": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "mrx_bin_map_work_bytes": (_i, [_vp, _i, _i, _vp, _vp]),
     "mrx_bin_map_bucketed": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz]),
+    "mrx_map_project": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _d, _d, _vp, _sz]),
+    "mrx_map_normal_work_bytes": (_i, [_vp, _i, _i, _vp, _vp]),
+    "mrx_map_normal_apply": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz]),
+    "mrx_bin_map_blocks": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mrx_map_block_solve": (_i, [_vp, _i, _i, C.c_longlong, _vp, _vp, _d, _i, _vp, _vp]),
     "mrx_tod_detrend_window": (_i, [_vp, _vp, _sz, _i, _i, _i, _vp, _vp]),
     "mrx_sosfilt_chunk": (_i, []),
     "mrx_sosfilt_work_doubles": (_i, [_i, _i, _i, C.POINTER(_sz)]),

@@ -801,14 +801,56 @@ __device__ __forceinline__ void bin_corners(const MapArgs& g, const BucketArgs& 
   }
 }
 
-template <bool kChain, bool kBil, bool kW>
-// (168 registers instead of 174: measured 21.3 -> 19.7 ms)
-#ifndef MRX_BIN_WAVES
-#define MRX_BIN_WAVES 3
-#endif
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MRX_BIN_WAVES, MRX_BIN_WAVES))) void bin_bucket_kernel(MapArgs g, BinArgs b, BucketArgs k) {
+// ---- the maximum-likelihood map-maker's operators: P x, P^T W P x, the block diagonal of P^T W P ----
+// The pointing matrix is the binning's, signed: a sample's row holds w_k(d) b_c at pixel c of plane (k, channel), with
+// the pixels and float32 corner weights of axis_weights and the corner order and float64 products of bin_map_kernel.
+struct MlArgs {
+  const double* x;           // [S][C][n_eta][n_xi] the map the operator is applied to
+  const double* det_weight;  // [D] or null (ones): the per-detector factor of W
+  double* y;                 // the operator's map output: P^T W P x (added), or the blocks [S(S+1)/2][C][n_eta][n_xi]
+  float* out;                // mrx_map_project: [D][ld_out]
+  size_t ld_out;
+  double alpha, beta;
+};
+
+// a sample's pixels and corner weights, exactly as bin_map_kernel forms them: corners (e0,x0), (e1,x0), (e0,x1), (e1,x1)
+struct MlCorners {
+  int o[4];     // pixel offsets in a plane
+  double w[4];  // corner weights (nearest pixel: 1, 0, 0, 0)
+};
+
+__device__ __forceinline__ MlCorners ml_corners(const MapArgs& g, const Axis& ax_eta, const Axis& ax_xi, float ox, float oy) {
+  int e0, e1, x0, x1;
+  float pef, pxf;
+  axis_weights(ax_eta, oy, g.bilinear, e0, e1, pef);
+  axis_weights(ax_xi, ox, g.bilinear, x0, x1, pxf);
+  const double pe = (double)pef, px = (double)pxf;
+  MlCorners c;
+  c.o[0] = e0 * g.n_xi + x0; c.o[1] = e1 * g.n_xi + x0; c.o[2] = e0 * g.n_xi + x1; c.o[3] = e1 * g.n_xi + x1;
+  c.w[0] = (1.0 - pe) * (1.0 - px); c.w[1] = pe * (1.0 - px); c.w[2] = (1.0 - pe) * px; c.w[3] = pe * px;
+  return c;
+}
+
+// (P x)_s = sum_k w_k sum_c b_c x[k][chan][pix_c], float64; corners of zero weight are not read
+__device__ __forceinline__ double ml_gather(const MapArgs& g, const MlArgs& m, const DetConst& dc, int chan, const MlCorners& c) {
+  const size_t plane = (size_t)g.n_eta * g.n_xi;
+  const int corners = g.bilinear ? 4 : 1;
+  double v = 0.0;
+  for (int k = 0; k < g.S; ++k) {
+    const double* xk = m.x + ((size_t)k * g.C + chan) * plane;
+    double s = 0.0;
+    for (int q = 0; q < corners; ++q)
+      if (c.w[q] != 0.0) s = fma(c.w[q], xk[c.o[q]], s);
+    v = fma(dc.w[k], s, v);
+  }
+  return v;
+}
+
+template <bool kChain, bool kBil, bool kW, bool kNormal>
+__device__ __forceinline__ void bin_bucket_body(const MapArgs& g, const BinArgs& b, const BucketArgs& k, const MlArgs& m) {
   using Tile = BinTile<kBil>;
-  using Entry = BinEntryT<bin_entry_bytes(kBil, kW)>;
+  // the normal operator routes W (P x)_s b_c, a float64, in the 16-byte entry (its signal field holds 1)
+  using Entry = BinEntryT<kNormal ? 16 : bin_entry_bytes(kBil, kW)>;
   constexpr int kDet = Tile::kDet, kSpt = Tile::kSpt, kCorners = Tile::kCorners;
   __shared__ DetConst dets[kDet];
   __shared__ uint32_t part[kBlock];
@@ -906,6 +948,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MRX_BIN_
   for (int dl = 0; dl < nd; ++dl) {
     const int d = d0 + dl;
     const int chan = b.channel ? min(max(b.channel[d], 0), g.C - 1) : 0;
+    double det_w = 1.0;
+    if constexpr (kNormal) det_w = m.det_weight ? m.det_weight[d] : 1.0;
     uint32_t grp[kGroup];
     if constexpr (kGroup == 4) {
       const uint2 l2 = lo16[dl * kBlock + threadIdx.x];
@@ -931,8 +975,27 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MRX_BIN_
       } else {
         wc[0] = 1.0;
       }
-      const double W = (kW || kBil) && b.weight ? (double)b.weight[(size_t)d * b.ld_w + sb + q] : 1.0;
-      const float D = b.tod[(size_t)d * b.ld_tod + sb + q];
+      double W = (kW || kBil) && b.weight ? (double)b.weight[(size_t)d * b.ld_w + sb + q] : 1.0;
+      float D;
+      if constexpr (kNormal) {
+        // W (P x)_s in place of W D: the sample's pixels again -- bilinear from its offsets, nearest from its sort word
+        MlCorners pc;
+        if constexpr (kBil) {
+          const float2 o = oxy[(dl * kBlock + threadIdx.x) * kSpt + q];
+          pc = ml_corners(g, ax_eta, ax_xi, o.x, o.y);
+        } else {
+          const uint32_t wd = grp[q];
+          const int rem = (int)(wd >> 11) - chan * k.nby * k.nbx, by = rem / k.nbx, bx = rem - by * k.nbx;
+          const int e = (by << 5) + (int)((wd >> 6) & 31u), x = (bx << 6) + (int)(wd & 63u);
+          pc.o[0] = e * g.n_xi + x;
+          pc.w[0] = 1.0;
+          pc.w[1] = pc.w[2] = pc.w[3] = 0.0;
+        }
+        W = (b.weight ? (double)b.weight[(size_t)d * b.ld_w + sb + q] : 1.0) * det_w * ml_gather(g, m, dets[dl], chan, pc);
+        D = 1.0f;
+      } else {
+        D = b.tod[(size_t)d * b.ld_tod + sb + q];
+      }
 #pragma unroll
       for (int c = 0; c < kCorners; ++c) {
         const uint32_t wd = grp[q * kCorners + c];
@@ -946,6 +1009,22 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MRX_BIN_
       }
     }
   }
+}
+
+template <bool kChain, bool kBil, bool kW>
+// (168 registers instead of 174: measured 21.3 -> 19.7 ms)
+#ifndef MRX_BIN_WAVES
+#define MRX_BIN_WAVES 3
+#endif
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MRX_BIN_WAVES, MRX_BIN_WAVES))) void bin_bucket_kernel(MapArgs g, BinArgs b, BucketArgs k) {
+  bin_bucket_body<kChain, kBil, kW, false>(g, b, k, MlArgs{});
+}
+
+// pass A of mrx_map_normal_apply: W (P x)_s b_c routed as pass A of the binning routes W D b_c (without the binning's cap of
+// three waves a SIMD: the gather of (P x)_s does not fit its 168 registers)
+template <bool kChain, bool kBil>
+__global__ __launch_bounds__(kBlock) void normal_bucket_kernel(MapArgs g, BinArgs b, BucketArgs k, MlArgs m) {
+  bin_bucket_body<kChain, kBil, true, true>(g, b, k, m);
 }
 
 // between the passes: the regions by falling number of contributions (rank by counting: R <= 2048), so that pass B's
@@ -964,11 +1043,12 @@ __global__ __launch_bounds__(1024) void bin_order_kernel(const uint32_t* __restr
 
 // pass B: block (region, split): the region's segments of the split's tiles into LDS, then the
 // block of 64 x 32 pixels into the map
-template <int kEntryBytes>
-__global__ __launch_bounds__(kBlock) void bin_accumulate_kernel(MapArgs g, BinArgs b, BucketArgs k, int splits) {
+template <int kEntryBytes, bool kNormal>
+__device__ __forceinline__ void bin_accumulate_body(const MapArgs& g, const BinArgs& b, const BucketArgs& k, int splits, const MlArgs& ml) {
   using Entry = BinEntryT<kEntryBytes>;
   const Entry* entries = reinterpret_cast<const Entry*>(k.entries);
-  extern __shared__ double bin_acc[];  // [S][2][kBinRegionPx]: sum, weight
+  extern __shared__ double bin_acc[];  // [S][2][kBinRegionPx]: sum, weight (the normal operator: [S][kBinRegionPx], its sum)
+  constexpr int kPlanes = kNormal ? 1 : 2;
   __shared__ uint32_t seg_cnt[kBlock];   // a batch's non-empty segments: count,
   __shared__ uint32_t seg_base[kBlock];  // index of the first entry in the work buffer minus its place in the batch's list,
   __shared__ int seg_d0[kBlock];         // first detector of the tile,
@@ -979,7 +1059,7 @@ __global__ __launch_bounds__(kBlock) void bin_accumulate_kernel(MapArgs g, BinAr
   // under the scan's centre hold several times the samples of those at its rim (measured: 20 ms
   // against 9 ms for this kernel).  Rotating by the split spreads every column over the XCDs.
   const int r = k.order[(blockIdx.x + blockIdx.y) % (unsigned)k.R];
-  for (int i = threadIdx.x; i < g.S * 2 * kBinRegionPx; i += kBlock) bin_acc[i] = 0.0;
+  for (int i = threadIdx.x; i < g.S * kPlanes * kBinRegionPx; i += kBlock) bin_acc[i] = 0.0;
   const int per = (k.n_tiles + splits - 1) / splits;
   const int t0 = blockIdx.y * per, t1 = min(k.n_tiles, t0 + per);
   const uint32_t* row = k.tab + (size_t)r * k.n_tiles;
@@ -1043,8 +1123,12 @@ __global__ __launch_bounds__(kBlock) void bin_accumulate_kernel(MapArgs g, BinAr
         if (m[i] == 0.0) continue;  // zero weight: nothing to add (np.abs(P) entries that are 0); padding
         const uint32_t px = en[i].local & (uint32_t)(kBinRegionPx - 1);
         const double ww = en[i].weight();
-        atomicAdd(&bin_acc[(s * 2) * kBinRegionPx + px], m[i] * (ww * (double)en[i].d));
-        atomicAdd(&bin_acc[(s * 2 + 1) * kBinRegionPx + px], fabs(m[i]) * ww);
+        if constexpr (kNormal) {
+          atomicAdd(&bin_acc[s * kBinRegionPx + px], m[i] * ww);
+        } else {
+          atomicAdd(&bin_acc[(s * 2) * kBinRegionPx + px], m[i] * (ww * (double)en[i].d));
+          atomicAdd(&bin_acc[(s * 2 + 1) * kBinRegionPx + px], fabs(m[i]) * ww);
+        }
       }
     };
     // Two trips in flight.  An entry needs a second, dependent load (its detector's Stokes weight); loads return
@@ -1087,13 +1171,29 @@ __global__ __launch_bounds__(kBlock) void bin_accumulate_kernel(MapArgs g, BinAr
   for (int s = 0; s < g.S; ++s) {
     const size_t base = ((size_t)s * g.C + chan) * plane;
     for (int i = threadIdx.x; i < kBinRegionPx; i += kBlock) {
-      const double wv = bin_acc[(s * 2 + 1) * kBinRegionPx + i];
       const int e = (by << 5) + (i >> 6), x = (bx << 6) + (i & 63);
-      if (wv == 0.0 || e >= g.n_eta || x >= g.n_xi) continue;
-      atomicAdd(b.sum + base + (size_t)e * g.n_xi + x, bin_acc[(s * 2) * kBinRegionPx + i]);
-      atomicAdd(b.wgt + base + (size_t)e * g.n_xi + x, wv);
+      if constexpr (kNormal) {
+        const double v = bin_acc[s * kBinRegionPx + i];
+        if (v == 0.0 || e >= g.n_eta || x >= g.n_xi) continue;
+        atomicAdd(ml.y + base + (size_t)e * g.n_xi + x, v);
+      } else {
+        const double wv = bin_acc[(s * 2 + 1) * kBinRegionPx + i];
+        if (wv == 0.0 || e >= g.n_eta || x >= g.n_xi) continue;
+        atomicAdd(b.sum + base + (size_t)e * g.n_xi + x, bin_acc[(s * 2) * kBinRegionPx + i]);
+        atomicAdd(b.wgt + base + (size_t)e * g.n_xi + x, wv);
+      }
     }
   }
+}
+
+template <int kEntryBytes>
+__global__ __launch_bounds__(kBlock) void bin_accumulate_kernel(MapArgs g, BinArgs b, BucketArgs k, int splits) {
+  bin_accumulate_body<kEntryBytes, false>(g, b, k, splits, MlArgs{});
+}
+
+// pass B of mrx_map_normal_apply: the routed W (P x)_s b_c times w_k(d), summed per pixel in LDS, into y
+__global__ __launch_bounds__(kBlock) void normal_accumulate_kernel(MapArgs g, BinArgs b, BucketArgs k, int splits, MlArgs m) {
+  bin_accumulate_body<16, true>(g, b, k, splits, m);
 }
 
 // kKrj: the field leaves in K_RJ -- every row's four values times the row's scale, divided by den_band(el_det) exactly as
@@ -1428,6 +1528,180 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kChain ?
   }
 }
 
+// mrx_map_project: out[d][s] = beta out[d][s] + alpha (P x)_s, the tile and the pointing of bin_map_kernel
+template <bool kChain>
+__global__ __launch_bounds__(kBlock) void map_project_kernel(MapArgs g, BinArgs b, MlArgs m) {
+  __shared__ DetConst dets[kTileDet];
+  const int d0 = blockIdx.y * kTileDet;
+  const int sb = blockIdx.x * kTileSamples + threadIdx.x * kSamplesPerThread;
+  const int nd = min(kTileDet, g.D - d0);
+  if ((int)threadIdx.x < nd) dets[threadIdx.x] = make_det_const(g, d0 + threadIdx.x);
+  const Axis ax_eta = g.eta, ax_xi = g.xi;
+  SampleConst sc[kSamplesPerThread];
+#pragma unroll
+  for (int q = 0; q < kSamplesPerThread; ++q) {
+    sample_const(g, sb + q, kChain, sc[q]);
+    sc[q].s = min(max(sb + q, 0), g.T - 1);
+  }
+  __syncthreads();
+  if (sb >= g.T) return;
+  for (int dl = 0; dl < nd; ++dl) {
+    const DetConst dc = dets[dl];
+    const int d = d0 + dl;
+    const int chan = b.channel ? min(max(b.channel[d], 0), g.C - 1) : 0;
+    float* row = m.out + (size_t)d * m.ld_out;
+#pragma unroll
+    for (int q = 0; q < kSamplesPerThread; ++q) {
+      if (sb + q >= g.T) break;
+      float ox, oy, el_d;
+      sample_offsets<kChain, false>(g, dc, sc[q], ox, oy, el_d);
+      double v = m.alpha * ml_gather(g, m, dc, chan, ml_corners(g, ax_eta, ax_xi, ox, oy));
+      if (m.beta != 0.0) v = fma(m.beta, (double)row[sb + q], v);  // (beta = 0: out is not read)
+      row[sb + q] = (float)v;
+    }
+  }
+}
+
+// one run of consecutive samples with the same pixels: the corners' sums go out with one atomic per plane and corner
+template <bool kBlocks>
+__device__ __forceinline__ void ml_flush(const MapArgs& g, const MlArgs& m, const DetConst& dc, int chan, const int (&o)[4],
+                                         const double (&A)[4]) {
+  const size_t plane = (size_t)g.n_eta * g.n_xi;
+  const int corners = g.bilinear ? 4 : 1;
+  if constexpr (kBlocks) {
+    int idx = 0;  // H[k, l], k <= l, row-major
+    for (int k = 0; k < g.S; ++k)
+      for (int l = k; l < g.S; ++l, ++idx) {
+        const double wkl = dc.w[k] * dc.w[l];
+        double* h = m.y + ((size_t)idx * g.C + chan) * plane;
+        for (int c = 0; c < corners; ++c)
+          if (A[c] != 0.0 && wkl != 0.0) atomicAdd(h + o[c], wkl * A[c]);
+      }
+  } else {
+    for (int k = 0; k < g.S; ++k) {
+      if (dc.w[k] == 0.0) continue;
+      double* y = m.y + ((size_t)k * g.C + chan) * plane;
+      for (int c = 0; c < corners; ++c)
+        if (A[c] != 0.0) atomicAdd(y + o[c], dc.w[k] * A[c]);
+    }
+  }
+}
+
+// float64 atomics with run merging (the BinRun form): kBlocks -- the block diagonal, A[c] = sum W b_c^2; else the
+// normal operator, A[c] = sum W (P x)_s b_c
+template <bool kChain, bool kBlocks>
+__global__ __launch_bounds__(kBlock) void ml_atomic_kernel(MapArgs g, BinArgs b, MlArgs m) {
+  __shared__ DetConst dets[kTileDet];
+  const int d0 = blockIdx.y * kTileDet;
+  const int sb = blockIdx.x * kTileSamples + threadIdx.x * kSamplesPerThread;
+  const int nd = min(kTileDet, g.D - d0);
+  if ((int)threadIdx.x < nd) dets[threadIdx.x] = make_det_const(g, d0 + threadIdx.x);
+  const Axis ax_eta = g.eta, ax_xi = g.xi;
+  SampleConst sc[kSamplesPerThread];
+#pragma unroll
+  for (int q = 0; q < kSamplesPerThread; ++q) {
+    sample_const(g, sb + q, kChain, sc[q]);
+    sc[q].s = min(max(sb + q, 0), g.T - 1);
+  }
+  __syncthreads();
+  if (sb >= g.T) return;
+  for (int dl = 0; dl < nd; ++dl) {
+    const DetConst dc = dets[dl];
+    const int d = d0 + dl;
+    const int chan = b.channel ? min(max(b.channel[d], 0), g.C - 1) : 0;
+    const double det_w = m.det_weight ? m.det_weight[d] : 1.0;
+    int o[4] = {0, 0, 0, 0};
+    double A[4] = {0.0, 0.0, 0.0, 0.0};
+    bool open = false;
+#pragma unroll
+    for (int q = 0; q < kSamplesPerThread; ++q) {
+      if (sb + q >= g.T) break;
+      float ox, oy, el_d;
+      sample_offsets<kChain, false>(g, dc, sc[q], ox, oy, el_d);
+      const MlCorners pc = ml_corners(g, ax_eta, ax_xi, ox, oy);
+      double W = (b.weight ? (double)b.weight[(size_t)d * b.ld_w + sb + q] : 1.0) * det_w;
+      if (!kBlocks) W *= ml_gather(g, m, dc, chan, pc);
+      if (open && (pc.o[0] != o[0] || pc.o[1] != o[1] || pc.o[2] != o[2] || pc.o[3] != o[3])) {
+        ml_flush<kBlocks>(g, m, dc, chan, o, A);
+        open = false;
+      }
+      if (!open) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          o[c] = pc.o[c];
+          A[c] = 0.0;
+        }
+        open = true;
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) A[c] = fma(W, kBlocks ? pc.w[c] * pc.w[c] : pc.w[c], A[c]);
+    }
+    if (open) ml_flush<kBlocks>(g, m, dc, chan, o, A);
+  }
+}
+
+// mrx_map_block_solve: one thread per (channel, pixel); H [S(S+1)/2][n], r and z [S][n], n = C x pixels
+__global__ __launch_bounds__(kBlock) void block_solve_kernel(int S, long long n, const double* __restrict__ H, const double* r,
+                                                             double rcond, int nan_invalid, double* z, uint8_t* __restrict__ mask) {
+  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) {
+    double a[3][3] = {}, inv[3][3] = {};
+    for (int k = 0, idx = 0; k < S; ++k)
+      for (int l = k; l < S; ++l, ++idx) a[k][l] = a[l][k] = H[(size_t)idx * n + i];
+    // H = L D L^T (L unit lower triangular), then H^-1 column by column: a rank-deficient block leaves a pivot at rounding
+    // level and a huge inverse (its adjugate and determinant would both vanish, their ratio meaning nothing)
+    double L[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}}, dg[3] = {1.0, 1.0, 1.0};
+    bool ok = a[0][0] > 0.0 && isfinite(a[0][0]);
+    for (int j = 0; j < S && ok; ++j) {
+      double dj = a[j][j];
+      for (int m = 0; m < j; ++m) dj -= L[j][m] * L[j][m] * dg[m];
+      dg[j] = dj;
+      ok = dj > 0.0;
+      for (int r2 = j + 1; r2 < S && ok; ++r2) {
+        double v = a[r2][j];
+        for (int m = 0; m < j; ++m) v -= L[r2][m] * L[j][m] * dg[m];
+        L[r2][j] = v / dj;
+      }
+    }
+    if (ok) {
+      for (int c = 0; c < S; ++c) {  // solve L D L^T x = e_c
+        double y[3];
+        for (int r2 = 0; r2 < S; ++r2) {
+          double v = r2 == c ? 1.0 : 0.0;
+          for (int m = 0; m < r2; ++m) v -= L[r2][m] * y[m];
+          y[r2] = v;
+        }
+        for (int r2 = 0; r2 < S; ++r2) y[r2] /= dg[r2];
+        for (int r2 = S - 1; r2 >= 0; --r2) {
+          double v = y[r2];
+          for (int m = r2 + 1; m < S; ++m) v -= L[m][r2] * inv[m][c];
+          inv[r2][c] = v;
+        }
+      }
+      // reciprocal condition number in the 1-norm, 1 / (|H|_1 |H^-1|_1) (LAPACK's, exact for S <= 3)
+      double na = 0.0, ni = 0.0;
+      for (int l = 0; l < S; ++l) {
+        double ca = 0.0, ci = 0.0;
+        for (int k = 0; k < S; ++k) {
+          ca += fabs(a[k][l]);
+          ci += fabs(inv[k][l]);
+        }
+        na = fmax(na, ca);
+        ni = fmax(ni, ci);
+      }
+      ok = isfinite(ni) && 1.0 / (na * ni) >= rcond;
+    }
+    double rv[3] = {}, zv[3];
+    for (int k = 0; k < S; ++k) rv[k] = r[(size_t)k * n + i];
+    for (int k = 0; k < S; ++k) {
+      double v = 0.0;
+      for (int l = 0; l < S; ++l) v = fma(inv[k][l], rv[l], v);
+      zv[k] = ok ? v : (nan_invalid ? __builtin_nan("") : 0.0);
+    }
+    for (int k = 0; k < S; ++k) z[(size_t)k * n + i] = zv[k];  // (after every read of r: z may be r)
+    if (mask) mask[i] = ok ? 1 : 0;
+  }
+}
+
 }  // namespace
 
 // mrx_map_sample (krj == nullptr) and mrx_map_sample_krj
@@ -1633,18 +1907,15 @@ int mrx_map_sample_krj(mrx_ctx* ctx, const mrx_sky_map* map, const mrx_map_cal* 
   return map_sample(ctx, map, cal, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w, D, d_out, ld_out, &kj);
 }
 
-static int bin_map_args(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_tod, size_t ld_tod,
-                        const float* d_weight, size_t ld_weight, const float* d_az, const float* d_el, int T,
-                        const double* d_transform, const float* d_dx, const float* d_dy,
-                        const double* d_stokes_w, const int32_t* d_channel, int D, double* d_sum,
-                        double* d_wgt, MapArgs& g, BinArgs& b) {
-  MRX_REQUIRE(ctx, map && d_tod && d_az && d_el && d_dx && d_dy && d_stokes_w && d_sum && d_wgt, "null pointer");
+// the grid and the pointing of the binning and of the map-maker's operators
+static int map_grid_args(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_az, const float* d_el, int T,
+                         const double* d_transform, const float* d_dx, const float* d_dy, const double* d_stokes_w, int D,
+                         MapArgs& g) {
   MRX_REQUIRE(ctx, map->n_channels >= 1 && map->n_stokes >= 1 && map->n_stokes <= kMaxStokes &&
                        map->n_eta >= 2 && map->n_xi >= 2,
               "need n_channels >= 1, 1 <= n_stokes <= 4, n_eta >= 2, n_xi >= 2");
   MRX_REQUIRE(ctx, map->deta != 0.0 && map->dxi != 0.0, "map axes need a non-zero step");
   MRX_REQUIRE(ctx, (long long)map->n_eta * map->n_xi < (1LL << 31), "a map plane must hold fewer than 2^31 pixels");
-  MRX_REQUIRE(ctx, ld_tod >= (size_t)T && (!d_weight || ld_weight >= (size_t)T), "leading dimension smaller than T");
   g = MapArgs{};
   g.eta = make_axis(map->n_eta, map->eta0, map->deta);
   g.xi = make_axis(map->n_xi, map->xi0, map->dxi);
@@ -1669,6 +1940,18 @@ static int bin_map_args(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_tod
   g.stokes_w = d_stokes_w;
   g.D = D;
   g.T = T;
+  return MRX_OK;
+}
+
+static int bin_map_args(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_tod, size_t ld_tod,
+                        const float* d_weight, size_t ld_weight, const float* d_az, const float* d_el, int T,
+                        const double* d_transform, const float* d_dx, const float* d_dy,
+                        const double* d_stokes_w, const int32_t* d_channel, int D, double* d_sum,
+                        double* d_wgt, MapArgs& g, BinArgs& b) {
+  MRX_REQUIRE(ctx, map && d_tod && d_az && d_el && d_dx && d_dy && d_stokes_w && d_sum && d_wgt, "null pointer");
+  const int rc = map_grid_args(ctx, map, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w, D, g);
+  if (rc != MRX_OK) return rc;
+  MRX_REQUIRE(ctx, ld_tod >= (size_t)T && (!d_weight || ld_weight >= (size_t)T), "leading dimension smaller than T");
   b = BinArgs{d_tod, ld_tod, d_weight, ld_weight, d_channel, d_sum, d_wgt};
   return MRX_OK;
 }
@@ -1813,6 +2096,173 @@ int mrx_bin_map_bucketed(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_to
     hipLaunchKernelGGL(pass_b, dim3(k.R, sp), dim3(kBlock), lds_b, ctx->stream, g, b, k, sp);
     MRX_CHECK_LAUNCH(ctx);
   }
+  return MRX_OK;
+}
+
+// ---- the maximum-likelihood map-maker's operators ----
+
+static int ml_args(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_weight, size_t ld_weight, const double* d_det_weight,
+                   const float* d_az, const float* d_el, int T, const double* d_transform, const float* d_dx, const float* d_dy,
+                   const double* d_stokes_w, const int32_t* d_channel, int D, MapArgs& g, BinArgs& b, MlArgs& m) {
+  MRX_REQUIRE(ctx, map && d_az && d_el && d_dx && d_dy && d_stokes_w, "null pointer");
+  const int rc = map_grid_args(ctx, map, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w, D, g);
+  if (rc != MRX_OK) return rc;
+  MRX_REQUIRE(ctx, !d_weight || ld_weight >= (size_t)T, "leading dimension smaller than T");
+  MRX_REQUIRE(ctx, mrx_ceil_div(D, kTileDet) <= 65535, "D too large for one launch");
+  b = BinArgs{nullptr, 0, d_weight, ld_weight, d_channel, nullptr, nullptr};
+  m = MlArgs{};
+  m.det_weight = d_det_weight;
+  return MRX_OK;
+}
+
+int mrx_map_project(mrx_ctx* ctx, const mrx_sky_map* map, const double* d_x, const float* d_az, const float* d_el, int T,
+                    const double* d_transform, const float* d_dx, const float* d_dy, const double* d_stokes_w,
+                    const int32_t* d_channel, int D, double alpha, double beta, float* d_out, size_t ld_out) {
+  MRX_ENTER(ctx);
+  if (!ctx) return MRX_ERR_INVALID;
+  MRX_REQUIRE(ctx, D >= 0 && T >= 0, "negative size");
+  if (D == 0 || T == 0) return MRX_OK;
+  MRX_REQUIRE(ctx, d_x && d_out, "null pointer");
+  MRX_REQUIRE(ctx, ld_out >= (size_t)T, "ld_out smaller than T");
+  MapArgs g;
+  BinArgs b;
+  MlArgs m;
+  const int rc = ml_args(ctx, map, nullptr, 0, nullptr, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w, d_channel, D, g, b, m);
+  if (rc != MRX_OK) return rc;
+  m.x = d_x;
+  m.out = d_out;
+  m.ld_out = ld_out;
+  m.alpha = alpha;
+  m.beta = beta;
+  const dim3 grid(mrx_ceil_div(T, kTileSamples), mrx_ceil_div(D, kTileDet));
+  if (ctx->options[MRX_OPT_POINTING_CHAIN])
+    hipLaunchKernelGGL(map_project_kernel<true>, grid, dim3(kBlock), 0, ctx->stream, g, b, m);
+  else
+    hipLaunchKernelGGL(map_project_kernel<false>, grid, dim3(kBlock), 0, ctx->stream, g, b, m);
+  MRX_CHECK_LAUNCH(ctx);
+  return MRX_OK;
+}
+
+int mrx_map_normal_work_bytes(const mrx_sky_map* map, int D, int T, size_t* min_bytes, size_t* full_bytes) {
+  int nbx, nby;
+  if (!min_bytes || !full_bytes) return MRX_ERR_INVALID;
+  if (map && !bin_regions(map, &nbx, &nby)) {  // the atomic form: no buffer
+    *min_bytes = *full_bytes = 0;
+    return map->n_eta >= 2 && map->n_xi >= 2 && map->n_channels >= 1 ? MRX_OK : MRX_ERR_INVALID;
+  }
+  return mrx_bin_map_work_bytes(map, D, T, min_bytes, full_bytes);  // (sized for 16-byte entries: the ones this form routes)
+}
+
+int mrx_map_normal_apply(mrx_ctx* ctx, const mrx_sky_map* map, const double* d_x, const float* d_weight, size_t ld_weight,
+                         const double* d_det_weight, const float* d_az, const float* d_el, int T, const double* d_transform,
+                         const float* d_dx, const float* d_dy, const double* d_stokes_w, const int32_t* d_channel, int D,
+                         double* d_y, void* d_work, size_t work_bytes) {
+  MRX_ENTER(ctx);
+  if (!ctx) return MRX_ERR_INVALID;
+  MRX_REQUIRE(ctx, D >= 0 && T >= 0, "negative size");
+  if (D == 0 || T == 0) return MRX_OK;
+  MRX_REQUIRE(ctx, d_x && d_y, "null pointer");
+  MapArgs g;
+  BinArgs b;
+  MlArgs m;
+  const int rc = ml_args(ctx, map, d_weight, ld_weight, d_det_weight, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w,
+                         d_channel, D, g, b, m);
+  if (rc != MRX_OK) return rc;
+  m.x = d_x;
+  m.y = d_y;
+  const bool chain = ctx->options[MRX_OPT_POINTING_CHAIN] != 0;
+  BucketArgs k{};
+  k.R = bin_regions(map, &k.nbx, &k.nby);
+  if (!k.R || !d_work) {  // float64 atomics with run merging
+    const dim3 grid(mrx_ceil_div(T, kTileSamples), mrx_ceil_div(D, kTileDet));
+    if (chain)
+      hipLaunchKernelGGL((ml_atomic_kernel<true, false>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
+    else
+      hipLaunchKernelGGL((ml_atomic_kernel<false, false>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
+    MRX_CHECK_LAUNCH(ctx);
+    return MRX_OK;
+  }
+  // the routed form: mrx_bin_map_bucketed's passes and chunks, with 16-byte entries
+  const bool bil = map->bilinear != 0;
+  const BinGeometry q = bin_geometry(bil, k.R);
+  k.tile_det = q.tile_det;
+  k.tile_entries = q.tile_entries;
+  const int tiles_y = mrx_ceil_div(D, q.tile_det);
+  MRX_REQUIRE(ctx, tiles_y <= 65535, "D too large for one launch");
+  const size_t entry_bytes = 16;
+  const size_t col = (size_t)tiles_y * ((size_t)q.tile_entries * entry_bytes + (size_t)k.R * sizeof(uint32_t));
+  MRX_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(d_work) & 15u) == 0 && work_bytes >= col,
+              "work buffer: 16-byte aligned, at least mrx_map_normal_work_bytes' minimum (or NULL: the atomic form)");
+  const int cols_total = mrx_ceil_div(T, q.tile_samples);
+  int cols = (int)(work_bytes / col < (size_t)cols_total ? work_bytes / col : (size_t)cols_total);
+  if (cols < 1) cols = 1;
+  while ((long long)cols * tiles_y * q.tile_entries > (1LL << 32) - 1) cols = (cols + 1) / 2;
+  const size_t lds_b = (size_t)g.S * kBinRegionPx * sizeof(double);
+  typedef void (*BucketKernel)(MapArgs, BinArgs, BucketArgs, MlArgs);
+  const BucketKernel pass_a = bil ? (chain ? normal_bucket_kernel<true, true> : normal_bucket_kernel<false, true>)
+                                  : (chain ? normal_bucket_kernel<true, false> : normal_bucket_kernel<false, false>);
+  MRX_LDS_CAP(ctx, pass_a, q.lds_a);
+  MRX_LDS_CAP(ctx, normal_accumulate_kernel, lds_b);
+  if (!ctx->d_bin_order) MRX_HIP(ctx, hipMalloc(&ctx->d_bin_order, sizeof(uint32_t) * 2 * kBinMaxRegions));
+  k.totals = ctx->d_bin_order;
+  k.order = reinterpret_cast<const int*>(ctx->d_bin_order + kBinMaxRegions);
+  const int splits = 65536 / k.R < 1 ? 1 : 65536 / k.R;
+  for (int c0 = 0; c0 < cols_total; c0 += cols) {
+    const int nc = cols_total - c0 < cols ? cols_total - c0 : cols;
+    k.tiles_x = nc;
+    k.n_tiles = nc * tiles_y;
+    k.s0 = c0 * q.tile_samples;
+    k.s1 = (long long)(c0 + nc) * q.tile_samples < (long long)T ? (c0 + nc) * q.tile_samples : T;
+    k.entries = d_work;
+    k.tab = reinterpret_cast<uint32_t*>(static_cast<char*>(d_work) + (size_t)k.n_tiles * q.tile_entries * entry_bytes);
+    MRX_HIP(ctx, hipMemsetAsync(k.tab, 0, (size_t)k.R * k.n_tiles * sizeof(uint32_t), ctx->stream));
+    MRX_HIP(ctx, hipMemsetAsync(k.totals, 0, (size_t)k.R * sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(pass_a, dim3(nc, tiles_y), dim3(kBlock), q.lds_a, ctx->stream, g, b, k, m);
+    hipLaunchKernelGGL(bin_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, k.totals, k.R, const_cast<int*>(k.order));
+    const int sp = splits < k.n_tiles ? splits : k.n_tiles;
+    hipLaunchKernelGGL(normal_accumulate_kernel, dim3(k.R, sp), dim3(kBlock), lds_b, ctx->stream, g, b, k, sp, m);
+    MRX_CHECK_LAUNCH(ctx);
+  }
+  return MRX_OK;
+}
+
+int mrx_bin_map_blocks(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_weight, size_t ld_weight,
+                       const double* d_det_weight, const float* d_az, const float* d_el, int T, const double* d_transform,
+                       const float* d_dx, const float* d_dy, const double* d_stokes_w, const int32_t* d_channel, int D,
+                       double* d_blocks) {
+  MRX_ENTER(ctx);
+  if (!ctx) return MRX_ERR_INVALID;
+  MRX_REQUIRE(ctx, D >= 0 && T >= 0, "negative size");
+  if (D == 0 || T == 0) return MRX_OK;
+  MRX_REQUIRE(ctx, d_blocks, "null pointer");
+  MapArgs g;
+  BinArgs b;
+  MlArgs m;
+  const int rc = ml_args(ctx, map, d_weight, ld_weight, d_det_weight, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w,
+                         d_channel, D, g, b, m);
+  if (rc != MRX_OK) return rc;
+  m.y = d_blocks;
+  const dim3 grid(mrx_ceil_div(T, kTileSamples), mrx_ceil_div(D, kTileDet));
+  if (ctx->options[MRX_OPT_POINTING_CHAIN])
+    hipLaunchKernelGGL((ml_atomic_kernel<true, true>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
+  else
+    hipLaunchKernelGGL((ml_atomic_kernel<false, true>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
+  MRX_CHECK_LAUNCH(ctx);
+  return MRX_OK;
+}
+
+int mrx_map_block_solve(mrx_ctx* ctx, int n_stokes, int n_channels, long long n_pix, const double* d_blocks,
+                        const double* d_rhs, double rcond, int nan_invalid, double* d_z, uint8_t* d_mask) {
+  MRX_ENTER(ctx);
+  if (!ctx) return MRX_ERR_INVALID;
+  MRX_REQUIRE(ctx, n_stokes >= 1 && n_stokes <= 3 && n_channels >= 1 && n_pix >= 0, "need 1 <= n_stokes <= 3, n_channels >= 1");
+  if (n_pix == 0) return MRX_OK;
+  MRX_REQUIRE(ctx, d_blocks && d_rhs && d_z, "null pointer");
+  const long long n = (long long)n_channels * n_pix;
+  const unsigned blocks = (unsigned)std::min<long long>((n + kBlock - 1) / kBlock, 65536LL);
+  hipLaunchKernelGGL(block_solve_kernel, dim3(blocks), dim3(kBlock), 0, ctx->stream, n_stokes, n, d_blocks, d_rhs, rcond,
+                     nan_invalid, d_z, d_mask);
+  MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;
 }
 

@@ -2,7 +2,11 @@
 ``map = ((W * D) @ P) / (W @ |P|)`` with the Stokes-weighted pointing matrix of
 map/projection.py:134-179 -- on the device (``mrx_bin_map_bucketed`` / ``mrx_bin_map``), never
 materialising P.  ``tod_preprocessing`` runs ``maria_amd.tod_processing.process_tod`` first, as
-mappers/base.py:138 does; the map post-processing pipeline stays with maria's front end."""
+mappers/base.py:138 does; the map post-processing pipeline stays with maria's front end.
+
+``MaximumLikelihoodMapper`` (maria/mappers/ml_mapper.py): the white-noise GLS map, I, Q and U solved jointly, on the
+same grid and pointing, with the operators of DESIGN 3.12 (``mrx_bin_map_blocks``, ``mrx_map_block_solve``,
+``mrx_map_normal_apply``)."""
 
 from __future__ import annotations
 
@@ -47,13 +51,12 @@ def bin_map(ctx, sky, signal, weight, az, el, transform, dx, dy, stokes_w, chann
         ctx.call("mrx_bin_map", *args)
 
 
-class BinMapper:
-    def __init__(self, tods, center, width=None, height=None, resolution=None, stokes="I", nu=None, frame="ra/dec",
-                 units="K_RJ", degrees=True, bilinear=False, tod_preprocessing=None, map_postprocessing=None, device="cuda:0"):
-        if map_postprocessing:
-            # BinMapper.run overrides BaseMapper.run (mappers/bin_mapper.py:84 vs base.py:162-198):
-            # the reference accepts the argument and never applies it
-            logger.warning("BinMapper does not apply 'map_postprocessing' (neither does the reference's)")
+class _GridMapper:
+    """What the mappers share: the tangent-plane grid (mappers/base.py:295-301), the frame, the units, the map channels
+    and, per TOD, the device inputs of the binning's pointing."""
+
+    def _init_grid(self, tods, center, width, height, resolution, stokes, nu, frame, units, degrees, bilinear, tod_preprocessing,
+                   device):
         self.tod_preprocessing = dict(tod_preprocessing or {})  # mappers/base.py:138: tod.process(config=...)
         if frame not in ("ra/dec", "az/el"):
             raise NotImplementedError(f"frame '{frame}': only 'ra/dec' and 'az/el' are built")
@@ -76,55 +79,53 @@ class BinMapper:
         self.device = torch.device(device)
         self.products = None
 
-    def run(self):
+    def _sky(self):
+        deta, dxi = (self.eta[-1] - self.eta[0]) / (self.n_eta - 1), (self.xi[-1] - self.xi[0]) / (self.n_xi - 1)
+        return MrxSkyMap(None, len(self.nu), len(self.stokes), self.n_eta, self.n_xi, float(self.eta[0]), float(deta), float(self.xi[0]),
+                         float(dxi), float(self.center[0]), float(self.center[1]), 1 if self.bilinear else 0, 0)
+
+    def _tod_inputs(self, tod, ctx, unit_i_response=False):
+        """(signal, weight, az, el, transform, dx, dy, stokes_w, channel) of one TOD on the device; weight None for ones.
+        ``unit_i_response``: the Stokes weights over the detector's I weight (its Mueller [0, 0])."""
         from .sim import sky_transform_stack
 
         dev = self.device
-        ctx = Context(dev.index or 0)
-        ctx.set_stream(torch.cuda.current_stream(dev))
-        S, Cn = len(self.stokes), len(self.nu)
-        msum = torch.zeros((S, Cn, self.n_eta, self.n_xi), dtype=torch.float64, device=dev)
-        mwgt = torch.zeros_like(msum)
-        deta, dxi = (self.eta[-1] - self.eta[0]) / (self.n_eta - 1), (self.xi[-1] - self.xi[0]) / (self.n_xi - 1)
-        sky = MrxSkyMap(None, Cn, S, self.n_eta, self.n_xi, float(self.eta[0]), float(deta), float(self.xi[0]), float(dxi),
-                        float(self.center[0]), float(self.center[1]), 1 if self.bilinear else 0, 0)
+        dets, coords = tod.dets, tod.coords
         f32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float32)).to(dev)  # noqa: E731
-        for tod in self.tods:
-            dets, coords = tod.dets, tod.coords
-            if dets.n == 0:
-                continue
-            weight = None
-            if self.tod_preprocessing:
-                from .tod_processing import process_tod
+        weight = None
+        if self.tod_preprocessing:
+            from .tod_processing import process_tod
 
-                done = process_tod(tod, config={k: dict(v) for k, v in self.tod_preprocessing.items()}, ctx=ctx, device=dev)
-                signal = done.data["total"]
-                if not np.all(done.weight == 1.0):  # the window is the processed TOD's weight (processing.py:193)
-                    weight = torch.as_tensor(np.ascontiguousarray(done.weight, np.float32)).to(dev).expand(signal.shape[0], -1).contiguous()
-            else:
-                signal = None
-                for field in tod.data.values():  # tod.signal: the sum of the fields
-                    f = field if isinstance(field, torch.Tensor) else torch.as_tensor(field)
-                    f = f.to(dev, torch.float32)
-                    signal = f.clone() if signal is None else signal.add_(f)
-                signal = signal.contiguous()
-            transform = None
-            if self.frame == "ra/dec":
-                transform = torch.as_tensor(sky_transform_stack(coords.t, tod.metadata["latitude"], tod.metadata["longitude"]).reshape(-1, 9)).to(dev)
-            stokes_w = torch.as_tensor(np.ascontiguousarray(mueller_row(dets.gamma)[:, ["IQUV".index(s) for s in self.stokes]], np.float64)).to(dev)
-            # the nu plane whose frequency is the detector's band centre, else plane 0 (projection.py:152-155)
-            chan = np.zeros(dets.n, np.int32)
-            for k, nu in enumerate(self.nu):
-                chan[dets.band_center == nu] = k
-            d_chan = torch.as_tensor(chan).to(dev)
-            az, el = f32(coords._baz), f32(coords._bel)
-            dx, dy = f32(coords.offsets[:, 0]), f32(coords.offsets[:, 1])
-            bin_map(ctx, sky, signal, weight, az, el, transform, dx, dy, stokes_w, d_chan, msum, mwgt)
-            torch.cuda.current_stream(dev).synchronize()
-        data = (msum / mwgt).cpu().numpy()  # 0/0 = nan where nothing was observed, as numpy gives the reference
-        self.products = {"data": data, "weight": mwgt.cpu().numpy(), "sum": msum.cpu().numpy()}
+            done = process_tod(tod, config={k: dict(v) for k, v in self.tod_preprocessing.items()}, ctx=ctx, device=dev)
+            signal = done.data["total"]
+            if not np.all(done.weight == 1.0):  # the window is the processed TOD's weight (processing.py:193)
+                weight = torch.as_tensor(np.ascontiguousarray(done.weight, np.float32)).to(dev).expand(signal.shape[0], -1).contiguous()
+        else:
+            signal = None
+            for field in tod.data.values():  # tod.signal: the sum of the fields
+                f = field if isinstance(field, torch.Tensor) else torch.as_tensor(field)
+                f = f.to(dev, torch.float32)
+                signal = f.clone() if signal is None else signal.add_(f)
+            signal = signal.contiguous()
+        transform = None
+        if self.frame == "ra/dec":
+            transform = torch.as_tensor(sky_transform_stack(coords.t, tod.metadata["latitude"], tod.metadata["longitude"]).reshape(-1, 9)).to(dev)
+        row = mueller_row(dets.gamma)
+        if unit_i_response:
+            row = row / row[:, :1]
+        stokes_w = torch.as_tensor(np.ascontiguousarray(row[:, ["IQUV".index(s) for s in self.stokes]], np.float64)).to(dev)
+        # the nu plane whose frequency is the detector's band centre, else plane 0 (projection.py:152-155)
+        chan = np.zeros(dets.n, np.int32)
+        for k, nu in enumerate(self.nu):
+            chan[dets.band_center == nu] = k
+        d_chan = torch.as_tensor(chan).to(dev)
+        az, el = f32(coords._baz), f32(coords._bel)
+        dx, dy = f32(coords.offsets[:, 0]), f32(coords.offsets[:, 1])
+        return signal, weight, az, el, transform, dx, dy, stokes_w, d_chan
+
+    def _projection_map(self, data, weight):
         out = ProjectionMap.__new__(ProjectionMap)
-        out.data, out.weight = data.astype(np.float32), self.products["weight"]
+        out.data, out.weight = data.astype(np.float32), weight
         out.eta, out.xi, out.center = self.eta, self.xi, self.center
         unit = np.pi / 180 if self.degrees else 1.0
         out.x_res = out.y_res = unit * self.resolution
@@ -136,3 +137,164 @@ class BinMapper:
         if self.products is None:
             raise RuntimeError("Mapper has not been run yet!")
         return self.products["data"]
+
+
+class BinMapper(_GridMapper):
+    def __init__(self, tods, center, width=None, height=None, resolution=None, stokes="I", nu=None, frame="ra/dec",
+                 units="K_RJ", degrees=True, bilinear=False, tod_preprocessing=None, map_postprocessing=None, device="cuda:0"):
+        if map_postprocessing:
+            # BinMapper.run overrides BaseMapper.run (mappers/bin_mapper.py:84 vs base.py:162-198):
+            # the reference accepts the argument and never applies it
+            logger.warning("BinMapper does not apply 'map_postprocessing' (neither does the reference's)")
+        self._init_grid(tods, center, width, height, resolution, stokes, nu, frame, units, degrees, bilinear, tod_preprocessing, device)
+
+    def run(self):
+        dev = self.device
+        ctx = Context(dev.index or 0)
+        ctx.set_stream(torch.cuda.current_stream(dev))
+        S, Cn = len(self.stokes), len(self.nu)
+        msum = torch.zeros((S, Cn, self.n_eta, self.n_xi), dtype=torch.float64, device=dev)
+        mwgt = torch.zeros_like(msum)
+        sky = self._sky()
+        for tod in self.tods:
+            if tod.dets.n == 0:
+                continue
+            signal, weight, az, el, transform, dx, dy, stokes_w, d_chan = self._tod_inputs(tod, ctx)
+            bin_map(ctx, sky, signal, weight, az, el, transform, dx, dy, stokes_w, d_chan, msum, mwgt)
+            torch.cuda.current_stream(dev).synchronize()
+        data = (msum / mwgt).cpu().numpy()  # 0/0 = nan where nothing was observed, as numpy gives the reference
+        self.products = {"data": data, "weight": mwgt.cpu().numpy(), "sum": msum.cpu().numpy()}
+        return self._projection_map(data, self.products["weight"])
+
+
+class MaximumLikelihoodMapper(_GridMapper):
+    """The white-noise generalised-least-squares map:  m = argmin (d - P m)^T W (d - P m),  i.e. (P^T W P) m = P^T W d,
+    with P the binning's Stokes-weighted pointing matrix (signed) and W a per-detector weight (``noise_weights``) times
+    the per-sample weight of the TOD pre-processing.  I, Q and U are solved jointly: nearest-pixel pointing makes P^T W P
+    block-diagonal (one S x S block per pixel and channel) and the map is the exact per-pixel solve; bilinear pointing is
+    solved by conjugate gradients preconditioned with those blocks, from the block solve, applying P^T W P on the device
+    (``mrx_map_normal_apply``) once per TOD and iteration.  A pixel whose block is singular or has a reciprocal condition
+    number below ``rcond`` (unobserved, or seen at one polarisation angle) is left out and is NaN in the map.
+
+    The reference's class name with BinMapper's grid keywords, plus ``noise_weights`` ("inverse_variance": 1 / var of
+    each pre-processed detector row; "uniform"; or an [ndet] array), ``max_iter``, ``tol`` (on |r| / |b|) and ``rcond``.
+    Not converging is not an error: ``products["converged"]`` is False and a warning goes to the "maria" logger."""
+
+    def __init__(self, tods, center, width=None, height=None, resolution=None, stokes="IQU", nu=None, frame="ra/dec", units="K_RJ",
+                 degrees=True, bilinear=False, tod_preprocessing=None, noise_weights="inverse_variance", max_iter=100, tol=1e-6, rcond=1e-3,
+                 device="cuda:0"):
+        self._init_grid(tods, center, width, height, resolution, stokes, nu, frame, units, degrees, bilinear, tod_preprocessing, device)
+        if not stokes or len(stokes) > 3 or any(s not in "IQU" for s in stokes) or len(set(stokes)) != len(stokes):
+            raise ValueError(f"stokes '{stokes}': distinct planes of 'IQU' (the per-pixel solve takes at most three)")
+        if isinstance(noise_weights, str):
+            if noise_weights not in ("inverse_variance", "uniform"):
+                raise ValueError(f"noise_weights '{noise_weights}': 'inverse_variance', 'uniform' or an [ndet] array")
+        else:
+            noise_weights = np.asarray(noise_weights, np.float64)
+            for tod in self.tods:
+                if noise_weights.shape != (tod.dets.n,):
+                    raise ValueError(f"noise_weights has shape {noise_weights.shape}; the TOD has {tod.dets.n} detectors")
+        self.noise_weights, self.max_iter, self.tol, self.rcond = noise_weights, int(max_iter), float(tol), float(rcond)
+
+    def _det_weight(self, signal):
+        if isinstance(self.noise_weights, str):
+            if self.noise_weights == "uniform":
+                return None
+            var = signal.double().var(dim=1)
+            return torch.where(var > 0, 1.0 / var, torch.zeros_like(var)).contiguous()
+        return torch.as_tensor(self.noise_weights).to(self.device)
+
+    def run(self):
+        dev = self.device
+        ctx = Context(dev.index or 0)
+        ctx.set_stream(torch.cuda.current_stream(dev))
+        S, Cn, n_pix = len(self.stokes), len(self.nu), self.n_eta * self.n_xi
+        shape = (S, Cn, self.n_eta, self.n_xi)
+        rhs = torch.zeros(shape, dtype=torch.float64, device=dev)
+        scratch = torch.zeros_like(rhs)  # (the binning's |P| weight: not used here)
+        blocks = torch.zeros((S * (S + 1) // 2, Cn, self.n_eta, self.n_xi), dtype=torch.float64, device=dev)
+        sky = self._sky()
+        ops = []  # per TOD: the normal operator's arguments
+        for tod in self.tods:
+            if tod.dets.n == 0:
+                continue
+            # a TOD in K_RJ is calibrated per detector to a unit response to I (TOD.to divides by the Mueller [0, 0]
+            # element): its pointing matrix carries the Mueller row over that element; in pW the row itself
+            signal, weight, az, el, transform, dx, dy, stokes_w, d_chan = self._tod_inputs(tod, ctx, unit_i_response=self.units == "K_RJ")
+            det_w = self._det_weight(signal)
+            D, T = signal.shape
+            # b = P^T W d: the binning's sum, the per-detector weight folded into the sample weight
+            w_bin = weight
+            if det_w is not None:
+                w_bin = (det_w[:, None] * (1.0 if weight is None else weight.double())).float().expand(D, T).contiguous()
+            bin_map(ctx, sky, signal, w_bin, az, el, transform, dx, dy, stokes_w, d_chan, rhs, scratch)
+            point = (ptr(az), ptr(el), T, ptr(transform), ptr(dx), ptr(dy), ptr(stokes_w), ptr(d_chan), D)
+            wargs = (ptr(weight), 0 if weight is None else weight.stride(0), ptr(det_w))
+            ctx.call("mrx_bin_map_blocks", C.byref(sky), *wargs, *point, ptr(blocks))
+            if self.bilinear:
+                ops.append((signal.shape, wargs, point, (weight, det_w, az, el, transform, dx, dy, stokes_w, d_chan)))
+        solve = lambda r, nan: self._block_solve(ctx, blocks, r, nan)  # noqa: E731
+        x, mask = solve(rhs, True)
+        residuals, converged = [], True
+        if self.bilinear and ops:
+            x, residuals, converged = self._pcg(ctx, sky, ops, rhs, mask, solve)
+        x = torch.where(mask, x, torch.full_like(x, float("nan")))
+        torch.cuda.current_stream(dev).synchronize()
+        data = x.cpu().numpy()
+        self.products = {"data": data, "weight": blocks[:1].cpu().numpy(),  # H[0, 0]: [1, C, eta, xi]
+                         "blocks": blocks.cpu().numpy(), "rhs": rhs.cpu().numpy(), "residuals": np.asarray(residuals, float),
+                         "n_iter": max(len(residuals) - 1, 0), "converged": bool(converged)}
+        return self._projection_map(data, self.products["weight"])
+
+    def _block_solve(self, ctx, blocks, r, nan_invalid):
+        """z = H^-1 r per pixel and channel; the mask [S, C, eta, xi] (bool, one plane repeated) of the solved blocks."""
+        S, Cn = r.shape[:2]
+        z = torch.empty_like(r)
+        mask = torch.empty((Cn, self.n_eta, self.n_xi), dtype=torch.uint8, device=r.device)
+        ctx.call("mrx_map_block_solve", S, Cn, self.n_eta * self.n_xi, ptr(blocks), ptr(r), self.rcond, 1 if nan_invalid else 0,
+                 ptr(z), ptr(mask))
+        return z, mask.bool().unsqueeze(0).expand(r.shape)
+
+    def _pcg(self, ctx, sky, ops, rhs, mask, solve):
+        """Conjugate gradients on the solved pixels, preconditioned by the block diagonal, from the block solve."""
+        dev = rhs.device
+        need = 0
+        for shape, *_ in ops:
+            lo, full = C.c_size_t(), C.c_size_t()
+            if ctx.lib.mrx_map_normal_work_bytes(C.byref(sky), shape[0], shape[1], C.byref(lo), C.byref(full)) == 0:
+                free = torch.cuda.mem_get_info(dev)[0]
+                need = max(need, lo.value, min(full.value, BIN_WORK_LIMIT_BYTES, max(free // 2, lo.value)))
+        work = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+
+        def normal(v):
+            y = torch.zeros_like(v)
+            for _, wargs, point, _keep in ops:
+                ctx.call("mrx_map_normal_apply", C.byref(sky), ptr(v), *wargs, *point, ptr(y), ptr(work), 0 if work is None else work.numel())
+            return torch.where(mask, y, torch.zeros_like(y))
+
+        precond = lambda r: solve(r, False)[0]  # noqa: E731
+        b = torch.where(mask, rhs, torch.zeros_like(rhs))
+        b_norm = float(torch.linalg.vector_norm(b)) or 1.0
+        x = precond(b)
+        r = b - normal(x)
+        z = precond(r)
+        p = z.clone()
+        rz = float(torch.sum(r * z))
+        residuals = [float(torch.linalg.vector_norm(r)) / b_norm]
+        while residuals[-1] >= self.tol and len(residuals) <= self.max_iter:
+            Ap = normal(p)
+            alpha = rz / float(torch.sum(p * Ap))
+            x.add_(p, alpha=alpha)
+            r.sub_(Ap, alpha=alpha)
+            residuals.append(float(torch.linalg.vector_norm(r)) / b_norm)
+            if residuals[-1] < self.tol:
+                break
+            z = precond(r)
+            rz_new = float(torch.sum(r * z))
+            p = z + (rz_new / rz) * p
+            rz = rz_new
+        converged = residuals[-1] < self.tol
+        if not converged:
+            logger.warning("MaximumLikelihoodMapper: conjugate gradients stopped at |r|/|b| = %.3e after %d iterations (tol %.1e)",
+                           residuals[-1], len(residuals) - 1, self.tol)
+        return x, residuals, converged
