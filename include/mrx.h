@@ -765,6 +765,37 @@ int mrx_bin_map_blocks(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_weig
 int mrx_map_block_solve(mrx_ctx* ctx, int n_stokes, int n_channels, long long n_pix, const double* d_blocks,
                         const double* d_rhs, double rcond, int nan_invalid, double* d_z, uint8_t* d_mask);
 
+/* ---- destriping (DestripingMapper) ---------------------------------------- */
+
+/* The operators of the destriper's baseline system.  Per TOD  d = P m + F a + n:  F expands the per-detector baseline
+ * amplitudes a[d][b] to samples, baseline b covering samples [b L, min((b + 1) L, T)) (the last one may be shorter), so a
+ * detector has nb = ceil(T / L) baselines; P, W, the grid and the pointing arguments are mrx_map_normal_apply's.  Both take
+ * nearest-pixel pointing only (MRX_ERR_UNSUPPORTED for a bilinear map) and L >= 16 samples (MRX_ERR_INVALID below; L > T
+ * gives one baseline a detector); MRX_OPT_POINTING_CHAIN selects the float32 chain.
+ *
+ * The baseline reduction, F^T W mu (tod - alpha P x) in one pass:
+ *   d_y[d][b]    += sum_{s in b} W_s mu_s (d_tod[d][s] - alpha (P x)_s)
+ *   d_hits[d][b] += sum_{s in b} W_s mu_s
+ * mu_s = d_mask[channel(d)][pixel(d, s)] (the block solve's mask: 1 where solved), or 1 with d_mask = NULL.  d_tod = NULL
+ * reads no TOD (0), d_x = NULL projects no map; d_y or d_hits may be NULL (not both).  Summed per (detector, baseline) in
+ * float64, one atomic per baseline and tile of 1024 samples.
+ *  d_tod   [D][ld_tod] float32,  d_x  [n_stokes][n_channels][n_eta][n_xi] float64
+ *  d_y, d_hits  [D][nb] float64 (added to) */
+int mrx_baseline_reduce(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_tod, size_t ld_tod, const double* d_x,
+                        double alpha, const float* d_weight, size_t ld_weight, const double* d_det_weight,
+                        const uint8_t* d_mask, int L, const float* d_az, const float* d_el, int T, const double* d_transform,
+                        const float* d_dx, const float* d_dy, const double* d_stokes_w, const int32_t* d_channel, int D,
+                        double* d_y, double* d_hits);
+
+/* The baselines binned:  d_y += P^T W F a,  with no TOD-sized intermediate: W a[d][s / L] is routed to map regions and
+ * summed as mrx_map_normal_apply routes W (P x)_s.  Maps of more than 2048 regions, or d_work = NULL, take float64 atomics
+ * with run merging instead.  mrx_map_normal_work_bytes sizes d_work (the same 16-byte entries and chunks).
+ *  d_amp  [D][nb] float64,  d_y  [n_stokes][n_channels][n_eta][n_xi] float64 (added to) */
+int mrx_bin_map_baselines(mrx_ctx* ctx, const mrx_sky_map* map, const double* d_amp, int L, const float* d_weight,
+                          size_t ld_weight, const double* d_det_weight, const float* d_az, const float* d_el, int T,
+                          const double* d_transform, const float* d_dx, const float* d_dy, const double* d_stokes_w,
+                          const int32_t* d_channel, int D, double* d_y, void* d_work, size_t work_bytes);
+
 /* ---- TOD pre-processing for the mappers (tod/processing.py:91-204) --------------------- */
 
 /* remove_slope (D -= linspace(D[:, 0], D[:, -1], T), processing.py:99-105) and / or window

@@ -215,6 +215,8 @@ SIGNATURES = {
     "mrx_map_normal_apply": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz]),
     "mrx_bin_map_blocks": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "mrx_map_block_solve": (_i, [_vp, _i, _i, C.c_longlong, _vp, _vp, _d, _i, _vp, _vp]),
+    "mrx_baseline_reduce": (_i, [_vp, _vp, _vp, _sz, _vp, _d, _vp, _sz, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "mrx_bin_map_baselines": (_i, [_vp, _vp, _vp, _i, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz]),
     "mrx_tod_detrend_window": (_i, [_vp, _vp, _sz, _i, _i, _i, _vp, _vp]),
     "mrx_sosfilt_chunk": (_i, []),
     "mrx_sosfilt_work_doubles": (_i, [_i, _i, _i, C.POINTER(_sz)]),

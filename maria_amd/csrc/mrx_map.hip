@@ -811,6 +811,11 @@ struct MlArgs {
   float* out;                // mrx_map_project: [D][ld_out]
   size_t ld_out;
   double alpha, beta;
+  // the destriper's operators: baseline b of a detector covers samples [b L, min((b + 1) L, T))
+  const double* amp;         // mrx_bin_map_baselines: [D][nb] baseline amplitudes a
+  int L, nb;                 // baseline length in samples, baselines per detector ceil(T / L)
+  const uint8_t* mask;       // mrx_baseline_reduce: [C][n_eta][n_xi] 1 where the pixel's block is solved, or null (ones)
+  double* hits;              // mrx_baseline_reduce: [D][nb] sum of W mu, or null
 };
 
 // a sample's pixels and corner weights, exactly as bin_map_kernel forms them: corners (e0,x0), (e1,x0), (e0,x1), (e1,x1)
@@ -846,10 +851,15 @@ __device__ __forceinline__ double ml_gather(const MapArgs& g, const MlArgs& m, c
   return v;
 }
 
-template <bool kChain, bool kBil, bool kW, bool kNormal>
+// what pass A routes: the TOD (the binning), W (P x)_s (the normal operator) or W a[d][s / L] (the destriper's P^T W F a)
+enum BinSource { kSrcTod = 0, kSrcNormal = 1, kSrcBaselines = 2 };
+
+template <bool kChain, bool kBil, bool kW, int kSrc>
 __device__ __forceinline__ void bin_bucket_body(const MapArgs& g, const BinArgs& b, const BucketArgs& k, const MlArgs& m) {
+  constexpr bool kNormal = kSrc != kSrcTod;
   using Tile = BinTile<kBil>;
-  // the normal operator routes W (P x)_s b_c, a float64, in the 16-byte entry (its signal field holds 1)
+  // the normal operator routes W (P x)_s b_c, a float64, in the 16-byte entry (its signal field holds 1); so does the
+  // destriper's W a_b
   using Entry = BinEntryT<kNormal ? 16 : bin_entry_bytes(kBil, kW)>;
   constexpr int kDet = Tile::kDet, kSpt = Tile::kSpt, kCorners = Tile::kCorners;
   __shared__ DetConst dets[kDet];
@@ -977,7 +987,11 @@ __device__ __forceinline__ void bin_bucket_body(const MapArgs& g, const BinArgs&
       }
       double W = (kW || kBil) && b.weight ? (double)b.weight[(size_t)d * b.ld_w + sb + q] : 1.0;
       float D;
-      if constexpr (kNormal) {
+      if constexpr (kSrc == kSrcBaselines) {
+        // W a[d][s / L] in place of W D (nearest pixel only: the corner weight is 1)
+        W = (b.weight ? (double)b.weight[(size_t)d * b.ld_w + sb + q] : 1.0) * det_w * m.amp[(size_t)d * m.nb + (sb + q) / m.L];
+        D = 1.0f;
+      } else if constexpr (kNormal) {
         // W (P x)_s in place of W D: the sample's pixels again -- bilinear from its offsets, nearest from its sort word
         MlCorners pc;
         if constexpr (kBil) {
@@ -1017,14 +1031,20 @@ template <bool kChain, bool kBil, bool kW>
 #define MRX_BIN_WAVES 3
 #endif
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MRX_BIN_WAVES, MRX_BIN_WAVES))) void bin_bucket_kernel(MapArgs g, BinArgs b, BucketArgs k) {
-  bin_bucket_body<kChain, kBil, kW, false>(g, b, k, MlArgs{});
+  bin_bucket_body<kChain, kBil, kW, kSrcTod>(g, b, k, MlArgs{});
 }
 
 // pass A of mrx_map_normal_apply: W (P x)_s b_c routed as pass A of the binning routes W D b_c (without the binning's cap of
 // three waves a SIMD: the gather of (P x)_s does not fit its 168 registers)
 template <bool kChain, bool kBil>
 __global__ __launch_bounds__(kBlock) void normal_bucket_kernel(MapArgs g, BinArgs b, BucketArgs k, MlArgs m) {
-  bin_bucket_body<kChain, kBil, true, true>(g, b, k, m);
+  bin_bucket_body<kChain, kBil, true, kSrcNormal>(g, b, k, m);
+}
+
+// pass A of mrx_bin_map_baselines: W a[d][s / L] routed the same way (nearest pixel; pass B is normal_accumulate_kernel's)
+template <bool kChain>
+__global__ __launch_bounds__(kBlock) void baseline_bucket_kernel(MapArgs g, BinArgs b, BucketArgs k, MlArgs m) {
+  bin_bucket_body<kChain, false, true, kSrcBaselines>(g, b, k, m);
 }
 
 // between the passes: the regions by falling number of contributions (rank by counting: R <= 2048), so that pass B's
@@ -1562,6 +1582,110 @@ __global__ __launch_bounds__(kBlock) void map_project_kernel(MapArgs g, BinArgs 
   }
 }
 
+// ---- the destriper's baseline reduction ----
+// mrx_baseline_reduce: y[d][b] += sum_{s in b} W mu (tod_s - alpha (P x)_s), hits[d][b] += sum_{s in b} W mu, on the tile
+// and the pointing of map_project_kernel.  With L >= 16 a thread's four samples lie in at most two baselines; each wave sums
+// every baseline's run of lanes in float64 with a segmented shuffle reduction, the run's first lane adds the sum to the
+// tile's LDS row, and the tile sends one float64 atomic per (detector, baseline) it touches: none per sample.
+constexpr int kBaseMinL = 16;
+constexpr int kBaseTileSeg = kTileSamples / kBaseMinL + 2;  // baselines a tile of 1024 samples meets at most
+
+// the sums over a wave's runs of equal keys (each key's lanes contiguous): the run's first lane ends with the run's sums
+template <bool kHits>
+__device__ __forceinline__ void seg_sum(int key, double& v, double& h) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int ko = __shfl_down(key, off, 64);
+    const double vo = __shfl_down(v, off, 64);
+    double ho = 0.0;
+    if (kHits) ho = __shfl_down(h, off, 64);
+    if (lane + off < 64 && ko == key) {
+      v += vo;
+      if (kHits) h += ho;
+    }
+  }
+}
+
+template <bool kChain, bool kHits>
+__global__ __launch_bounds__(kBlock) void baseline_reduce_kernel(MapArgs g, BinArgs b, MlArgs m) {
+  __shared__ DetConst dets[kTileDet];
+  __shared__ double acc[kHits ? 2 : 1][kTileDet][kBaseTileSeg];
+  const int d0 = blockIdx.y * kTileDet;
+  const int t0 = blockIdx.x * kTileSamples;
+  const int sb = t0 + threadIdx.x * kSamplesPerThread;
+  const int nd = min(kTileDet, g.D - d0);
+  const int b0 = t0 / m.L, nseg = (min(t0 + kTileSamples, g.T) - 1) / m.L - b0 + 1;  // the tile's baselines [b0, b0 + nseg)
+  if ((int)threadIdx.x < nd) dets[threadIdx.x] = make_det_const(g, d0 + threadIdx.x);
+  for (int i = threadIdx.x; i < (kHits ? 2 : 1) * kTileDet * kBaseTileSeg; i += kBlock) (&acc[0][0][0])[i] = 0.0;
+  const bool point = m.x || m.mask;  // (uniform) the TOD alone, unmasked, needs no pixels
+  const Axis ax_eta = g.eta, ax_xi = g.xi;
+  SampleConst sc[kSamplesPerThread];
+  if (point) {
+#pragma unroll
+    for (int q = 0; q < kSamplesPerThread; ++q) {
+      sample_const(g, sb + q, kChain, sc[q]);
+      sc[q].s = min(max(sb + q, 0), g.T - 1);
+    }
+  }
+  __syncthreads();
+  // (no early exit: every lane takes part in the shuffles; lanes past T add nothing, under a key of their own)
+  const int kA = sb < g.T ? sb / m.L : 0x7ffffff0;
+  const int lane = threadIdx.x & 63;
+  const int prevA = __shfl_up(kA, 1, 64);
+  const size_t plane = (size_t)g.n_eta * g.n_xi;
+  for (int dl = 0; dl < nd; ++dl) {
+    const DetConst dc = dets[dl];
+    const int d = d0 + dl;
+    const int chan = b.channel ? min(max(b.channel[d], 0), g.C - 1) : 0;
+    const double det_w = m.det_weight ? m.det_weight[d] : 1.0;
+    double vA = 0.0, hA = 0.0, vB = 0.0, hB = 0.0;  // the samples in baseline kA, and in kA + 1
+#pragma unroll
+    for (int q = 0; q < kSamplesPerThread; ++q) {
+      const int s = sb + q;
+      if (s >= g.T) break;
+      double W = (b.weight ? (double)b.weight[(size_t)d * b.ld_w + s] : 1.0) * det_w;
+      double v = b.tod ? (double)b.tod[(size_t)d * b.ld_tod + s] : 0.0;
+      if (point) {
+        float ox, oy, el_d;
+        sample_offsets<kChain, false>(g, dc, sc[q], ox, oy, el_d);
+        const MlCorners pc = ml_corners(g, ax_eta, ax_xi, ox, oy);
+        if (m.mask && !m.mask[chan * plane + pc.o[0]]) W = 0.0;
+        if (m.x) v = fma(-m.alpha, ml_gather(g, m, dc, chan, pc), v);
+      }
+      if (s / m.L == kA) {
+        vA = fma(W, v, vA);
+        hA += W;
+      } else {
+        vB = fma(W, v, vB);
+        hB += W;
+      }
+    }
+    seg_sum<kHits>(kA, vA, hA);
+    seg_sum<kHits>(kA + 1, vB, hB);
+    // run heads: the A keys run over the wave's lanes, and so do the B keys (kA + 1 steps with kA)
+    if (lane == 0 || prevA != kA) {
+      const int j = kA - b0;
+      if (j >= 0 && j < nseg) {
+        atomicAdd(&acc[0][dl][j], vA);
+        if (kHits) atomicAdd(&acc[kHits ? 1 : 0][dl][j], hA);
+      }
+      const int jb = j + 1;
+      if (jb >= 0 && jb < nseg) {
+        atomicAdd(&acc[0][dl][jb], vB);
+        if (kHits) atomicAdd(&acc[kHits ? 1 : 0][dl][jb], hB);
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nd * nseg; i += kBlock) {
+    const int dl = i / nseg, j = i - dl * nseg;
+    const size_t at = (size_t)(d0 + dl) * m.nb + (b0 + j);
+    if (m.y && acc[0][dl][j] != 0.0) atomicAdd(m.y + at, acc[0][dl][j]);
+    if (kHits && acc[kHits ? 1 : 0][dl][j] != 0.0) atomicAdd(m.hits + at, acc[kHits ? 1 : 0][dl][j]);
+  }
+}
+
 // one run of consecutive samples with the same pixels: the corners' sums go out with one atomic per plane and corner
 template <bool kBlocks>
 __device__ __forceinline__ void ml_flush(const MapArgs& g, const MlArgs& m, const DetConst& dc, int chan, const int (&o)[4],
@@ -1587,9 +1711,9 @@ __device__ __forceinline__ void ml_flush(const MapArgs& g, const MlArgs& m, cons
   }
 }
 
-// float64 atomics with run merging (the BinRun form): kBlocks -- the block diagonal, A[c] = sum W b_c^2; else the
-// normal operator, A[c] = sum W (P x)_s b_c
-template <bool kChain, bool kBlocks>
+// float64 atomics with run merging (the BinRun form): kBlocks -- the block diagonal, A[c] = sum W b_c^2; kBase -- the
+// destriper's P^T W F a, A[c] = sum W a[d][s / L] b_c; else the normal operator, A[c] = sum W (P x)_s b_c
+template <bool kChain, bool kBlocks, bool kBase = false>
 __global__ __launch_bounds__(kBlock) void ml_atomic_kernel(MapArgs g, BinArgs b, MlArgs m) {
   __shared__ DetConst dets[kTileDet];
   const int d0 = blockIdx.y * kTileDet;
@@ -1620,7 +1744,8 @@ __global__ __launch_bounds__(kBlock) void ml_atomic_kernel(MapArgs g, BinArgs b,
       sample_offsets<kChain, false>(g, dc, sc[q], ox, oy, el_d);
       const MlCorners pc = ml_corners(g, ax_eta, ax_xi, ox, oy);
       double W = (b.weight ? (double)b.weight[(size_t)d * b.ld_w + sb + q] : 1.0) * det_w;
-      if (!kBlocks) W *= ml_gather(g, m, dc, chan, pc);
+      if (kBase) W *= m.amp[(size_t)d * m.nb + (sb + q) / m.L];
+      else if (!kBlocks) W *= ml_gather(g, m, dc, chan, pc);
       if (open && (pc.o[0] != o[0] || pc.o[1] != o[1] || pc.o[2] != o[2] || pc.o[3] != o[3])) {
         ml_flush<kBlocks>(g, m, dc, chan, o, A);
         open = false;
@@ -2143,6 +2268,52 @@ int mrx_map_project(mrx_ctx* ctx, const mrx_sky_map* map, const double* d_x, con
   return MRX_OK;
 }
 
+// the routed form of an operator that routes a float64 per sample (mrx_map_normal_apply, mrx_bin_map_baselines):
+// mrx_bin_map_bucketed's passes and chunks with 16-byte entries, pass A given, pass B normal_accumulate_kernel
+typedef void (*MlBucketKernel)(MapArgs, BinArgs, BucketArgs, MlArgs);
+static int ml_routed(mrx_ctx* ctx, const mrx_sky_map* map, const MapArgs& g, const BinArgs& b, const MlArgs& m, BucketArgs k,
+                     MlBucketKernel pass_a, void* d_work, size_t work_bytes) {
+  const int D = g.D, T = g.T;
+  const bool bil = map->bilinear != 0;
+  const BinGeometry q = bin_geometry(bil, k.R);
+  k.tile_det = q.tile_det;
+  k.tile_entries = q.tile_entries;
+  const int tiles_y = mrx_ceil_div(D, q.tile_det);
+  MRX_REQUIRE(ctx, tiles_y <= 65535, "D too large for one launch");
+  const size_t entry_bytes = 16;
+  const size_t col = (size_t)tiles_y * ((size_t)q.tile_entries * entry_bytes + (size_t)k.R * sizeof(uint32_t));
+  MRX_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(d_work) & 15u) == 0 && work_bytes >= col,
+              "work buffer: 16-byte aligned, at least mrx_map_normal_work_bytes' minimum (or NULL: the atomic form)");
+  const int cols_total = mrx_ceil_div(T, q.tile_samples);
+  int cols = (int)(work_bytes / col < (size_t)cols_total ? work_bytes / col : (size_t)cols_total);
+  if (cols < 1) cols = 1;
+  while ((long long)cols * tiles_y * q.tile_entries > (1LL << 32) - 1) cols = (cols + 1) / 2;
+  const size_t lds_b = (size_t)g.S * kBinRegionPx * sizeof(double);
+  MRX_LDS_CAP(ctx, pass_a, q.lds_a);
+  MRX_LDS_CAP(ctx, normal_accumulate_kernel, lds_b);
+  if (!ctx->d_bin_order) MRX_HIP(ctx, hipMalloc(&ctx->d_bin_order, sizeof(uint32_t) * 2 * kBinMaxRegions));
+  k.totals = ctx->d_bin_order;
+  k.order = reinterpret_cast<const int*>(ctx->d_bin_order + kBinMaxRegions);
+  const int splits = 65536 / k.R < 1 ? 1 : 65536 / k.R;
+  for (int c0 = 0; c0 < cols_total; c0 += cols) {
+    const int nc = cols_total - c0 < cols ? cols_total - c0 : cols;
+    k.tiles_x = nc;
+    k.n_tiles = nc * tiles_y;
+    k.s0 = c0 * q.tile_samples;
+    k.s1 = (long long)(c0 + nc) * q.tile_samples < (long long)T ? (c0 + nc) * q.tile_samples : T;
+    k.entries = d_work;
+    k.tab = reinterpret_cast<uint32_t*>(static_cast<char*>(d_work) + (size_t)k.n_tiles * q.tile_entries * entry_bytes);
+    MRX_HIP(ctx, hipMemsetAsync(k.tab, 0, (size_t)k.R * k.n_tiles * sizeof(uint32_t), ctx->stream));
+    MRX_HIP(ctx, hipMemsetAsync(k.totals, 0, (size_t)k.R * sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(pass_a, dim3(nc, tiles_y), dim3(kBlock), q.lds_a, ctx->stream, g, b, k, m);
+    hipLaunchKernelGGL(bin_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, k.totals, k.R, const_cast<int*>(k.order));
+    const int sp = splits < k.n_tiles ? splits : k.n_tiles;
+    hipLaunchKernelGGL(normal_accumulate_kernel, dim3(k.R, sp), dim3(kBlock), lds_b, ctx->stream, g, b, k, sp, m);
+    MRX_CHECK_LAUNCH(ctx);
+  }
+  return MRX_OK;
+}
+
 int mrx_map_normal_work_bytes(const mrx_sky_map* map, int D, int T, size_t* min_bytes, size_t* full_bytes) {
   int nbx, nby;
   if (!min_bytes || !full_bytes) return MRX_ERR_INVALID;
@@ -2182,48 +2353,11 @@ int mrx_map_normal_apply(mrx_ctx* ctx, const mrx_sky_map* map, const double* d_x
     MRX_CHECK_LAUNCH(ctx);
     return MRX_OK;
   }
-  // the routed form: mrx_bin_map_bucketed's passes and chunks, with 16-byte entries
-  const bool bil = map->bilinear != 0;
-  const BinGeometry q = bin_geometry(bil, k.R);
-  k.tile_det = q.tile_det;
-  k.tile_entries = q.tile_entries;
-  const int tiles_y = mrx_ceil_div(D, q.tile_det);
-  MRX_REQUIRE(ctx, tiles_y <= 65535, "D too large for one launch");
-  const size_t entry_bytes = 16;
-  const size_t col = (size_t)tiles_y * ((size_t)q.tile_entries * entry_bytes + (size_t)k.R * sizeof(uint32_t));
-  MRX_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(d_work) & 15u) == 0 && work_bytes >= col,
-              "work buffer: 16-byte aligned, at least mrx_map_normal_work_bytes' minimum (or NULL: the atomic form)");
-  const int cols_total = mrx_ceil_div(T, q.tile_samples);
-  int cols = (int)(work_bytes / col < (size_t)cols_total ? work_bytes / col : (size_t)cols_total);
-  if (cols < 1) cols = 1;
-  while ((long long)cols * tiles_y * q.tile_entries > (1LL << 32) - 1) cols = (cols + 1) / 2;
-  const size_t lds_b = (size_t)g.S * kBinRegionPx * sizeof(double);
   typedef void (*BucketKernel)(MapArgs, BinArgs, BucketArgs, MlArgs);
+  const bool bil = map->bilinear != 0;
   const BucketKernel pass_a = bil ? (chain ? normal_bucket_kernel<true, true> : normal_bucket_kernel<false, true>)
                                   : (chain ? normal_bucket_kernel<true, false> : normal_bucket_kernel<false, false>);
-  MRX_LDS_CAP(ctx, pass_a, q.lds_a);
-  MRX_LDS_CAP(ctx, normal_accumulate_kernel, lds_b);
-  if (!ctx->d_bin_order) MRX_HIP(ctx, hipMalloc(&ctx->d_bin_order, sizeof(uint32_t) * 2 * kBinMaxRegions));
-  k.totals = ctx->d_bin_order;
-  k.order = reinterpret_cast<const int*>(ctx->d_bin_order + kBinMaxRegions);
-  const int splits = 65536 / k.R < 1 ? 1 : 65536 / k.R;
-  for (int c0 = 0; c0 < cols_total; c0 += cols) {
-    const int nc = cols_total - c0 < cols ? cols_total - c0 : cols;
-    k.tiles_x = nc;
-    k.n_tiles = nc * tiles_y;
-    k.s0 = c0 * q.tile_samples;
-    k.s1 = (long long)(c0 + nc) * q.tile_samples < (long long)T ? (c0 + nc) * q.tile_samples : T;
-    k.entries = d_work;
-    k.tab = reinterpret_cast<uint32_t*>(static_cast<char*>(d_work) + (size_t)k.n_tiles * q.tile_entries * entry_bytes);
-    MRX_HIP(ctx, hipMemsetAsync(k.tab, 0, (size_t)k.R * k.n_tiles * sizeof(uint32_t), ctx->stream));
-    MRX_HIP(ctx, hipMemsetAsync(k.totals, 0, (size_t)k.R * sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(pass_a, dim3(nc, tiles_y), dim3(kBlock), q.lds_a, ctx->stream, g, b, k, m);
-    hipLaunchKernelGGL(bin_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, k.totals, k.R, const_cast<int*>(k.order));
-    const int sp = splits < k.n_tiles ? splits : k.n_tiles;
-    hipLaunchKernelGGL(normal_accumulate_kernel, dim3(k.R, sp), dim3(kBlock), lds_b, ctx->stream, g, b, k, sp, m);
-    MRX_CHECK_LAUNCH(ctx);
-  }
-  return MRX_OK;
+  return ml_routed(ctx, map, g, b, m, k, pass_a, d_work, work_bytes);
 }
 
 int mrx_bin_map_blocks(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_weight, size_t ld_weight,
@@ -2264,6 +2398,98 @@ int mrx_map_block_solve(mrx_ctx* ctx, int n_stokes, int n_channels, long long n_
                      nan_invalid, d_z, d_mask);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;
+}
+
+// ---- the destriper's operators ----
+
+// what the destriper's operators take: L >= 16 samples, nearest-pixel pointing
+static int baseline_check(mrx_ctx* ctx, const mrx_sky_map* map, int L) {
+  if (L < kBaseMinL) return mrx_fail(ctx, MRX_ERR_INVALID, "baseline length %d samples: at least %d", L, kBaseMinL);
+  if (map && map->bilinear) return mrx_fail(ctx, MRX_ERR_UNSUPPORTED, "the destriper's operators take nearest-pixel pointing only");
+  return MRX_OK;
+}
+
+int mrx_baseline_reduce(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_tod, size_t ld_tod, const double* d_x,
+                        double alpha, const float* d_weight, size_t ld_weight, const double* d_det_weight,
+                        const uint8_t* d_mask, int L, const float* d_az, const float* d_el, int T, const double* d_transform,
+                        const float* d_dx, const float* d_dy, const double* d_stokes_w, const int32_t* d_channel, int D,
+                        double* d_y, double* d_hits) {
+  MRX_ENTER(ctx);
+  if (!ctx) return MRX_ERR_INVALID;
+  MRX_REQUIRE(ctx, D >= 0 && T >= 0, "negative size");
+  const int brc = baseline_check(ctx, map, L);
+  if (brc != MRX_OK) return brc;
+  const int nb = (int)(((long long)T + L - 1) / L);
+  if (D == 0 || T == 0) return MRX_OK;
+  MRX_REQUIRE(ctx, d_y || d_hits, "null pointer: neither d_y nor d_hits");
+  MRX_REQUIRE(ctx, !d_tod || ld_tod >= (size_t)T, "leading dimension smaller than T");
+  MapArgs g;
+  BinArgs b;
+  MlArgs m;
+  const int rc = ml_args(ctx, map, d_weight, ld_weight, d_det_weight, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w,
+                         d_channel, D, g, b, m);
+  if (rc != MRX_OK) return rc;
+  b.tod = d_tod;
+  b.ld_tod = ld_tod;
+  m.x = d_x;
+  m.alpha = alpha;
+  m.mask = d_mask;
+  m.L = L;
+  m.nb = nb;
+  m.y = d_y;
+  m.hits = d_hits;
+  const dim3 grid(mrx_ceil_div(T, kTileSamples), mrx_ceil_div(D, kTileDet));
+  const bool chain = ctx->options[MRX_OPT_POINTING_CHAIN] != 0;
+  if (d_hits) {
+    if (chain)
+      hipLaunchKernelGGL((baseline_reduce_kernel<true, true>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
+    else
+      hipLaunchKernelGGL((baseline_reduce_kernel<false, true>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
+  } else {
+    if (chain)
+      hipLaunchKernelGGL((baseline_reduce_kernel<true, false>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
+    else
+      hipLaunchKernelGGL((baseline_reduce_kernel<false, false>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
+  }
+  MRX_CHECK_LAUNCH(ctx);
+  return MRX_OK;
+}
+
+int mrx_bin_map_baselines(mrx_ctx* ctx, const mrx_sky_map* map, const double* d_amp, int L, const float* d_weight,
+                          size_t ld_weight, const double* d_det_weight, const float* d_az, const float* d_el, int T,
+                          const double* d_transform, const float* d_dx, const float* d_dy, const double* d_stokes_w,
+                          const int32_t* d_channel, int D, double* d_y, void* d_work, size_t work_bytes) {
+  MRX_ENTER(ctx);
+  if (!ctx) return MRX_ERR_INVALID;
+  MRX_REQUIRE(ctx, D >= 0 && T >= 0, "negative size");
+  const int brc = baseline_check(ctx, map, L);
+  if (brc != MRX_OK) return brc;
+  const int nb = (int)(((long long)T + L - 1) / L);
+  if (D == 0 || T == 0) return MRX_OK;
+  MRX_REQUIRE(ctx, d_amp && d_y, "null pointer");
+  MapArgs g;
+  BinArgs b;
+  MlArgs m;
+  const int rc = ml_args(ctx, map, d_weight, ld_weight, d_det_weight, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w,
+                         d_channel, D, g, b, m);
+  if (rc != MRX_OK) return rc;
+  m.amp = d_amp;
+  m.L = L;
+  m.nb = nb;
+  m.y = d_y;
+  const bool chain = ctx->options[MRX_OPT_POINTING_CHAIN] != 0;
+  BucketArgs k{};
+  k.R = bin_regions(map, &k.nbx, &k.nby);
+  if (!k.R || !d_work) {  // float64 atomics with run merging
+    const dim3 grid(mrx_ceil_div(T, kTileSamples), mrx_ceil_div(D, kTileDet));
+    if (chain)
+      hipLaunchKernelGGL((ml_atomic_kernel<true, false, true>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
+    else
+      hipLaunchKernelGGL((ml_atomic_kernel<false, false, true>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
+    MRX_CHECK_LAUNCH(ctx);
+    return MRX_OK;
+  }
+  return ml_routed(ctx, map, g, b, m, k, chain ? baseline_bucket_kernel<true> : baseline_bucket_kernel<false>, d_work, work_bytes);
 }
 
 }  // extern "C"

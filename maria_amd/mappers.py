@@ -167,23 +167,11 @@ class BinMapper(_GridMapper):
         return self._projection_map(data, self.products["weight"])
 
 
-class MaximumLikelihoodMapper(_GridMapper):
-    """The white-noise generalised-least-squares map:  m = argmin (d - P m)^T W (d - P m),  i.e. (P^T W P) m = P^T W d,
-    with P the binning's Stokes-weighted pointing matrix (signed) and W a per-detector weight (``noise_weights``) times
-    the per-sample weight of the TOD pre-processing.  I, Q and U are solved jointly: nearest-pixel pointing makes P^T W P
-    block-diagonal (one S x S block per pixel and channel) and the map is the exact per-pixel solve; bilinear pointing is
-    solved by conjugate gradients preconditioned with those blocks, from the block solve, applying P^T W P on the device
-    (``mrx_map_normal_apply``) once per TOD and iteration.  A pixel whose block is singular or has a reciprocal condition
-    number below ``rcond`` (unobserved, or seen at one polarisation angle) is left out and is NaN in the map.
+class _GlsMapper(_GridMapper):
+    """What the white-noise GLS mappers share: the argument checks, the weights W, b = P^T W d with the block diagonal of
+    P^T W P, the block solve and preconditioned conjugate gradients."""
 
-    The reference's class name with BinMapper's grid keywords, plus ``noise_weights`` ("inverse_variance": 1 / var of
-    each pre-processed detector row; "uniform"; or an [ndet] array), ``max_iter``, ``tol`` (on |r| / |b|) and ``rcond``.
-    Not converging is not an error: ``products["converged"]`` is False and a warning goes to the "maria" logger."""
-
-    def __init__(self, tods, center, width=None, height=None, resolution=None, stokes="IQU", nu=None, frame="ra/dec", units="K_RJ",
-                 degrees=True, bilinear=False, tod_preprocessing=None, noise_weights="inverse_variance", max_iter=100, tol=1e-6, rcond=1e-3,
-                 device="cuda:0"):
-        self._init_grid(tods, center, width, height, resolution, stokes, nu, frame, units, degrees, bilinear, tod_preprocessing, device)
+    def _init_gls(self, stokes, noise_weights, max_iter, tol, rcond):
         if not stokes or len(stokes) > 3 or any(s not in "IQU" for s in stokes) or len(set(stokes)) != len(stokes):
             raise ValueError(f"stokes '{stokes}': distinct planes of 'IQU' (the per-pixel solve takes at most three)")
         if isinstance(noise_weights, str):
@@ -204,17 +192,17 @@ class MaximumLikelihoodMapper(_GridMapper):
             return torch.where(var > 0, 1.0 / var, torch.zeros_like(var)).contiguous()
         return torch.as_tensor(self.noise_weights).to(self.device)
 
-    def run(self):
+    def _normal_inputs(self, ctx, sky, keep):
+        """rhs = P^T W d and the blocks of P^T W P over the TODs; per kept TOD ``(signal, wargs, point, refs)``: the weight
+        and pointing arguments of the operators and the tensors behind them (``keep``: "none", "op" -- without the
+        signal -- or "all")."""
         dev = self.device
-        ctx = Context(dev.index or 0)
-        ctx.set_stream(torch.cuda.current_stream(dev))
-        S, Cn, n_pix = len(self.stokes), len(self.nu), self.n_eta * self.n_xi
+        S, Cn = len(self.stokes), len(self.nu)
         shape = (S, Cn, self.n_eta, self.n_xi)
         rhs = torch.zeros(shape, dtype=torch.float64, device=dev)
         scratch = torch.zeros_like(rhs)  # (the binning's |P| weight: not used here)
         blocks = torch.zeros((S * (S + 1) // 2, Cn, self.n_eta, self.n_xi), dtype=torch.float64, device=dev)
-        sky = self._sky()
-        ops = []  # per TOD: the normal operator's arguments
+        kept = []
         for tod in self.tods:
             if tod.dets.n == 0:
                 continue
@@ -231,8 +219,84 @@ class MaximumLikelihoodMapper(_GridMapper):
             point = (ptr(az), ptr(el), T, ptr(transform), ptr(dx), ptr(dy), ptr(stokes_w), ptr(d_chan), D)
             wargs = (ptr(weight), 0 if weight is None else weight.stride(0), ptr(det_w))
             ctx.call("mrx_bin_map_blocks", C.byref(sky), *wargs, *point, ptr(blocks))
-            if self.bilinear:
-                ops.append((signal.shape, wargs, point, (weight, det_w, az, el, transform, dx, dy, stokes_w, d_chan)))
+            if keep != "none":
+                kept.append((signal if keep == "all" else signal.shape, wargs, point,
+                             (weight, det_w, az, el, transform, dx, dy, stokes_w, d_chan)))
+        return rhs, blocks, kept
+
+    def _block_solve(self, ctx, blocks, r, nan_invalid):
+        """z = H^-1 r per pixel and channel; the mask [S, C, eta, xi] (bool, one plane repeated) of the solved blocks."""
+        S, Cn = r.shape[:2]
+        z = torch.empty_like(r)
+        mask = torch.empty((Cn, self.n_eta, self.n_xi), dtype=torch.uint8, device=r.device)
+        ctx.call("mrx_map_block_solve", S, Cn, self.n_eta * self.n_xi, ptr(blocks), ptr(r), self.rcond, 1 if nan_invalid else 0,
+                 ptr(z), ptr(mask))
+        return z, mask.bool().unsqueeze(0).expand(r.shape)
+
+    def _work(self, ctx, sky, shapes):
+        """The routed operators' work buffer for TODs of these [D, T] shapes (None: the atomic form)."""
+        need = 0
+        for shape in shapes:
+            lo, full = C.c_size_t(), C.c_size_t()
+            if ctx.lib.mrx_map_normal_work_bytes(C.byref(sky), shape[0], shape[1], C.byref(lo), C.byref(full)) == 0:
+                free = torch.cuda.mem_get_info(self.device)[0]
+                need = max(need, lo.value, min(full.value, BIN_WORK_LIMIT_BYTES, max(free // 2, lo.value)))
+        return torch.empty(need, dtype=torch.uint8, device=self.device) if need else None
+
+    def _cg(self, apply, precond, b):
+        """Preconditioned conjugate gradients for apply(x) = b from x = precond(b); (x, |r| / |b| per iteration, converged)."""
+        b_norm = float(torch.linalg.vector_norm(b)) or 1.0
+        x = precond(b)
+        r = b - apply(x)
+        z = precond(r)
+        p = z.clone()
+        rz = float(torch.sum(r * z))
+        residuals = [float(torch.linalg.vector_norm(r)) / b_norm]
+        while residuals[-1] >= self.tol and len(residuals) <= self.max_iter:
+            Ap = apply(p)
+            alpha = rz / float(torch.sum(p * Ap))
+            x.add_(p, alpha=alpha)
+            r.sub_(Ap, alpha=alpha)
+            residuals.append(float(torch.linalg.vector_norm(r)) / b_norm)
+            if residuals[-1] < self.tol:
+                break
+            z = precond(r)
+            rz_new = float(torch.sum(r * z))
+            p = z + (rz_new / rz) * p
+            rz = rz_new
+        converged = residuals[-1] < self.tol
+        if not converged:
+            logger.warning("%s: conjugate gradients stopped at |r|/|b| = %.3e after %d iterations (tol %.1e)", type(self).__name__,
+                           residuals[-1], len(residuals) - 1, self.tol)
+        return x, residuals, converged
+
+
+class MaximumLikelihoodMapper(_GlsMapper):
+    """The white-noise generalised-least-squares map:  m = argmin (d - P m)^T W (d - P m),  i.e. (P^T W P) m = P^T W d,
+    with P the binning's Stokes-weighted pointing matrix (signed) and W a per-detector weight (``noise_weights``) times
+    the per-sample weight of the TOD pre-processing.  I, Q and U are solved jointly: nearest-pixel pointing makes P^T W P
+    block-diagonal (one S x S block per pixel and channel) and the map is the exact per-pixel solve; bilinear pointing is
+    solved by conjugate gradients preconditioned with those blocks, from the block solve, applying P^T W P on the device
+    (``mrx_map_normal_apply``) once per TOD and iteration.  A pixel whose block is singular or has a reciprocal condition
+    number below ``rcond`` (unobserved, or seen at one polarisation angle) is left out and is NaN in the map.
+
+    The reference's class name with BinMapper's grid keywords, plus ``noise_weights`` ("inverse_variance": 1 / var of
+    each pre-processed detector row; "uniform"; or an [ndet] array), ``max_iter``, ``tol`` (on |r| / |b|) and ``rcond``.
+    Not converging is not an error: ``products["converged"]`` is False and a warning goes to the "maria" logger."""
+
+    def __init__(self, tods, center, width=None, height=None, resolution=None, stokes="IQU", nu=None, frame="ra/dec", units="K_RJ",
+                 degrees=True, bilinear=False, tod_preprocessing=None, noise_weights="inverse_variance", max_iter=100, tol=1e-6, rcond=1e-3,
+                 device="cuda:0"):
+        self._init_grid(tods, center, width, height, resolution, stokes, nu, frame, units, degrees, bilinear, tod_preprocessing, device)
+        self._init_gls(stokes, noise_weights, max_iter, tol, rcond)
+
+    def run(self):
+        dev = self.device
+        ctx = Context(dev.index or 0)
+        ctx.set_stream(torch.cuda.current_stream(dev))
+        sky = self._sky()
+        # per TOD (bilinear): the normal operator's arguments
+        rhs, blocks, ops = self._normal_inputs(ctx, sky, "op" if self.bilinear else "none")
         solve = lambda r, nan: self._block_solve(ctx, blocks, r, nan)  # noqa: E731
         x, mask = solve(rhs, True)
         residuals, converged = [], True
@@ -246,25 +310,9 @@ class MaximumLikelihoodMapper(_GridMapper):
                          "n_iter": max(len(residuals) - 1, 0), "converged": bool(converged)}
         return self._projection_map(data, self.products["weight"])
 
-    def _block_solve(self, ctx, blocks, r, nan_invalid):
-        """z = H^-1 r per pixel and channel; the mask [S, C, eta, xi] (bool, one plane repeated) of the solved blocks."""
-        S, Cn = r.shape[:2]
-        z = torch.empty_like(r)
-        mask = torch.empty((Cn, self.n_eta, self.n_xi), dtype=torch.uint8, device=r.device)
-        ctx.call("mrx_map_block_solve", S, Cn, self.n_eta * self.n_xi, ptr(blocks), ptr(r), self.rcond, 1 if nan_invalid else 0,
-                 ptr(z), ptr(mask))
-        return z, mask.bool().unsqueeze(0).expand(r.shape)
-
     def _pcg(self, ctx, sky, ops, rhs, mask, solve):
         """Conjugate gradients on the solved pixels, preconditioned by the block diagonal, from the block solve."""
-        dev = rhs.device
-        need = 0
-        for shape, *_ in ops:
-            lo, full = C.c_size_t(), C.c_size_t()
-            if ctx.lib.mrx_map_normal_work_bytes(C.byref(sky), shape[0], shape[1], C.byref(lo), C.byref(full)) == 0:
-                free = torch.cuda.mem_get_info(dev)[0]
-                need = max(need, lo.value, min(full.value, BIN_WORK_LIMIT_BYTES, max(free // 2, lo.value)))
-        work = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+        work = self._work(ctx, sky, [shape for shape, *_ in ops])
 
         def normal(v):
             y = torch.zeros_like(v)
@@ -273,28 +321,116 @@ class MaximumLikelihoodMapper(_GridMapper):
             return torch.where(mask, y, torch.zeros_like(y))
 
         precond = lambda r: solve(r, False)[0]  # noqa: E731
-        b = torch.where(mask, rhs, torch.zeros_like(rhs))
-        b_norm = float(torch.linalg.vector_norm(b)) or 1.0
-        x = precond(b)
-        r = b - normal(x)
-        z = precond(r)
-        p = z.clone()
-        rz = float(torch.sum(r * z))
-        residuals = [float(torch.linalg.vector_norm(r)) / b_norm]
-        while residuals[-1] >= self.tol and len(residuals) <= self.max_iter:
-            Ap = normal(p)
-            alpha = rz / float(torch.sum(p * Ap))
-            x.add_(p, alpha=alpha)
-            r.sub_(Ap, alpha=alpha)
-            residuals.append(float(torch.linalg.vector_norm(r)) / b_norm)
-            if residuals[-1] < self.tol:
-                break
-            z = precond(r)
-            rz_new = float(torch.sum(r * z))
-            p = z + (rz_new / rz) * p
-            rz = rz_new
-        converged = residuals[-1] < self.tol
-        if not converged:
-            logger.warning("MaximumLikelihoodMapper: conjugate gradients stopped at |r|/|b| = %.3e after %d iterations (tol %.1e)",
-                           residuals[-1], len(residuals) - 1, self.tol)
-        return x, residuals, converged
+        return self._cg(normal, precond, torch.where(mask, rhs, torch.zeros_like(rhs)))
+
+
+class DestripingMapper(_GlsMapper):
+    """The destriped map (the Madam / Keihanen--Kurki-Suonio formulation without a baseline prior): per TOD
+    d = P m + F a + n, with F expanding one offset a[d][b] per detector and baseline of ``baseline_length`` seconds
+    (L samples; the last baseline of a TOD may be shorter) and n white.  The offsets are the solution of
+
+        A a = F^T W mu (d - P m0),   A a = F^T W mu F a - F^T W mu P M^-1 P^T W F a,   M = P^T W P,
+
+    with m0 = M^-1 P^T W d the white-noise map of ``MaximumLikelihoodMapper`` and mu the mask of the solved pixels (a sample
+    in a pixel whose block is not solved takes no part), by conjugate gradients over every TOD's offsets preconditioned by
+    1 / hits, hits = F^T W mu 1 (offsets with no hits stay 0).  The map is m = m0 - M^-1 P^T W F a, NaN in unsolved pixels.
+
+    Gauge: a detector's Stokes weights w_k(d) are constant in time, so adding c w_k(d) to the offsets of every detector of
+    one map channel and subtracting c from that channel's plane k leaves the data unchanged, for each plane (for I,
+    w_I = 1 in K_RJ: a constant on every offset).  A is singular along these S directions per channel; the system is
+    consistent and CG converges.  After the solve the offsets of each channel are made hits-orthogonal to them,
+    sum hits w_k(d) a = 0 for every k (in K_RJ with I: the hits-weighted mean of the offsets is 0), and the map is formed
+    from them: each plane is the sky's up to one constant per channel, which the data cannot determine.
+
+    Operators on the device, no TOD-sized intermediate per iteration: ``mrx_bin_map_baselines`` (P^T W F a),
+    ``mrx_map_block_solve`` (M^-1) and ``mrx_baseline_reduce`` (F^T W mu (d - alpha P x), and the hits); F^T W mu F a is
+    hits times a.  Nearest-pixel pointing only.  MaximumLikelihoodMapper's keywords plus ``baseline_length`` (seconds; at
+    least 16 samples).  ``products`` adds ``baselines`` and ``hits``, one [ndet, nb] array per TOD."""
+
+    def __init__(self, tods, center, width=None, height=None, resolution=None, stokes="IQU", nu=None, frame="ra/dec", units="K_RJ",
+                 degrees=True, bilinear=False, tod_preprocessing=None, noise_weights="inverse_variance", max_iter=100, tol=1e-6, rcond=1e-3,
+                 baseline_length=1.0, device="cuda:0"):
+        if bilinear:
+            raise NotImplementedError("DestripingMapper takes nearest-pixel pointing only (bilinear=False)")
+        self._init_grid(tods, center, width, height, resolution, stokes, nu, frame, units, degrees, bilinear, tod_preprocessing, device)
+        self._init_gls(stokes, noise_weights, max_iter, tol, rcond)
+        self.baseline_length = float(baseline_length)
+        self.baseline_samples = []  # L per TOD with detectors
+        for tod in self.tods:
+            if tod.dets.n == 0:
+                continue
+            t = np.asarray(tod.coords.t, float)
+            span = t[-1] - t[0] if t.size > 1 else 0.0
+            L = round(self.baseline_length * (t.size - 1) / span) if span > 0 else 1 << 30  # (one sample: one baseline)
+            if L < 16:
+                raise ValueError(f"baseline_length {self.baseline_length} s is {L} samples at this TOD's sample rate: at least 16")
+            self.baseline_samples.append(int(min(L, 1 << 30)))
+
+    def run(self):
+        dev = self.device
+        ctx = Context(dev.index or 0)
+        ctx.set_stream(torch.cuda.current_stream(dev))
+        sky = self._sky()
+        rhs, blocks, tods = self._normal_inputs(ctx, sky, "all")
+        solve = lambda r: self._block_solve(ctx, blocks, r, False)  # noqa: E731  (0 in unsolved pixels)
+        m0, mask = solve(rhs)
+        mu = mask[0].to(torch.uint8).contiguous()  # [C, eta, xi]
+        # the offsets of all TODs in one vector, [D, nb] views per TOD
+        sizes = [(sig.shape[0], -(-sig.shape[1] // L)) for (sig, *_), L in zip(tods, self.baseline_samples)]
+        offs = np.cumsum([0] + [D * nb for D, nb in sizes])
+        views = lambda v: [v[offs[i]:offs[i + 1]].view(sizes[i]) for i in range(len(sizes))]  # noqa: E731
+        n = int(offs[-1])
+        b, hits = torch.zeros(n, dtype=torch.float64, device=dev), torch.zeros(n, dtype=torch.float64, device=dev)
+        work = self._work(ctx, sky, [sig.shape for sig, *_ in tods])
+
+        def reduce(tod, x, y, h, signal=None):
+            (_, wargs, point, _refs), L = tods[tod], self.baseline_samples[tod]
+            ctx.call("mrx_baseline_reduce", C.byref(sky), ptr(signal), 0 if signal is None else signal.stride(0), ptr(x), 1.0, *wargs,
+                     ptr(mu), L, *point, ptr(y), ptr(h))
+
+        def bin_offsets(a):  # P^T W F a
+            y = torch.zeros_like(rhs)
+            for i, ai in enumerate(views(a)):
+                _, wargs, point, _refs = tods[i]
+                ctx.call("mrx_bin_map_baselines", C.byref(sky), ptr(ai), self.baseline_samples[i], *wargs, *point, ptr(y), ptr(work),
+                         0 if work is None else work.numel())
+            return y
+
+        def apply(a):  # A a = hits a - F^T W mu P M^-1 P^T W F a
+            u = solve(bin_offsets(a))[0]
+            out = hits * a
+            for i, oi in enumerate(views(out)):
+                reduce(i, u, oi, None)
+            return out
+
+        for i, (bi, hi) in enumerate(zip(views(b), views(hits))):
+            reduce(i, m0, bi, hi, signal=tods[i][0])  # F^T W mu (d - P m0) and the hits
+        inv_hits = torch.where(hits > 0, 1.0 / hits, torch.zeros_like(hits))
+        a, residuals, converged = self._cg(apply, lambda r: inv_hits * r, b)
+        self._fix_gauge(a, hits, views, tods)
+        x = m0 - solve(bin_offsets(a))[0]
+        x = torch.where(mask, x, torch.full_like(x, float("nan")))
+        torch.cuda.current_stream(dev).synchronize()
+        data = x.cpu().numpy()
+        self.products = {"data": data, "weight": blocks[:1].cpu().numpy(), "blocks": blocks.cpu().numpy(), "rhs": rhs.cpu().numpy(),
+                         "baselines": [v.cpu().numpy() for v in views(a)], "hits": [v.cpu().numpy() for v in views(hits)],
+                         "residuals": np.asarray(residuals, float), "n_iter": max(len(residuals) - 1, 0), "converged": bool(converged)}
+        return self._projection_map(data, self.products["weight"])
+
+    def _fix_gauge(self, a, hits, views, tods):
+        """Per map channel, the offsets made hits-orthogonal to the null directions of A, g_k[d][b] = w_k(d) for every
+        Stokes plane k:  a -= sum_k c_k g_k  with  G c = n,  G_kl = sum hits g_k g_l,  n_k = sum hits g_k a."""
+        S, Cn = len(self.stokes), len(self.nu)
+        G = torch.zeros((Cn, S, S), dtype=torch.float64, device=a.device)
+        num = torch.zeros((Cn, S), dtype=torch.float64, device=a.device)
+        per_tod = []
+        for ai, hi, (_, _, _, refs) in zip(views(a), views(hits), tods):
+            sw, d_chan = refs[7], refs[8].long()
+            hs, ha = hi.sum(dim=1), (hi * ai).sum(dim=1)
+            G.index_add_(0, d_chan, sw[:, :, None] * sw[:, None, :] * hs[:, None, None])
+            num.index_add_(0, d_chan, sw * ha[:, None])
+            per_tod.append((sw, d_chan))
+        c = (torch.linalg.pinv(G, rtol=1e-12) @ num[:, :, None])[:, :, 0]  # (a channel without hits: G = 0, c = 0)
+        for ai, hi, (sw, d_chan) in zip(views(a), views(hits), per_tod):
+            shift = (sw * c[d_chan]).sum(dim=1)
+            ai.sub_(torch.where(hi > 0, shift[:, None].expand_as(ai), torch.zeros_like(ai)))  # (offsets with no hits stay 0)
