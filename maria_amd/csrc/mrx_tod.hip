@@ -181,6 +181,17 @@ __global__ __launch_bounds__(kBlock) void sos_scan_kernel(SosArgs g) {
   }
 }
 
+// np.linspace(first, last, T)[t] of float32 end points, as numpy >= 2 evaluates it: in float32,
+// step = (last - first) / (T - 1), then t * step + first, each operation rounded (no fma), the
+// last point set to `last`.  The float32 division is done in float64 and rounded once: a float64
+// quotient of two floats rounds to the correctly rounded float32 quotient.
+__device__ __forceinline__ float line_at_f32(float first, float last, int t, int T) {
+#pragma clang fp contract(off)
+  if (t == T - 1) return last;
+  const float step = T > 1 ? (float)((double)(last - first) / (double)(T - 1)) : 0.f;
+  return (float)t * step + first;
+}
+
 // remove_slope and / or window in place: v = float32(x - line); v = float32(v * w[t])
 __global__ __launch_bounds__(kBlock) void detrend_window_kernel(float* __restrict__ data, size_t ld, int D, int T,
                                                               int remove_slope, const double* __restrict__ window,
@@ -192,11 +203,7 @@ __global__ __launch_bounds__(kBlock) void detrend_window_kernel(float* __restric
   for (int d = d0; d < min(d0 + 16, D); ++d) {
     float* row = data + (size_t)d * ld;
     float v = row[t];
-    if (remove_slope) {
-      const double first = anchors[2 * d], last = anchors[2 * d + 1];
-      const double step = T > 1 ? (last - first) / (double)(T - 1) : 0.0;
-      v = (float)((double)v - line_at(first, last, step, t, T));
-    }
+    if (remove_slope) v -= line_at_f32((float)anchors[2 * d], (float)anchors[2 * d + 1], t, T);
     if (window) v = (float)((double)v * wt);
     row[t] = v;
   }

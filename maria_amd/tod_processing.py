@@ -210,14 +210,7 @@ def process_tod(tod, config=None, ctx=None, device="cuda:0", **kwargs):
         if "f_lower" in sub:
             sections.append(bessel_sos(sub["f_lower"], sample_rate, order, "high"))
         if sections:
-            sos = np.ascontiguousarray(np.concatenate(sections, axis=0), np.float64)
-            chunk = ctx.lib.mrx_sosfilt_chunk()
-            M = torch.as_tensor(np.ascontiguousarray(chunk_matrix(sos, chunk))).to(dev)
-            need = C.c_size_t()
-            ctx.lib.mrx_sosfilt_work_doubles(n_det, n_samp, len(sos), C.byref(need))
-            work = torch.empty(need.value, dtype=torch.float64, device=dev)
-            ctx.call("mrx_sosfilt", sos.ctypes.data_as(C.POINTER(C.c_double)), len(sos), ptr(M), ptr(D), D.stride(0), n_det, n_samp,
-                     1, ptr(D), D.stride(0), ptr(work))
+            sosfilt(ctx, np.concatenate(sections, axis=0), D, remove_slope=True)
         else:  # the reference removes the slope before looking for filters (processing.py:151)
             ctx.call("mrx_tod_detrend_window", ptr(D), D.stride(0), n_det, n_samp, 1, None, ptr(anchors))
         check("filter")
@@ -241,3 +234,34 @@ def process_tod(tod, config=None, ctx=None, device="cuda:0", **kwargs):
         check("remove_modes")
 
     return ProcessedTOD(tod, D, weight, config)
+
+
+SOS_MAX_SECTIONS = 8   # kMaxSections of mrx_tod.hip
+SOS_MAX_ROWS = 65535   # grid.y of one mrx_sosfilt launch
+
+
+def sosfilt(ctx, sos, D, remove_slope=False):
+    """scipy.signal.sosfilt of every row of the float32 device tensor ``D`` [n_det, T] in place,
+    optionally after remove_slope, through ``mrx_sosfilt``.  One launch takes at most
+    ``SOS_MAX_SECTIONS`` sections and ``SOS_MAX_ROWS`` rows: a longer cascade runs as
+    consecutive calls (float32 between them; only the first removes the slope), more rows as
+    row blocks."""
+    sos = np.ascontiguousarray(sos, np.float64).reshape(-1, 6)
+    n_det, n_samp = D.shape
+    if n_det == 0 or n_samp == 0:
+        return D
+    chunk = ctx.lib.mrx_sosfilt_chunk()
+    for k, s0 in enumerate(range(0, len(sos), SOS_MAX_SECTIONS)):
+        part = np.ascontiguousarray(sos[s0 : s0 + SOS_MAX_SECTIONS])
+        M = torch.as_tensor(np.ascontiguousarray(chunk_matrix(part, chunk))).to(D.device)
+        rows = min(n_det, SOS_MAX_ROWS)
+        need = C.c_size_t()
+        rc = ctx.lib.mrx_sosfilt_work_doubles(rows, n_samp, len(part), C.byref(need))
+        if rc != 0:
+            raise ValueError(f"mrx_sosfilt_work_doubles({rows}, {n_samp}, {len(part)}) failed ({rc})")
+        work = torch.empty(need.value, dtype=torch.float64, device=D.device)
+        for lo in range(0, n_det, rows):
+            blk = D[lo : lo + rows]
+            ctx.call("mrx_sosfilt", part.ctypes.data_as(C.POINTER(C.c_double)), len(part), ptr(M), ptr(blk), blk.stride(0), len(blk),
+                     n_samp, int(remove_slope and k == 0), ptr(blk), blk.stride(0), ptr(work))
+    return D

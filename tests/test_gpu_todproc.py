@@ -127,3 +127,87 @@ def test_mapper_with_preprocessing_recovers_a_map_under_atmosphere(gpu_ctx):
     raw_edge = raw_edge[np.isfinite(raw_edge)]
     snr_raw = (np.nanmean(raw[centre]) - np.nanmean(raw_edge)) / np.nanstd(raw_edge)
     assert snr_clean > 5 and snr_clean > 3 * abs(snr_raw), (snr_clean, snr_raw)
+
+
+def _check_against_oracle(config, tod, signal, t, el, gpu_ctx, label):
+    """process_tod against the oracle with test_process_tod_matches_oracle's bound; returns the
+    error over that bound's float32 term (max|ref|)."""
+    from maria_amd.tod_processing import process_tod
+    from oracle import todproc
+
+    ref, _ = todproc.process_tod(signal, t, el, {k: dict(v) for k, v in config.items()})
+    out = process_tod(tod, config={k: dict(v) for k, v in config.items()}, ctx=gpu_ctx)
+    got = out.data["total"].cpu().numpy()
+    del out
+    assert got.shape == ref.shape and got.dtype == np.float32
+    err = np.abs(got.astype(np.float64) - ref).max(axis=1)
+    tol = 2e-6 * np.abs(ref).max()
+    if "remove_modes" in config and "filter" not in config:
+        tol += 3e-6 * np.abs(signal).max()
+    print(f"[todproc] {label}: max err {err.max():.3e} = {err.max() / np.abs(ref).max():.2e} max|ref|"
+          f" = {err.max() / np.abs(signal).max():.2e} max|signal|; bound {tol:.3e}")
+    assert err.max() <= tol, (err.max(), tol, int(err.argmax()))
+    return got, ref, err, tol
+
+
+FILTER_EDGES = {"low": {"f_upper": 5.0}, "high": {"f_lower": 0.2}, "both": {"f_upper": 5.0, "f_lower": 0.2}}
+
+
+@pytest.mark.parametrize("edges", list(FILTER_EDGES))
+@pytest.mark.parametrize("order", range(8))
+def test_process_tod_filter_every_order(gpu_ctx, order, edges):
+    """The Bessel cascade has order + 1 sections per edge: both edges from order 4 on are more than
+    one mrx_sosfilt launch takes (8), and run as consecutive launches."""
+    tod, signal, t, el = _tod(seed=order)
+    _check_against_oracle({"filter": dict(FILTER_EDGES[edges], order=order)}, tod, signal, t, el, gpu_ctx, f"filter {edges} order {order}")
+
+
+def _big_tod(D, T, fs, seed=0, block=128):
+    """_tod's signal at full size with a second common mode, built in float32 row blocks (a
+    [D, T] float64 temporary of each term would be several GB of host memory).  The two common
+    modes have independent gains, so the two leading singular vectors are well separated: with
+    one, the second would be any vector of a near-degenerate white-noise spectrum, and the
+    reference's svds and the device's eigh would each pick their own."""
+    from maria_amd import synthetic
+    from maria_amd.instrument import Band, Detectors
+    from maria_amd.sim import TOD, Coordinates
+
+    rng = np.random.default_rng(seed)
+    t = 1.7e9 + np.arange(T) / fs
+    az, el = synthetic.daisy_scan(t)
+    dets = Detectors(synthetic.hex_pack(D, np.radians(0.3)), [Band(center=150e9, width=30e9, name="f150")])
+    common = (np.cumsum(rng.normal(size=T)) * 0.5).astype(np.float32)
+    second = (np.cumsum(rng.normal(size=T)) * 0.25).astype(np.float32)
+    ramp = np.linspace(0, 5, T, dtype=np.float32)
+    sig = np.empty((D, T), np.float32)
+    for lo in range(0, D, block):
+        n = min(block, D - lo)
+        gains = rng.uniform(0.8, 1.2, (n, 1)).astype(np.float32), rng.uniform(-1.0, 1.0, (n, 1)).astype(np.float32)
+        sig[lo : lo + n] = 30.0 + gains[0] * common + gains[1] * second + rng.standard_normal((n, T), np.float32) + ramp
+    coords = Coordinates(t, az, el, offsets=dets.offsets)
+    return TOD(data={"total": sig}, dets=dets, coords=coords, units="pW"), sig, t, el
+
+
+def test_process_tod_full_length_spline_blocks_and_float32_gram(gpu_ctx):
+    """1100 x 240 000 at 400 Hz: remove_spline stages 2e9 // (8 T) = 1041 rows at a time (two
+    blocks here), and D T = 2.64e8 > 2.5e8 sends remove_modes through its float32 Gram matrix --
+    the branch every full-size mapper run takes."""
+    import torch
+
+    D, T = 1100, 240_000
+    assert D > 2e9 // (8 * T) and D * T > 2.5e8
+    tod, signal, t, el = _big_tod(D, T, 400.0)
+    config = {"remove_spline": {"knot_spacing": 10.0}, "remove_modes": {"modes_to_remove": 2}}
+    _check_against_oracle(config, tod, signal, t, el, gpu_ctx, "spline + modes 1100 x 240000 (float32 Gram)")
+    torch.cuda.empty_cache()
+
+
+def test_process_tod_filter_more_rows_than_one_launch(gpu_ctx):
+    """65 536 + 37 rows: mrx_sosfilt takes at most 65 535 rows a launch (grid.y); process_tod
+    runs the filter on row blocks.  The rows of the second block are checked on their own too."""
+    D = 65_536 + 37
+    tod, signal, t, el = _tod(D=D, T=300, fs=50.0, seed=3)
+    got, ref, err, tol = _check_against_oracle({"filter": {"f_lower": 0.5, "f_upper": 10.0}}, tod, signal, t, el, gpu_ctx,
+                                               "filter 65573 x 300")
+    tail = slice(65_535 - 3, D)
+    assert err[tail].max() <= 2e-6 * np.abs(ref[tail]).max(), err[tail].max()

@@ -5,6 +5,8 @@ import json
 import os
 
 import numpy as np
+import pytest
+import scipy.signal
 
 from maria_amd import tod_processing as tp
 from oracle import todproc
@@ -60,3 +62,49 @@ def test_config_forms():
         tp.validate_process_config({"despike": {}})
     with pytest.raises(ValueError):
         tp.validate_process_config({"filter": {"cutoff": 1.0}})
+
+
+class _HostSosfilt:
+    """A stand-in for the library that runs each mrx_sosfilt call with scipy on host tensors and
+    records its (n_sections, rows, remove_slope): what tod_processing.sosfilt asks of the kernel."""
+
+    def __init__(self, work_rc=0):
+        self.calls, self.lib, self.work_rc = [], self, work_rc
+
+    def mrx_sosfilt_chunk(self):
+        return 256
+
+    def mrx_sosfilt_work_doubles(self, D, T, S, need):
+        need._obj.value = 16
+        return self.work_rc
+
+    def call(self, name, sos, S, M, d_in, ld_in, D, T, remove_slope, d_out, ld_out, work):
+        import ctypes as C
+
+        assert name == "mrx_sosfilt" and d_in.value == d_out.value and ld_in == ld_out
+        self.calls.append((S, D, remove_slope))
+        sos = np.ctypeslib.as_array(sos, shape=(S, 6)).copy()
+        rows = np.ctypeslib.as_array(C.cast(d_in.value, C.POINTER(C.c_float)), shape=(D, ld_in))
+        x = rows[:, :T].astype(np.float64)
+        if remove_slope:
+            x = todproc.remove_slope(x)
+        rows[:, :T] = scipy.signal.sosfilt(sos, x, axis=-1)
+
+
+def test_host_sosfilt_splits_long_cascades_and_many_rows():
+    """mrx_sosfilt takes at most 8 sections and 65 535 rows a launch: a 16-section cascade on
+    65 536 + 37 rows is two section groups x two row blocks, the slope removed by the first group
+    only, and equals one float64 sosfilt up to the float32 rounding between the groups."""
+    import torch
+
+    rng = np.random.default_rng(0)
+    D, T = 65_536 + 37, 40
+    x = (np.cumsum(rng.normal(size=(D, T)), axis=1) + np.linspace(0, 3, T)).astype(np.float32)
+    sos = np.concatenate([tp.bessel_sos(5.0, 50.0, 7, "low"), tp.bessel_sos(0.5, 50.0, 7, "high")])
+    host = _HostSosfilt()
+    got = tp.sosfilt(host, sos, torch.as_tensor(x.copy()), remove_slope=True).numpy()
+    assert host.calls == [(8, 65_535, 1), (8, 38, 1), (8, 65_535, 0), (8, 38, 0)]
+    ref = scipy.signal.sosfilt(sos, todproc.remove_slope(x.astype(np.float64)), axis=-1)
+    assert np.abs(got - ref).max() <= 2e-6 * np.abs(ref).max()
+    with pytest.raises(ValueError, match="work_doubles"):
+        tp.sosfilt(_HostSosfilt(work_rc=-1), sos[:4], torch.as_tensor(x[:3].copy()))
