@@ -622,82 +622,12 @@ struct BinArgs {
   double* wgt;
 };
 
-// One run of consecutive samples that share their pixels: A[c] = sum W D w_c, B[c] = sum W w_c
-// over the 4 corners c (bilinear weights w_c >= 0); flushed with one atomic per corner, Stokes
-// plane and product.
-struct BinRun {
-  int e0, e1, x0, x1;
-  double A[4], B[4];
-};
-
-__device__ __forceinline__ void flush_run(const MapArgs& g, const BinArgs& b, const DetConst& dc, int chan, const BinRun& r) {
-  const int plane = g.n_eta * g.n_xi;
-  const int o[4] = {r.e0 * g.n_xi + r.x0, r.e1 * g.n_xi + r.x0, r.e0 * g.n_xi + r.x1, r.e1 * g.n_xi + r.x1};
-  const int corners = g.bilinear ? 4 : 1;
-  for (int k = 0; k < g.S; ++k) {
-    const size_t base = ((size_t)k * g.C + chan) * plane;
-    const double m = dc.w[k];
-    for (int c = 0; c < corners; ++c) {
-      if (r.B[c] == 0.0) continue;  // zero weight: nothing to add (np.abs(P) entries that are 0)
-      atomicAdd(b.sum + base + o[c], m * r.A[c]);
-      atomicAdd(b.wgt + base + o[c], fabs(m) * r.B[c]);
-    }
-  }
+__device__ __forceinline__ int det_channel(const MapArgs& g, const BinArgs& b, int d) {  // the map channel of detector d
+  return b.channel ? min(max(b.channel[d], 0), g.C - 1) : 0;
 }
 
-template <bool kChain>
-__global__ __launch_bounds__(kBlock) void bin_map_kernel(MapArgs g, BinArgs b) {
-  __shared__ DetConst dets[kTileDet];
-  const int d0 = blockIdx.y * kTileDet;
-  const int sb = blockIdx.x * kTileSamples + threadIdx.x * kSamplesPerThread;
-  const int nd = min(kTileDet, g.D - d0);
-  if ((int)threadIdx.x < nd) dets[threadIdx.x] = make_det_const(g, d0 + threadIdx.x);
-  const Axis ax_eta = g.eta, ax_xi = g.xi;
-  SampleConst sc[kSamplesPerThread];
-#pragma unroll
-  for (int q = 0; q < kSamplesPerThread; ++q) {
-    sample_const(g, sb + q, kChain, sc[q]);
-    sc[q].s = min(max(sb + q, 0), g.T - 1);
-  }
-  __syncthreads();
-  if (sb >= g.T) return;
-  for (int dl = 0; dl < nd; ++dl) {
-    const DetConst dc = dets[dl];
-    const int d = d0 + dl;
-    const int chan = b.channel ? min(max(b.channel[d], 0), g.C - 1) : 0;
-    BinRun run;
-    bool open = false;
-#pragma unroll
-    for (int q = 0; q < kSamplesPerThread; ++q) {
-      if (sb + q >= g.T) break;
-      float ox, oy, el_d;
-      sample_offsets<kChain, false>(g, dc, sc[q], ox, oy, el_d);
-      int e0, e1, x0, x1;
-      float pef, pxf;
-      axis_weights(ax_eta, oy, g.bilinear, e0, e1, pef);
-      axis_weights(ax_xi, ox, g.bilinear, x0, x1, pxf);
-      const double pe = (double)pef, px = (double)pxf;
-      const double W = b.weight ? (double)b.weight[(size_t)d * b.ld_w + sb + q] : 1.0;
-      const double WD = W * (double)b.tod[(size_t)d * b.ld_tod + sb + q];
-      const double w[4] = {(1.0 - pe) * (1.0 - px), pe * (1.0 - px), (1.0 - pe) * px, pe * px};
-      if (open && (e0 != run.e0 || x0 != run.x0 || e1 != run.e1 || x1 != run.x1)) {
-        flush_run(g, b, dc, chan, run);
-        open = false;
-      }
-      if (!open) {
-        run.e0 = e0; run.e1 = e1; run.x0 = x0; run.x1 = x1;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) run.A[c] = run.B[c] = 0.0;
-        open = true;
-      }
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        run.A[c] = fma(WD, w[c], run.A[c]);
-        run.B[c] = fma(W, w[c], run.B[c]);
-      }
-    }
-    if (open) flush_run(g, b, dc, chan, run);
-  }
+__device__ __forceinline__ double sample_weight(const BinArgs& b, int d, int s) {  // W of sample s of detector d
+  return b.weight ? (double)b.weight[(size_t)d * b.ld_w + s] : 1.0;
 }
 
 // ---- bucketed binning: no global atomics on scattered addresses ---------------------------
@@ -784,13 +714,13 @@ __device__ __forceinline__ void bin_corners(const MapArgs& g, const BucketArgs& 
   float pef, pxf;
   axis_weights(ax_eta, oy, kBil, e0, e1, pef);
   axis_weights(ax_xi, ox, kBil, x0, x1, pxf);
-  const double pe = (double)pef, px = (double)pxf;  // the products below in float64, as bin_map_kernel forms them
+  const double pe = (double)pef, px = (double)pxf;  // the products below in float64, as ml_corners forms them
   auto pixel = [&](int e, int x) {
     const uint32_t r = (uint32_t)((chan * k.nby + (e >> 5)) * k.nbx + (x >> 6));
     return (r << 11) | (uint32_t)(((e & 31) << 6) | (x & 63));
   };
   if constexpr (kBil) {
-    // the order and the weights of bin_map_kernel: (e0,x0), (e1,x0), (e0,x1), (e1,x1)
+    // the order and the weights of ml_corners: (e0,x0), (e1,x0), (e0,x1), (e1,x1)
     word[0] = pixel(e0, x0); wc[0] = (1.0 - pe) * (1.0 - px);
     word[1] = pixel(e1, x0); wc[1] = pe * (1.0 - px);
     word[2] = pixel(e0, x1); wc[2] = (1.0 - pe) * px;
@@ -803,7 +733,7 @@ __device__ __forceinline__ void bin_corners(const MapArgs& g, const BucketArgs& 
 
 // ---- the maximum-likelihood map-maker's operators: P x, P^T W P x, the block diagonal of P^T W P ----
 // The pointing matrix is the binning's, signed: a sample's row holds w_k(d) b_c at pixel c of plane (k, channel), with
-// the pixels and float32 corner weights of axis_weights and the corner order and float64 products of bin_map_kernel.
+// the pixels and float32 corner weights of axis_weights and the corner order and float64 products of ml_corners.
 struct MlArgs {
   const double* x;           // [S][C][n_eta][n_xi] the map the operator is applied to
   const double* det_weight;  // [D] or null (ones): the per-detector factor of W
@@ -818,7 +748,10 @@ struct MlArgs {
   double* hits;              // mrx_baseline_reduce: [D][nb] sum of W mu, or null
 };
 
-// a sample's pixels and corner weights, exactly as bin_map_kernel forms them: corners (e0,x0), (e1,x0), (e0,x1), (e1,x1)
+__device__ __forceinline__ double det_weight(const MlArgs& m, int d) { return m.det_weight ? m.det_weight[d] : 1.0; }
+
+// a sample's pixels and corner weights (in float64, from axis_weights' float32 ones): corners (e0,x0), (e1,x0), (e0,x1),
+// (e1,x1).  The pixels are the key of a run of samples in bin_atomic_kernel.
 struct MlCorners {
   int o[4];     // pixel offsets in a plane
   double w[4];  // corner weights (nearest pixel: 1, 0, 0, 0)
@@ -851,8 +784,9 @@ __device__ __forceinline__ double ml_gather(const MapArgs& g, const MlArgs& m, c
   return v;
 }
 
-// what pass A routes: the TOD (the binning), W (P x)_s (the normal operator) or W a[d][s / L] (the destriper's P^T W F a)
-enum BinSource { kSrcTod = 0, kSrcNormal = 1, kSrcBaselines = 2 };
+// what pass A and bin_atomic_kernel bin: the TOD (the binning), W (P x)_s (the normal operator), W a[d][s / L] (the
+// destriper's P^T W F a) or W b_c (the block diagonal of P^T W P: bin_atomic_kernel only)
+enum BinSource { kSrcTod = 0, kSrcNormal = 1, kSrcBaselines = 2, kSrcBlocks = 3 };
 
 template <bool kChain, bool kBil, bool kW, int kSrc>
 __device__ __forceinline__ void bin_bucket_body(const MapArgs& g, const BinArgs& b, const BucketArgs& k, const MlArgs& m) {
@@ -896,7 +830,7 @@ __device__ __forceinline__ void bin_bucket_body(const MapArgs& g, const BinArgs&
   for (int dl = 0; dl < nd; ++dl) {
     const DetConst dc = dets[dl];
     const int d = d0 + dl;
-    const int chan = b.channel ? min(max(b.channel[d], 0), g.C - 1) : 0;
+    const int chan = det_channel(g, b, d);
     uint32_t grp[kGroup];
 #pragma unroll
     for (int q = 0; q < kSpt; ++q) {
@@ -957,9 +891,9 @@ __device__ __forceinline__ void bin_bucket_body(const MapArgs& g, const BinArgs&
   Entry* slot = reinterpret_cast<Entry*>(k.entries) + (size_t)tile * Tile::kEntries;
   for (int dl = 0; dl < nd; ++dl) {
     const int d = d0 + dl;
-    const int chan = b.channel ? min(max(b.channel[d], 0), g.C - 1) : 0;
+    const int chan = det_channel(g, b, d);
     double det_w = 1.0;
-    if constexpr (kNormal) det_w = m.det_weight ? m.det_weight[d] : 1.0;
+    if constexpr (kNormal) det_w = det_weight(m, d);
     uint32_t grp[kGroup];
     if constexpr (kGroup == 4) {
       const uint2 l2 = lo16[dl * kBlock + threadIdx.x];
@@ -985,11 +919,11 @@ __device__ __forceinline__ void bin_bucket_body(const MapArgs& g, const BinArgs&
       } else {
         wc[0] = 1.0;
       }
-      double W = (kW || kBil) && b.weight ? (double)b.weight[(size_t)d * b.ld_w + sb + q] : 1.0;
+      double W = kW || kBil ? sample_weight(b, d, sb + q) : 1.0;
       float D;
       if constexpr (kSrc == kSrcBaselines) {
         // W a[d][s / L] in place of W D (nearest pixel only: the corner weight is 1)
-        W = (b.weight ? (double)b.weight[(size_t)d * b.ld_w + sb + q] : 1.0) * det_w * m.amp[(size_t)d * m.nb + (sb + q) / m.L];
+        W = sample_weight(b, d, sb + q) * det_w * m.amp[(size_t)d * m.nb + (sb + q) / m.L];
         D = 1.0f;
       } else if constexpr (kNormal) {
         // W (P x)_s in place of W D: the sample's pixels again -- bilinear from its offsets, nearest from its sort word
@@ -1005,7 +939,7 @@ __device__ __forceinline__ void bin_bucket_body(const MapArgs& g, const BinArgs&
           pc.w[0] = 1.0;
           pc.w[1] = pc.w[2] = pc.w[3] = 0.0;
         }
-        W = (b.weight ? (double)b.weight[(size_t)d * b.ld_w + sb + q] : 1.0) * det_w * ml_gather(g, m, dets[dl], chan, pc);
+        W = sample_weight(b, d, sb + q) * det_w * ml_gather(g, m, dets[dl], chan, pc);
         D = 1.0f;
       } else {
         D = b.tod[(size_t)d * b.ld_tod + sb + q];
@@ -1025,12 +959,13 @@ __device__ __forceinline__ void bin_bucket_body(const MapArgs& g, const BinArgs&
   }
 }
 
+// (the MlArgs of every pass A and pass B: the one signature of routed_bin's kernels; the binning has no use for it)
 template <bool kChain, bool kBil, bool kW>
 // (168 registers instead of 174: measured 21.3 -> 19.7 ms)
 #ifndef MRX_BIN_WAVES
 #define MRX_BIN_WAVES 3
 #endif
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MRX_BIN_WAVES, MRX_BIN_WAVES))) void bin_bucket_kernel(MapArgs g, BinArgs b, BucketArgs k) {
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MRX_BIN_WAVES, MRX_BIN_WAVES))) void bin_bucket_kernel(MapArgs g, BinArgs b, BucketArgs k, MlArgs) {
   bin_bucket_body<kChain, kBil, kW, kSrcTod>(g, b, k, MlArgs{});
 }
 
@@ -1207,7 +1142,7 @@ __device__ __forceinline__ void bin_accumulate_body(const MapArgs& g, const BinA
 }
 
 template <int kEntryBytes>
-__global__ __launch_bounds__(kBlock) void bin_accumulate_kernel(MapArgs g, BinArgs b, BucketArgs k, int splits) {
+__global__ __launch_bounds__(kBlock) void bin_accumulate_kernel(MapArgs g, BinArgs b, BucketArgs k, int splits, MlArgs) {
   bin_accumulate_body<kEntryBytes, false>(g, b, k, splits, MlArgs{});
 }
 
@@ -1548,43 +1483,60 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kChain ?
   }
 }
 
-// mrx_map_project: out[d][s] = beta out[d][s] + alpha (P x)_s, the tile and the pointing of bin_map_kernel
+// The tile of the atomic operators (bin_atomic_kernel, map_project_kernel, baseline_reduce_kernel): 16 detectors x 1024
+// samples, four consecutive samples a thread.  The rows' constants go to the kernel's LDS (dets), the thread's samples'
+// to registers (none without point), then the barrier.
+template <bool kChain>
+struct MapTile {
+  int d0, nd, sb;  // the tile's first detector and its rows, the thread's first sample
+  SampleConst sc[kSamplesPerThread];
+  __device__ __forceinline__ MapTile(const MapArgs& g, DetConst* dets, bool point = true) {
+    d0 = blockIdx.y * kTileDet;
+    nd = min(kTileDet, g.D - d0);
+    sb = blockIdx.x * kTileSamples + threadIdx.x * kSamplesPerThread;
+    if ((int)threadIdx.x < nd) dets[threadIdx.x] = make_det_const(g, d0 + threadIdx.x);
+    if (point) {
+#pragma unroll
+      for (int q = 0; q < kSamplesPerThread; ++q) {
+        sample_const(g, sb + q, kChain, sc[q]);
+        sc[q].s = min(max(sb + q, 0), g.T - 1);
+      }
+    }
+    __syncthreads();
+  }
+  // the pixels and corner weights of the thread's sample q in row dc
+  __device__ __forceinline__ MlCorners corners(const MapArgs& g, const DetConst& dc, int q) const {
+    float ox, oy, el_d;
+    sample_offsets<kChain, false>(g, dc, sc[q], ox, oy, el_d);
+    return ml_corners(g, g.eta, g.xi, ox, oy);
+  }
+};
+
+// mrx_map_project: out[d][s] = beta out[d][s] + alpha (P x)_s
 template <bool kChain>
 __global__ __launch_bounds__(kBlock) void map_project_kernel(MapArgs g, BinArgs b, MlArgs m) {
   __shared__ DetConst dets[kTileDet];
-  const int d0 = blockIdx.y * kTileDet;
-  const int sb = blockIdx.x * kTileSamples + threadIdx.x * kSamplesPerThread;
-  const int nd = min(kTileDet, g.D - d0);
-  if ((int)threadIdx.x < nd) dets[threadIdx.x] = make_det_const(g, d0 + threadIdx.x);
-  const Axis ax_eta = g.eta, ax_xi = g.xi;
-  SampleConst sc[kSamplesPerThread];
-#pragma unroll
-  for (int q = 0; q < kSamplesPerThread; ++q) {
-    sample_const(g, sb + q, kChain, sc[q]);
-    sc[q].s = min(max(sb + q, 0), g.T - 1);
-  }
-  __syncthreads();
-  if (sb >= g.T) return;
-  for (int dl = 0; dl < nd; ++dl) {
+  const MapTile<kChain> t(g, dets);
+  if (t.sb >= g.T) return;
+  for (int dl = 0; dl < t.nd; ++dl) {
     const DetConst dc = dets[dl];
-    const int d = d0 + dl;
-    const int chan = b.channel ? min(max(b.channel[d], 0), g.C - 1) : 0;
+    const int d = t.d0 + dl;
+    const int chan = det_channel(g, b, d);
     float* row = m.out + (size_t)d * m.ld_out;
 #pragma unroll
     for (int q = 0; q < kSamplesPerThread; ++q) {
-      if (sb + q >= g.T) break;
-      float ox, oy, el_d;
-      sample_offsets<kChain, false>(g, dc, sc[q], ox, oy, el_d);
-      double v = m.alpha * ml_gather(g, m, dc, chan, ml_corners(g, ax_eta, ax_xi, ox, oy));
-      if (m.beta != 0.0) v = fma(m.beta, (double)row[sb + q], v);  // (beta = 0: out is not read)
-      row[sb + q] = (float)v;
+      const int s = t.sb + q;
+      if (s >= g.T) break;
+      double v = m.alpha * ml_gather(g, m, dc, chan, t.corners(g, dc, q));
+      if (m.beta != 0.0) v = fma(m.beta, (double)row[s], v);  // (beta = 0: out is not read)
+      row[s] = (float)v;
     }
   }
 }
 
 // ---- the destriper's baseline reduction ----
 // mrx_baseline_reduce: y[d][b] += sum_{s in b} W mu (tod_s - alpha (P x)_s), hits[d][b] += sum_{s in b} W mu, on the tile
-// and the pointing of map_project_kernel.  With L >= 16 a thread's four samples lie in at most two baselines; each wave sums
+// of the atomic operators (MapTile).  With L >= 16 a thread's four samples lie in at most two baselines; each wave sums
 // every baseline's run of lanes in float64 with a segmented shuffle reduction, the run's first lane adds the sum to the
 // tile's LDS row, and the tile sends one float64 atomic per (detector, baseline) it touches: none per sample.
 constexpr int kBaseMinL = 16;
@@ -1611,45 +1563,30 @@ template <bool kChain, bool kHits>
 __global__ __launch_bounds__(kBlock) void baseline_reduce_kernel(MapArgs g, BinArgs b, MlArgs m) {
   __shared__ DetConst dets[kTileDet];
   __shared__ double acc[kHits ? 2 : 1][kTileDet][kBaseTileSeg];
-  const int d0 = blockIdx.y * kTileDet;
-  const int t0 = blockIdx.x * kTileSamples;
-  const int sb = t0 + threadIdx.x * kSamplesPerThread;
-  const int nd = min(kTileDet, g.D - d0);
-  const int b0 = t0 / m.L, nseg = (min(t0 + kTileSamples, g.T) - 1) / m.L - b0 + 1;  // the tile's baselines [b0, b0 + nseg)
-  if ((int)threadIdx.x < nd) dets[threadIdx.x] = make_det_const(g, d0 + threadIdx.x);
   for (int i = threadIdx.x; i < (kHits ? 2 : 1) * kTileDet * kBaseTileSeg; i += kBlock) (&acc[0][0][0])[i] = 0.0;
   const bool point = m.x || m.mask;  // (uniform) the TOD alone, unmasked, needs no pixels
-  const Axis ax_eta = g.eta, ax_xi = g.xi;
-  SampleConst sc[kSamplesPerThread];
-  if (point) {
-#pragma unroll
-    for (int q = 0; q < kSamplesPerThread; ++q) {
-      sample_const(g, sb + q, kChain, sc[q]);
-      sc[q].s = min(max(sb + q, 0), g.T - 1);
-    }
-  }
-  __syncthreads();
+  const MapTile<kChain> t(g, dets, point);
+  const int t0 = blockIdx.x * kTileSamples, sb = t.sb;
+  const int b0 = t0 / m.L, nseg = (min(t0 + kTileSamples, g.T) - 1) / m.L - b0 + 1;  // the tile's baselines [b0, b0 + nseg)
   // (no early exit: every lane takes part in the shuffles; lanes past T add nothing, under a key of their own)
   const int kA = sb < g.T ? sb / m.L : 0x7ffffff0;
   const int lane = threadIdx.x & 63;
   const int prevA = __shfl_up(kA, 1, 64);
   const size_t plane = (size_t)g.n_eta * g.n_xi;
-  for (int dl = 0; dl < nd; ++dl) {
+  for (int dl = 0; dl < t.nd; ++dl) {
     const DetConst dc = dets[dl];
-    const int d = d0 + dl;
-    const int chan = b.channel ? min(max(b.channel[d], 0), g.C - 1) : 0;
-    const double det_w = m.det_weight ? m.det_weight[d] : 1.0;
+    const int d = t.d0 + dl;
+    const int chan = det_channel(g, b, d);
+    const double det_w = det_weight(m, d);
     double vA = 0.0, hA = 0.0, vB = 0.0, hB = 0.0;  // the samples in baseline kA, and in kA + 1
 #pragma unroll
     for (int q = 0; q < kSamplesPerThread; ++q) {
       const int s = sb + q;
       if (s >= g.T) break;
-      double W = (b.weight ? (double)b.weight[(size_t)d * b.ld_w + s] : 1.0) * det_w;
+      double W = sample_weight(b, d, s) * det_w;
       double v = b.tod ? (double)b.tod[(size_t)d * b.ld_tod + s] : 0.0;
       if (point) {
-        float ox, oy, el_d;
-        sample_offsets<kChain, false>(g, dc, sc[q], ox, oy, el_d);
-        const MlCorners pc = ml_corners(g, ax_eta, ax_xi, ox, oy);
+        const MlCorners pc = t.corners(g, dc, q);
         if (m.mask && !m.mask[chan * plane + pc.o[0]]) W = 0.0;
         if (m.x) v = fma(-m.alpha, ml_gather(g, m, dc, chan, pc), v);
       }
@@ -1678,21 +1615,32 @@ __global__ __launch_bounds__(kBlock) void baseline_reduce_kernel(MapArgs g, BinA
     }
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < nd * nseg; i += kBlock) {
+  for (int i = threadIdx.x; i < t.nd * nseg; i += kBlock) {
     const int dl = i / nseg, j = i - dl * nseg;
-    const size_t at = (size_t)(d0 + dl) * m.nb + (b0 + j);
+    const size_t at = (size_t)(t.d0 + dl) * m.nb + (b0 + j);
     if (m.y && acc[0][dl][j] != 0.0) atomicAdd(m.y + at, acc[0][dl][j]);
     if (kHits && acc[kHits ? 1 : 0][dl][j] != 0.0) atomicAdd(m.hits + at, acc[kHits ? 1 : 0][dl][j]);
   }
 }
 
-// one run of consecutive samples with the same pixels: the corners' sums go out with one atomic per plane and corner
-template <bool kBlocks>
-__device__ __forceinline__ void ml_flush(const MapArgs& g, const MlArgs& m, const DetConst& dc, int chan, const int (&o)[4],
-                                         const double (&A)[4]) {
+// One run of a thread's consecutive samples with the same pixels (bin_atomic_kernel): the corners' sums go out with one
+// atomic per corner, plane and product
+template <int kSrc>
+__device__ __forceinline__ void flush_corners(const MapArgs& g, const BinArgs& b, const MlArgs& m, const DetConst& dc, int chan,
+                                              const int (&o)[4], const double (&A)[4], const double (&B)[4]) {
   const size_t plane = (size_t)g.n_eta * g.n_xi;
   const int corners = g.bilinear ? 4 : 1;
-  if constexpr (kBlocks) {
+  if constexpr (kSrc == kSrcTod) {
+    for (int k = 0; k < g.S; ++k) {
+      const size_t base = ((size_t)k * g.C + chan) * plane;
+      const double w = dc.w[k];
+      for (int c = 0; c < corners; ++c) {
+        if (B[c] == 0.0) continue;  // zero weight: nothing to add (np.abs(P) entries that are 0)
+        atomicAdd(b.sum + base + o[c], w * A[c]);
+        atomicAdd(b.wgt + base + o[c], fabs(w) * B[c]);
+      }
+    }
+  } else if constexpr (kSrc == kSrcBlocks) {
     int idx = 0;  // H[k, l], k <= l, row-major
     for (int k = 0; k < g.S; ++k)
       for (int l = k; l < g.S; ++l, ++idx) {
@@ -1711,57 +1659,55 @@ __device__ __forceinline__ void ml_flush(const MapArgs& g, const MlArgs& m, cons
   }
 }
 
-// float64 atomics with run merging (the BinRun form): kBlocks -- the block diagonal, A[c] = sum W b_c^2; kBase -- the
-// destriper's P^T W F a, A[c] = sum W a[d][s / L] b_c; else the normal operator, A[c] = sum W (P x)_s b_c
-template <bool kChain, bool kBlocks, bool kBase = false>
-__global__ __launch_bounds__(kBlock) void ml_atomic_kernel(MapArgs g, BinArgs b, MlArgs m) {
+// The atomic form of the binning and of the map-maker's operators: float64 atomics with run merging -- a thread's
+// consecutive samples of a row that share their pixels are summed per corner and flushed once.  Per source, A[c] =
+// kSrcTod: sum W D b_c, with B[c] = sum W b_c (the binning's two maps; a corner goes out where B[c] != 0);
+// kSrcNormal: sum W (P x)_s b_c;  kSrcBaselines: sum W a[d][s / L] b_c;  kSrcBlocks: sum W b_c^2 (the block diagonal)
+template <bool kChain, int kSrc>
+__global__ __launch_bounds__(kBlock) void bin_atomic_kernel(MapArgs g, BinArgs b, MlArgs m) {
   __shared__ DetConst dets[kTileDet];
-  const int d0 = blockIdx.y * kTileDet;
-  const int sb = blockIdx.x * kTileSamples + threadIdx.x * kSamplesPerThread;
-  const int nd = min(kTileDet, g.D - d0);
-  if ((int)threadIdx.x < nd) dets[threadIdx.x] = make_det_const(g, d0 + threadIdx.x);
-  const Axis ax_eta = g.eta, ax_xi = g.xi;
-  SampleConst sc[kSamplesPerThread];
-#pragma unroll
-  for (int q = 0; q < kSamplesPerThread; ++q) {
-    sample_const(g, sb + q, kChain, sc[q]);
-    sc[q].s = min(max(sb + q, 0), g.T - 1);
-  }
-  __syncthreads();
-  if (sb >= g.T) return;
-  for (int dl = 0; dl < nd; ++dl) {
+  const MapTile<kChain> t(g, dets);
+  if (t.sb >= g.T) return;
+  for (int dl = 0; dl < t.nd; ++dl) {
     const DetConst dc = dets[dl];
-    const int d = d0 + dl;
-    const int chan = b.channel ? min(max(b.channel[d], 0), g.C - 1) : 0;
-    const double det_w = m.det_weight ? m.det_weight[d] : 1.0;
+    const int d = t.d0 + dl;
+    const int chan = det_channel(g, b, d);
+    const double det_w = kSrc == kSrcTod ? 1.0 : det_weight(m, d);
     int o[4] = {0, 0, 0, 0};
-    double A[4] = {0.0, 0.0, 0.0, 0.0};
+    double A[4] = {0.0, 0.0, 0.0, 0.0}, B[4] = {0.0, 0.0, 0.0, 0.0};
     bool open = false;
 #pragma unroll
     for (int q = 0; q < kSamplesPerThread; ++q) {
-      if (sb + q >= g.T) break;
-      float ox, oy, el_d;
-      sample_offsets<kChain, false>(g, dc, sc[q], ox, oy, el_d);
-      const MlCorners pc = ml_corners(g, ax_eta, ax_xi, ox, oy);
-      double W = (b.weight ? (double)b.weight[(size_t)d * b.ld_w + sb + q] : 1.0) * det_w;
-      if (kBase) W *= m.amp[(size_t)d * m.nb + (sb + q) / m.L];
-      else if (!kBlocks) W *= ml_gather(g, m, dc, chan, pc);
+      const int s = t.sb + q;
+      if (s >= g.T) break;
+      const MlCorners pc = t.corners(g, dc, q);
+      double W = sample_weight(b, d, s) * det_w;
+      if constexpr (kSrc == kSrcBaselines) W *= m.amp[(size_t)d * m.nb + s / m.L];
+      if constexpr (kSrc == kSrcNormal) W *= ml_gather(g, m, dc, chan, pc);
+      const double WD = kSrc == kSrcTod ? W * (double)b.tod[(size_t)d * b.ld_tod + s] : 0.0;
       if (open && (pc.o[0] != o[0] || pc.o[1] != o[1] || pc.o[2] != o[2] || pc.o[3] != o[3])) {
-        ml_flush<kBlocks>(g, m, dc, chan, o, A);
+        flush_corners<kSrc>(g, b, m, dc, chan, o, A, B);
         open = false;
       }
       if (!open) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           o[c] = pc.o[c];
-          A[c] = 0.0;
+          A[c] = B[c] = 0.0;
         }
         open = true;
       }
 #pragma unroll
-      for (int c = 0; c < 4; ++c) A[c] = fma(W, kBlocks ? pc.w[c] * pc.w[c] : pc.w[c], A[c]);
+      for (int c = 0; c < 4; ++c) {
+        if constexpr (kSrc == kSrcTod) {
+          A[c] = fma(WD, pc.w[c], A[c]);
+          B[c] = fma(W, pc.w[c], B[c]);
+        } else {
+          A[c] = fma(W, kSrc == kSrcBlocks ? pc.w[c] * pc.w[c] : pc.w[c], A[c]);
+        }
+      }
     }
-    if (open) ml_flush<kBlocks>(g, m, dc, chan, o, A);
+    if (open) flush_corners<kSrc>(g, b, m, dc, chan, o, A, B);
   }
 }
 
@@ -1829,6 +1775,38 @@ __global__ __launch_bounds__(kBlock) void block_solve_kernel(int S, long long n,
 
 }  // namespace
 
+// the map's grid and centre and the detectors' pointing, as every map kernel takes them (the callers check the sizes)
+static MapArgs map_args(const mrx_sky_map* map, const float* d_az, const float* d_el, int T, const double* d_transform,
+                        const float* d_dx, const float* d_dy, const double* d_stokes_w, int D) {
+  MapArgs g{};
+  g.eta = make_axis(map->n_eta, map->eta0, map->deta);
+  g.xi = make_axis(map->n_xi, map->xi0, map->dxi);
+  g.C = map->n_channels;
+  g.S = map->n_stokes;
+  g.n_eta = map->n_eta;
+  g.n_xi = map->n_xi;
+  g.cphi = (float)map->center_phi;
+  // exp(1j * (pi/2 - ctheta)) as jax evaluates it: the python float demoted to float32,
+  // then a complex64 exponential
+  const float ang = (float)(1.5707963267948966 - map->center_theta);
+  g.rot_re = (float)cos((double)ang);
+  g.rot_im = (float)sin((double)ang);
+  g.cos_cphi = cos(map->center_phi);
+  g.sin_cphi = sin(map->center_phi);
+  g.cos_ctheta = cos(map->center_theta);
+  g.sin_ctheta = sin(map->center_theta);
+  g.bilinear = map->bilinear;
+  g.az = d_az;
+  g.el = d_el;
+  g.transform = d_transform;
+  g.dx = d_dx;
+  g.dy = d_dy;
+  g.stokes_w = d_stokes_w;
+  g.D = D;
+  g.T = T;
+  return g;
+}
+
 // mrx_map_sample (krj == nullptr) and mrx_map_sample_krj
 static int map_sample(mrx_ctx* ctx, const mrx_sky_map* map, const mrx_map_cal* cal,
                       const float* d_az, const float* d_el, int T, const double* d_transform,
@@ -1850,25 +1828,8 @@ static int map_sample(mrx_ctx* ctx, const mrx_sky_map* map, const mrx_map_cal* c
   } else {
     MRX_REQUIRE(ctx, cal->d_scalar, "need a per-channel scalar calibration without a table");
   }
-  MapArgs g{};
+  MapArgs g = map_args(map, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w, D);
   g.values = map->d_values;
-  g.eta = make_axis(map->n_eta, map->eta0, map->deta);
-  g.xi = make_axis(map->n_xi, map->xi0, map->dxi);
-  g.C = map->n_channels;
-  g.S = map->n_stokes;
-  g.n_eta = map->n_eta;
-  g.n_xi = map->n_xi;
-  g.cphi = (float)map->center_phi;
-  // exp(1j * (pi/2 - ctheta)) as jax evaluates it: the python float demoted to float32,
-  // then a complex64 exponential
-  const float ang = (float)(1.5707963267948966 - map->center_theta);
-  g.rot_re = (float)cos((double)ang);
-  g.rot_im = (float)sin((double)ang);
-  g.cos_cphi = cos(map->center_phi);
-  g.sin_cphi = sin(map->center_phi);
-  g.cos_ctheta = cos(map->center_theta);
-  g.sin_ctheta = sin(map->center_theta);
-  g.bilinear = map->bilinear;
   {
     // (the sampler reads the map as ONE raw buffer: 32-bit offsets)
     const unsigned long long bytes = 4ull * (unsigned long long)map->n_channels * map->n_stokes * map->n_eta * map->n_xi;
@@ -1887,14 +1848,6 @@ static int map_sample(mrx_ctx* ctx, const mrx_sky_map* map, const mrx_map_cal* c
   g.inv_dta = cal->dta > 0.0 ? 1.0 / cal->dta : 0.0;
   g.t = cal->d_t;
   g.scalar = cal->d_scalar;
-  g.az = d_az;
-  g.el = d_el;
-  g.transform = d_transform;
-  g.dx = d_dx;
-  g.dy = d_dy;
-  g.stokes_w = d_stokes_w;
-  g.D = D;
-  g.T = T;
   g.out = d_out;
   g.ld = ld_out;
   g.vec_ok = (ld_out % 4 == 0) && ((reinterpret_cast<uintptr_t>(d_out) & 15u) == 0);
@@ -2032,52 +1985,34 @@ int mrx_map_sample_krj(mrx_ctx* ctx, const mrx_sky_map* map, const mrx_map_cal* 
   return map_sample(ctx, map, cal, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w, D, d_out, ld_out, &kj);
 }
 
-// the grid and the pointing of the binning and of the map-maker's operators
-static int map_grid_args(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_az, const float* d_el, int T,
-                         const double* d_transform, const float* d_dx, const float* d_dy, const double* d_stokes_w, int D,
-                         MapArgs& g) {
+// The arguments of the operators on the binning's pointing (the binning, the map-maker's and the destriper's): the map,
+// the pointing, the TOD (or null), the sample weights (or null) and the per-detector weights (or null).
+static int op_args(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_tod, size_t ld_tod, const float* d_weight, size_t ld_weight,
+                   const double* d_det_weight, const float* d_az, const float* d_el, int T, const double* d_transform,
+                   const float* d_dx, const float* d_dy, const double* d_stokes_w, const int32_t* d_channel, int D, MapArgs& g,
+                   BinArgs& b, MlArgs& m) {
+  MRX_REQUIRE(ctx, map && d_az && d_el && d_dx && d_dy && d_stokes_w, "null pointer");
   MRX_REQUIRE(ctx, map->n_channels >= 1 && map->n_stokes >= 1 && map->n_stokes <= kMaxStokes &&
                        map->n_eta >= 2 && map->n_xi >= 2,
               "need n_channels >= 1, 1 <= n_stokes <= 4, n_eta >= 2, n_xi >= 2");
   MRX_REQUIRE(ctx, map->deta != 0.0 && map->dxi != 0.0, "map axes need a non-zero step");
   MRX_REQUIRE(ctx, (long long)map->n_eta * map->n_xi < (1LL << 31), "a map plane must hold fewer than 2^31 pixels");
-  g = MapArgs{};
-  g.eta = make_axis(map->n_eta, map->eta0, map->deta);
-  g.xi = make_axis(map->n_xi, map->xi0, map->dxi);
-  g.C = map->n_channels;
-  g.S = map->n_stokes;
-  g.n_eta = map->n_eta;
-  g.n_xi = map->n_xi;
-  g.cphi = (float)map->center_phi;
-  const float ang = (float)(1.5707963267948966 - map->center_theta);
-  g.rot_re = (float)cos((double)ang);
-  g.rot_im = (float)sin((double)ang);
-  g.cos_cphi = cos(map->center_phi);
-  g.sin_cphi = sin(map->center_phi);
-  g.cos_ctheta = cos(map->center_theta);
-  g.sin_ctheta = sin(map->center_theta);
-  g.bilinear = map->bilinear;
-  g.az = d_az;
-  g.el = d_el;
-  g.transform = d_transform;
-  g.dx = d_dx;
-  g.dy = d_dy;
-  g.stokes_w = d_stokes_w;
-  g.D = D;
-  g.T = T;
+  MRX_REQUIRE(ctx, (!d_tod || ld_tod >= (size_t)T) && (!d_weight || ld_weight >= (size_t)T), "leading dimension smaller than T");
+  MRX_REQUIRE(ctx, mrx_ceil_div(D, kTileDet) <= 65535, "D too large for one launch");
+  g = map_args(map, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w, D);
+  b = BinArgs{d_tod, ld_tod, d_weight, ld_weight, d_channel, nullptr, nullptr};
+  m = MlArgs{};
+  m.det_weight = d_det_weight;
   return MRX_OK;
 }
 
-static int bin_map_args(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_tod, size_t ld_tod,
-                        const float* d_weight, size_t ld_weight, const float* d_az, const float* d_el, int T,
-                        const double* d_transform, const float* d_dx, const float* d_dy,
-                        const double* d_stokes_w, const int32_t* d_channel, int D, double* d_sum,
-                        double* d_wgt, MapArgs& g, BinArgs& b) {
-  MRX_REQUIRE(ctx, map && d_tod && d_az && d_el && d_dx && d_dy && d_stokes_w && d_sum && d_wgt, "null pointer");
-  const int rc = map_grid_args(ctx, map, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w, D, g);
-  if (rc != MRX_OK) return rc;
-  MRX_REQUIRE(ctx, ld_tod >= (size_t)T && (!d_weight || ld_weight >= (size_t)T), "leading dimension smaller than T");
-  b = BinArgs{d_tod, ld_tod, d_weight, ld_weight, d_channel, d_sum, d_wgt};
+// a kernel on the tile grid of the atomic operators (MapTile), in the pointing form the context selects
+typedef void (*TileKernel)(MapArgs, BinArgs, MlArgs);
+static int launch_tiles(mrx_ctx* ctx, TileKernel chain_form, TileKernel composed_form, const MapArgs& g, const BinArgs& b,
+                        const MlArgs& m) {
+  const dim3 grid(mrx_ceil_div(g.T, kTileSamples), mrx_ceil_div(g.D, kTileDet));
+  hipLaunchKernelGGL(ctx->options[MRX_OPT_POINTING_CHAIN] ? chain_form : composed_form, grid, dim3(kBlock), 0, ctx->stream, g, b, m);
+  MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;
 }
 
@@ -2090,19 +2025,16 @@ int mrx_bin_map(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_tod, size_t
   if (!ctx) return MRX_ERR_INVALID;
   MRX_REQUIRE(ctx, D >= 0 && T >= 0, "negative size");
   if (D == 0 || T == 0) return MRX_OK;
+  MRX_REQUIRE(ctx, d_tod && d_sum && d_wgt, "null pointer");
   MapArgs g;
   BinArgs b;
-  const int rc = bin_map_args(ctx, map, d_tod, ld_tod, d_weight, ld_weight, d_az, d_el, T, d_transform, d_dx, d_dy,
-                              d_stokes_w, d_channel, D, d_sum, d_wgt, g, b);
+  MlArgs m;
+  const int rc = op_args(ctx, map, d_tod, ld_tod, d_weight, ld_weight, nullptr, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w,
+                         d_channel, D, g, b, m);
   if (rc != MRX_OK) return rc;
-  dim3 grid(mrx_ceil_div(T, kTileSamples), mrx_ceil_div(D, kTileDet));
-  MRX_REQUIRE(ctx, grid.y <= 65535u, "D too large for one launch");
-  if (ctx->options[MRX_OPT_POINTING_CHAIN])
-    hipLaunchKernelGGL(bin_map_kernel<true>, grid, dim3(kBlock), 0, ctx->stream, g, b);
-  else
-    hipLaunchKernelGGL(bin_map_kernel<false>, grid, dim3(kBlock), 0, ctx->stream, g, b);
-  MRX_CHECK_LAUNCH(ctx);
-  return MRX_OK;
+  b.sum = d_sum;
+  b.wgt = d_wgt;
+  return launch_tiles(ctx, bin_atomic_kernel<true, kSrcTod>, bin_atomic_kernel<false, kSrcTod>, g, b, m);
 }
 
 // regions of a map for the bucketed form, or 0 when it does not apply
@@ -2150,6 +2082,56 @@ int mrx_bin_map_work_bytes(const mrx_sky_map* map, int D, int T, size_t* min_byt
   return MRX_OK;
 }
 
+// The routed form (mrx_bin_map_bucketed, mrx_map_normal_apply, mrx_bin_map_baselines): the time axis in chunks of
+// whole columns of tiles, as many as the work buffer holds; per chunk pass A routes the contributions to the map's
+// regions, bin_order_kernel ranks the regions and pass B sums each region in LDS into the map.  entry_bytes: of a routed
+// contribution; lds_b: pass B's dynamic LDS; too_small: the message for a buffer below one column, which names the
+// caller's sizing function.
+typedef void (*PassA)(MapArgs, BinArgs, BucketArgs, MlArgs);
+typedef void (*PassB)(MapArgs, BinArgs, BucketArgs, int, MlArgs);
+static int routed_bin(mrx_ctx* ctx, const MapArgs& g, const BinArgs& b, const MlArgs& m, BucketArgs k, PassA pass_a,
+                      PassB pass_b, int entry_bytes, size_t lds_b, void* d_work, size_t work_bytes, const char* too_small) {
+  const BinGeometry q = bin_geometry(g.bilinear != 0, k.R);
+  k.tile_det = q.tile_det;
+  k.tile_entries = q.tile_entries;
+  const int tiles_y = mrx_ceil_div(g.D, q.tile_det);
+  MRX_REQUIRE(ctx, tiles_y <= 65535, "D too large for one launch");
+  const size_t col = (size_t)tiles_y * ((size_t)q.tile_entries * entry_bytes + (size_t)k.R * sizeof(uint32_t));
+  MRX_REQUIRE(ctx, d_work && (reinterpret_cast<uintptr_t>(d_work) & 15u) == 0 && work_bytes >= col, too_small);
+  const int cols_total = mrx_ceil_div(g.T, q.tile_samples);
+  int cols = (int)(work_bytes / col < (size_t)cols_total ? work_bytes / col : (size_t)cols_total);
+  // pass B indexes the entries of a chunk with 32 bits
+  while ((long long)cols * tiles_y * q.tile_entries > (1LL << 32) - 1) cols = (cols + 1) / 2;
+  MRX_LDS_CAP(ctx, pass_a, q.lds_a);
+  MRX_LDS_CAP(ctx, pass_b, lds_b);
+  if (!ctx->d_bin_order) MRX_HIP(ctx, hipMalloc(&ctx->d_bin_order, sizeof(uint32_t) * 2 * kBinMaxRegions));
+  k.totals = ctx->d_bin_order;
+  k.order = reinterpret_cast<const int*>(ctx->d_bin_order + kBinMaxRegions);
+  // enough workgroups per region to fill the chip: the regions under the scan hold most samples
+  // (round 4, onto 1024^2, regions in dispatch order: 8192 items 28.4 ms, 16384 26.8, 32768 25.6, 65536 25.3, 131072 26.2 for
+  //  the call; heaviest regions first: 23.6 / 22.5 / 22.6 / 22.3 / 23.1 from 16384 to 262144)
+  const int splits = 65536 / k.R < 1 ? 1 : 65536 / k.R;
+  // the table right behind the entries is 16-byte aligned whatever the entry size (8, 12 or 16 bytes)
+  static_assert(BinTile<true>::kEntries % 4 == 0 && BinTile<false>::kEntries % 4 == 0, "a tile holds a multiple of 4 entries");
+  for (int c0 = 0; c0 < cols_total; c0 += cols) {
+    const int nc = cols_total - c0 < cols ? cols_total - c0 : cols;
+    k.tiles_x = nc;
+    k.n_tiles = nc * tiles_y;
+    k.s0 = c0 * q.tile_samples;
+    k.s1 = (long long)(c0 + nc) * q.tile_samples < (long long)g.T ? (c0 + nc) * q.tile_samples : g.T;
+    k.entries = d_work;
+    k.tab = reinterpret_cast<uint32_t*>(static_cast<char*>(d_work) + (size_t)k.n_tiles * q.tile_entries * entry_bytes);
+    MRX_HIP(ctx, hipMemsetAsync(k.tab, 0, (size_t)k.R * k.n_tiles * sizeof(uint32_t), ctx->stream));
+    MRX_HIP(ctx, hipMemsetAsync(k.totals, 0, (size_t)k.R * sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(pass_a, dim3(nc, tiles_y), dim3(kBlock), q.lds_a, ctx->stream, g, b, k, m);
+    hipLaunchKernelGGL(bin_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, k.totals, k.R, const_cast<int*>(k.order));
+    const int sp = splits < k.n_tiles ? splits : k.n_tiles;
+    hipLaunchKernelGGL(pass_b, dim3(k.R, sp), dim3(kBlock), lds_b, ctx->stream, g, b, k, sp, m);
+    MRX_CHECK_LAUNCH(ctx);
+  }
+  return MRX_OK;
+}
+
 int mrx_bin_map_bucketed(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_tod, size_t ld_tod,
                          const float* d_weight, size_t ld_weight, const float* d_az, const float* d_el, int T,
                          const double* d_transform, const float* d_dx, const float* d_dy,
@@ -2164,81 +2146,25 @@ int mrx_bin_map_bucketed(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_to
   if (!k.R)
     return mrx_fail(ctx, MRX_ERR_UNSUPPORTED, "mrx_bin_map_bucketed: maps of at most %d regions of %d x %d pixels (use mrx_bin_map)",
                     kBinMaxRegions, kBinBx, kBinBy);
+  MRX_REQUIRE(ctx, d_tod && d_sum && d_wgt, "null pointer");
   MapArgs g;
   BinArgs b;
-  const int rc = bin_map_args(ctx, map, d_tod, ld_tod, d_weight, ld_weight, d_az, d_el, T, d_transform, d_dx, d_dy,
-                              d_stokes_w, d_channel, D, d_sum, d_wgt, g, b);
+  MlArgs m;
+  const int rc = op_args(ctx, map, d_tod, ld_tod, d_weight, ld_weight, nullptr, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w,
+                         d_channel, D, g, b, m);
   if (rc != MRX_OK) return rc;
-  const bool bil = map->bilinear != 0;
-  const BinGeometry q = bin_geometry(bil, k.R);
-  k.tile_det = q.tile_det;
-  k.tile_entries = q.tile_entries;
-  const int tiles_y = mrx_ceil_div(D, q.tile_det);
-  MRX_REQUIRE(ctx, tiles_y <= 65535, "D too large for one launch");
-  const int entry_bytes = bin_entry_bytes(bil, d_weight != nullptr);
-  const size_t col = (size_t)tiles_y * ((size_t)q.tile_entries * entry_bytes + (size_t)k.R * sizeof(uint32_t));
-  MRX_REQUIRE(ctx, d_work && (reinterpret_cast<uintptr_t>(d_work) & 15u) == 0 && work_bytes >= col,
-              "work buffer: 16-byte aligned, at least mrx_bin_map_work_bytes' minimum");
-  const int cols_total = mrx_ceil_div(T, q.tile_samples);
-  const size_t usable = work_bytes - 16;  // the table behind the entries is moved up to a 16-byte boundary
-  int cols = (int)(usable / col < (size_t)cols_total ? usable / col : (size_t)cols_total);
-  if (cols < 1) cols = 1;  // (work_bytes >= the 16-byte-entry minimum: one column of 8- or 12-byte entries fits)
-  // pass B indexes the entries of a chunk with 32 bits
-  while ((long long)cols * tiles_y * q.tile_entries > (1LL << 32) - 1) cols = (cols + 1) / 2;
-  const size_t lds_b = (size_t)g.S * 2 * kBinRegionPx * sizeof(double);
-  const bool chain = ctx->options[MRX_OPT_POINTING_CHAIN] != 0;
-  typedef void (*BucketKernel)(MapArgs, BinArgs, BucketArgs);
-  typedef void (*AccKernel)(MapArgs, BinArgs, BucketArgs, int);
-  const bool wts = d_weight != nullptr;
-  const BucketKernel pass_a = bil ? (chain ? bin_bucket_kernel<true, true, true> : bin_bucket_kernel<false, true, true>)
-                              : wts ? (chain ? bin_bucket_kernel<true, false, true> : bin_bucket_kernel<false, false, true>)
-                                    : (chain ? bin_bucket_kernel<true, false, false> : bin_bucket_kernel<false, false, false>);
-  const AccKernel pass_b = bil ? bin_accumulate_kernel<16> : wts ? bin_accumulate_kernel<12> : bin_accumulate_kernel<8>;
-  MRX_LDS_CAP(ctx, pass_a, q.lds_a);
-  MRX_LDS_CAP(ctx, pass_b, lds_b);
-  // enough workgroups per region to fill the chip: the regions under the scan hold most samples
-  // (round 4, onto 1024^2, regions in dispatch order: 8192 items 28.4 ms, 16384 26.8, 32768 25.6, 65536 25.3, 131072 26.2 for
-  //  the call; heaviest regions first: 23.6 / 22.5 / 22.6 / 22.3 / 23.1 from 16384 to 262144)
-  if (!ctx->d_bin_order) MRX_HIP(ctx, hipMalloc(&ctx->d_bin_order, sizeof(uint32_t) * 2 * kBinMaxRegions));
-  k.totals = ctx->d_bin_order;
-  k.order = reinterpret_cast<const int*>(ctx->d_bin_order + kBinMaxRegions);
-  int splits = 65536 / k.R;
-  splits = splits < 1 ? 1 : splits;
-  for (int c0 = 0; c0 < cols_total; c0 += cols) {
-    const int nc = cols_total - c0 < cols ? cols_total - c0 : cols;
-    k.tiles_x = nc;
-    k.n_tiles = nc * tiles_y;
-    k.s0 = c0 * q.tile_samples;
-    k.s1 = (long long)(c0 + nc) * q.tile_samples < (long long)T ? (c0 + nc) * q.tile_samples : T;
-    k.entries = d_work;
-    // (the table behind the entries, 16-byte aligned whatever the entry size)
-    k.tab = reinterpret_cast<uint32_t*>(static_cast<char*>(d_work) + (((size_t)k.n_tiles * q.tile_entries * entry_bytes + 15) & ~(size_t)15));
-    MRX_HIP(ctx, hipMemsetAsync(k.tab, 0, (size_t)k.R * k.n_tiles * sizeof(uint32_t), ctx->stream));
-    MRX_HIP(ctx, hipMemsetAsync(k.totals, 0, (size_t)k.R * sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(pass_a, dim3(nc, tiles_y), dim3(kBlock), q.lds_a, ctx->stream, g, b, k);
-    hipLaunchKernelGGL(bin_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, k.totals, k.R, const_cast<int*>(k.order));
-    const int sp = splits < k.n_tiles ? splits : k.n_tiles;
-    hipLaunchKernelGGL(pass_b, dim3(k.R, sp), dim3(kBlock), lds_b, ctx->stream, g, b, k, sp);
-    MRX_CHECK_LAUNCH(ctx);
-  }
-  return MRX_OK;
+  b.sum = d_sum;
+  b.wgt = d_wgt;
+  const bool bil = map->bilinear != 0, wts = d_weight != nullptr, chain = ctx->options[MRX_OPT_POINTING_CHAIN] != 0;
+  const PassA pass_a = bil ? (chain ? bin_bucket_kernel<true, true, true> : bin_bucket_kernel<false, true, true>)
+                       : wts ? (chain ? bin_bucket_kernel<true, false, true> : bin_bucket_kernel<false, false, true>)
+                             : (chain ? bin_bucket_kernel<true, false, false> : bin_bucket_kernel<false, false, false>);
+  const PassB pass_b = bil ? bin_accumulate_kernel<16> : wts ? bin_accumulate_kernel<12> : bin_accumulate_kernel<8>;
+  return routed_bin(ctx, g, b, m, k, pass_a, pass_b, bin_entry_bytes(bil, wts), (size_t)g.S * 2 * kBinRegionPx * sizeof(double),
+                    d_work, work_bytes, "work buffer: 16-byte aligned, at least mrx_bin_map_work_bytes' minimum");
 }
 
 // ---- the maximum-likelihood map-maker's operators ----
-
-static int ml_args(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_weight, size_t ld_weight, const double* d_det_weight,
-                   const float* d_az, const float* d_el, int T, const double* d_transform, const float* d_dx, const float* d_dy,
-                   const double* d_stokes_w, const int32_t* d_channel, int D, MapArgs& g, BinArgs& b, MlArgs& m) {
-  MRX_REQUIRE(ctx, map && d_az && d_el && d_dx && d_dy && d_stokes_w, "null pointer");
-  const int rc = map_grid_args(ctx, map, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w, D, g);
-  if (rc != MRX_OK) return rc;
-  MRX_REQUIRE(ctx, !d_weight || ld_weight >= (size_t)T, "leading dimension smaller than T");
-  MRX_REQUIRE(ctx, mrx_ceil_div(D, kTileDet) <= 65535, "D too large for one launch");
-  b = BinArgs{nullptr, 0, d_weight, ld_weight, d_channel, nullptr, nullptr};
-  m = MlArgs{};
-  m.det_weight = d_det_weight;
-  return MRX_OK;
-}
 
 int mrx_map_project(mrx_ctx* ctx, const mrx_sky_map* map, const double* d_x, const float* d_az, const float* d_el, int T,
                     const double* d_transform, const float* d_dx, const float* d_dy, const double* d_stokes_w,
@@ -2252,66 +2178,23 @@ int mrx_map_project(mrx_ctx* ctx, const mrx_sky_map* map, const double* d_x, con
   MapArgs g;
   BinArgs b;
   MlArgs m;
-  const int rc = ml_args(ctx, map, nullptr, 0, nullptr, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w, d_channel, D, g, b, m);
+  const int rc = op_args(ctx, map, nullptr, 0, nullptr, 0, nullptr, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w, d_channel,
+                         D, g, b, m);
   if (rc != MRX_OK) return rc;
   m.x = d_x;
   m.out = d_out;
   m.ld_out = ld_out;
   m.alpha = alpha;
   m.beta = beta;
-  const dim3 grid(mrx_ceil_div(T, kTileSamples), mrx_ceil_div(D, kTileDet));
-  if (ctx->options[MRX_OPT_POINTING_CHAIN])
-    hipLaunchKernelGGL(map_project_kernel<true>, grid, dim3(kBlock), 0, ctx->stream, g, b, m);
-  else
-    hipLaunchKernelGGL(map_project_kernel<false>, grid, dim3(kBlock), 0, ctx->stream, g, b, m);
-  MRX_CHECK_LAUNCH(ctx);
-  return MRX_OK;
+  return launch_tiles(ctx, map_project_kernel<true>, map_project_kernel<false>, g, b, m);
 }
 
-// the routed form of an operator that routes a float64 per sample (mrx_map_normal_apply, mrx_bin_map_baselines):
-// mrx_bin_map_bucketed's passes and chunks with 16-byte entries, pass A given, pass B normal_accumulate_kernel
-typedef void (*MlBucketKernel)(MapArgs, BinArgs, BucketArgs, MlArgs);
-static int ml_routed(mrx_ctx* ctx, const mrx_sky_map* map, const MapArgs& g, const BinArgs& b, const MlArgs& m, BucketArgs k,
-                     MlBucketKernel pass_a, void* d_work, size_t work_bytes) {
-  const int D = g.D, T = g.T;
-  const bool bil = map->bilinear != 0;
-  const BinGeometry q = bin_geometry(bil, k.R);
-  k.tile_det = q.tile_det;
-  k.tile_entries = q.tile_entries;
-  const int tiles_y = mrx_ceil_div(D, q.tile_det);
-  MRX_REQUIRE(ctx, tiles_y <= 65535, "D too large for one launch");
-  const size_t entry_bytes = 16;
-  const size_t col = (size_t)tiles_y * ((size_t)q.tile_entries * entry_bytes + (size_t)k.R * sizeof(uint32_t));
-  MRX_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(d_work) & 15u) == 0 && work_bytes >= col,
-              "work buffer: 16-byte aligned, at least mrx_map_normal_work_bytes' minimum (or NULL: the atomic form)");
-  const int cols_total = mrx_ceil_div(T, q.tile_samples);
-  int cols = (int)(work_bytes / col < (size_t)cols_total ? work_bytes / col : (size_t)cols_total);
-  if (cols < 1) cols = 1;
-  while ((long long)cols * tiles_y * q.tile_entries > (1LL << 32) - 1) cols = (cols + 1) / 2;
-  const size_t lds_b = (size_t)g.S * kBinRegionPx * sizeof(double);
-  MRX_LDS_CAP(ctx, pass_a, q.lds_a);
-  MRX_LDS_CAP(ctx, normal_accumulate_kernel, lds_b);
-  if (!ctx->d_bin_order) MRX_HIP(ctx, hipMalloc(&ctx->d_bin_order, sizeof(uint32_t) * 2 * kBinMaxRegions));
-  k.totals = ctx->d_bin_order;
-  k.order = reinterpret_cast<const int*>(ctx->d_bin_order + kBinMaxRegions);
-  const int splits = 65536 / k.R < 1 ? 1 : 65536 / k.R;
-  for (int c0 = 0; c0 < cols_total; c0 += cols) {
-    const int nc = cols_total - c0 < cols ? cols_total - c0 : cols;
-    k.tiles_x = nc;
-    k.n_tiles = nc * tiles_y;
-    k.s0 = c0 * q.tile_samples;
-    k.s1 = (long long)(c0 + nc) * q.tile_samples < (long long)T ? (c0 + nc) * q.tile_samples : T;
-    k.entries = d_work;
-    k.tab = reinterpret_cast<uint32_t*>(static_cast<char*>(d_work) + (size_t)k.n_tiles * q.tile_entries * entry_bytes);
-    MRX_HIP(ctx, hipMemsetAsync(k.tab, 0, (size_t)k.R * k.n_tiles * sizeof(uint32_t), ctx->stream));
-    MRX_HIP(ctx, hipMemsetAsync(k.totals, 0, (size_t)k.R * sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(pass_a, dim3(nc, tiles_y), dim3(kBlock), q.lds_a, ctx->stream, g, b, k, m);
-    hipLaunchKernelGGL(bin_order_kernel, dim3(1), dim3(1024), 0, ctx->stream, k.totals, k.R, const_cast<int*>(k.order));
-    const int sp = splits < k.n_tiles ? splits : k.n_tiles;
-    hipLaunchKernelGGL(normal_accumulate_kernel, dim3(k.R, sp), dim3(kBlock), lds_b, ctx->stream, g, b, k, sp, m);
-    MRX_CHECK_LAUNCH(ctx);
-  }
-  return MRX_OK;
+// the routed form of an operator that routes a float64 per sample (mrx_map_normal_apply, mrx_bin_map_baselines): 16-byte
+// entries, pass B normal_accumulate_kernel
+static int ml_routed(mrx_ctx* ctx, const MapArgs& g, const BinArgs& b, const MlArgs& m, const BucketArgs& k, PassA pass_a,
+                     void* d_work, size_t work_bytes) {
+  return routed_bin(ctx, g, b, m, k, pass_a, normal_accumulate_kernel, 16, (size_t)g.S * kBinRegionPx * sizeof(double), d_work,
+                    work_bytes, "work buffer: 16-byte aligned, at least mrx_map_normal_work_bytes' minimum (or NULL: the atomic form)");
 }
 
 int mrx_map_normal_work_bytes(const mrx_sky_map* map, int D, int T, size_t* min_bytes, size_t* full_bytes) {
@@ -2336,28 +2219,18 @@ int mrx_map_normal_apply(mrx_ctx* ctx, const mrx_sky_map* map, const double* d_x
   MapArgs g;
   BinArgs b;
   MlArgs m;
-  const int rc = ml_args(ctx, map, d_weight, ld_weight, d_det_weight, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w,
-                         d_channel, D, g, b, m);
+  const int rc = op_args(ctx, map, nullptr, 0, d_weight, ld_weight, d_det_weight, d_az, d_el, T, d_transform, d_dx, d_dy,
+                         d_stokes_w, d_channel, D, g, b, m);
   if (rc != MRX_OK) return rc;
   m.x = d_x;
   m.y = d_y;
-  const bool chain = ctx->options[MRX_OPT_POINTING_CHAIN] != 0;
   BucketArgs k{};
   k.R = bin_regions(map, &k.nbx, &k.nby);
-  if (!k.R || !d_work) {  // float64 atomics with run merging
-    const dim3 grid(mrx_ceil_div(T, kTileSamples), mrx_ceil_div(D, kTileDet));
-    if (chain)
-      hipLaunchKernelGGL((ml_atomic_kernel<true, false>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
-    else
-      hipLaunchKernelGGL((ml_atomic_kernel<false, false>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
-    MRX_CHECK_LAUNCH(ctx);
-    return MRX_OK;
-  }
-  typedef void (*BucketKernel)(MapArgs, BinArgs, BucketArgs, MlArgs);
-  const bool bil = map->bilinear != 0;
-  const BucketKernel pass_a = bil ? (chain ? normal_bucket_kernel<true, true> : normal_bucket_kernel<false, true>)
-                                  : (chain ? normal_bucket_kernel<true, false> : normal_bucket_kernel<false, false>);
-  return ml_routed(ctx, map, g, b, m, k, pass_a, d_work, work_bytes);
+  if (!k.R || !d_work) return launch_tiles(ctx, bin_atomic_kernel<true, kSrcNormal>, bin_atomic_kernel<false, kSrcNormal>, g, b, m);
+  const bool bil = map->bilinear != 0, chain = ctx->options[MRX_OPT_POINTING_CHAIN] != 0;
+  const PassA pass_a = bil ? (chain ? normal_bucket_kernel<true, true> : normal_bucket_kernel<false, true>)
+                           : (chain ? normal_bucket_kernel<true, false> : normal_bucket_kernel<false, false>);
+  return ml_routed(ctx, g, b, m, k, pass_a, d_work, work_bytes);
 }
 
 int mrx_bin_map_blocks(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_weight, size_t ld_weight,
@@ -2372,17 +2245,11 @@ int mrx_bin_map_blocks(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_weig
   MapArgs g;
   BinArgs b;
   MlArgs m;
-  const int rc = ml_args(ctx, map, d_weight, ld_weight, d_det_weight, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w,
-                         d_channel, D, g, b, m);
+  const int rc = op_args(ctx, map, nullptr, 0, d_weight, ld_weight, d_det_weight, d_az, d_el, T, d_transform, d_dx, d_dy,
+                         d_stokes_w, d_channel, D, g, b, m);
   if (rc != MRX_OK) return rc;
   m.y = d_blocks;
-  const dim3 grid(mrx_ceil_div(T, kTileSamples), mrx_ceil_div(D, kTileDet));
-  if (ctx->options[MRX_OPT_POINTING_CHAIN])
-    hipLaunchKernelGGL((ml_atomic_kernel<true, true>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
-  else
-    hipLaunchKernelGGL((ml_atomic_kernel<false, true>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
-  MRX_CHECK_LAUNCH(ctx);
-  return MRX_OK;
+  return launch_tiles(ctx, bin_atomic_kernel<true, kSrcBlocks>, bin_atomic_kernel<false, kSrcBlocks>, g, b, m);
 }
 
 int mrx_map_block_solve(mrx_ctx* ctx, int n_stokes, int n_channels, long long n_pix, const double* d_blocks,
@@ -2422,15 +2289,12 @@ int mrx_baseline_reduce(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_tod
   const int nb = (int)(((long long)T + L - 1) / L);
   if (D == 0 || T == 0) return MRX_OK;
   MRX_REQUIRE(ctx, d_y || d_hits, "null pointer: neither d_y nor d_hits");
-  MRX_REQUIRE(ctx, !d_tod || ld_tod >= (size_t)T, "leading dimension smaller than T");
   MapArgs g;
   BinArgs b;
   MlArgs m;
-  const int rc = ml_args(ctx, map, d_weight, ld_weight, d_det_weight, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w,
-                         d_channel, D, g, b, m);
+  const int rc = op_args(ctx, map, d_tod, ld_tod, d_weight, ld_weight, d_det_weight, d_az, d_el, T, d_transform, d_dx, d_dy,
+                         d_stokes_w, d_channel, D, g, b, m);
   if (rc != MRX_OK) return rc;
-  b.tod = d_tod;
-  b.ld_tod = ld_tod;
   m.x = d_x;
   m.alpha = alpha;
   m.mask = d_mask;
@@ -2438,21 +2302,8 @@ int mrx_baseline_reduce(mrx_ctx* ctx, const mrx_sky_map* map, const float* d_tod
   m.nb = nb;
   m.y = d_y;
   m.hits = d_hits;
-  const dim3 grid(mrx_ceil_div(T, kTileSamples), mrx_ceil_div(D, kTileDet));
-  const bool chain = ctx->options[MRX_OPT_POINTING_CHAIN] != 0;
-  if (d_hits) {
-    if (chain)
-      hipLaunchKernelGGL((baseline_reduce_kernel<true, true>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
-    else
-      hipLaunchKernelGGL((baseline_reduce_kernel<false, true>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
-  } else {
-    if (chain)
-      hipLaunchKernelGGL((baseline_reduce_kernel<true, false>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
-    else
-      hipLaunchKernelGGL((baseline_reduce_kernel<false, false>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
-  }
-  MRX_CHECK_LAUNCH(ctx);
-  return MRX_OK;
+  return d_hits ? launch_tiles(ctx, baseline_reduce_kernel<true, true>, baseline_reduce_kernel<false, true>, g, b, m)
+                : launch_tiles(ctx, baseline_reduce_kernel<true, false>, baseline_reduce_kernel<false, false>, g, b, m);
 }
 
 int mrx_bin_map_baselines(mrx_ctx* ctx, const mrx_sky_map* map, const double* d_amp, int L, const float* d_weight,
@@ -2470,26 +2321,18 @@ int mrx_bin_map_baselines(mrx_ctx* ctx, const mrx_sky_map* map, const double* d_
   MapArgs g;
   BinArgs b;
   MlArgs m;
-  const int rc = ml_args(ctx, map, d_weight, ld_weight, d_det_weight, d_az, d_el, T, d_transform, d_dx, d_dy, d_stokes_w,
-                         d_channel, D, g, b, m);
+  const int rc = op_args(ctx, map, nullptr, 0, d_weight, ld_weight, d_det_weight, d_az, d_el, T, d_transform, d_dx, d_dy,
+                         d_stokes_w, d_channel, D, g, b, m);
   if (rc != MRX_OK) return rc;
   m.amp = d_amp;
   m.L = L;
   m.nb = nb;
   m.y = d_y;
-  const bool chain = ctx->options[MRX_OPT_POINTING_CHAIN] != 0;
   BucketArgs k{};
   k.R = bin_regions(map, &k.nbx, &k.nby);
-  if (!k.R || !d_work) {  // float64 atomics with run merging
-    const dim3 grid(mrx_ceil_div(T, kTileSamples), mrx_ceil_div(D, kTileDet));
-    if (chain)
-      hipLaunchKernelGGL((ml_atomic_kernel<true, false, true>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
-    else
-      hipLaunchKernelGGL((ml_atomic_kernel<false, false, true>), grid, dim3(kBlock), 0, ctx->stream, g, b, m);
-    MRX_CHECK_LAUNCH(ctx);
-    return MRX_OK;
-  }
-  return ml_routed(ctx, map, g, b, m, k, chain ? baseline_bucket_kernel<true> : baseline_bucket_kernel<false>, d_work, work_bytes);
+  if (!k.R || !d_work) return launch_tiles(ctx, bin_atomic_kernel<true, kSrcBaselines>, bin_atomic_kernel<false, kSrcBaselines>, g, b, m);
+  return ml_routed(ctx, g, b, m, k, ctx->options[MRX_OPT_POINTING_CHAIN] ? baseline_bucket_kernel<true> : baseline_bucket_kernel<false>,
+                   d_work, work_bytes);
 }
 
 }  // extern "C"

@@ -27,6 +27,13 @@ logger = logging.getLogger("maria")
 BIN_WORK_LIMIT_BYTES = 24 << 30
 
 
+def _work_bytes(lo, full, device):
+    """The size of a routed operator's work buffer from its sizing function's minimum (one column of tiles) and full size
+    (the whole time axis at once): the full size within BIN_WORK_LIMIT_BYTES and half the free memory, never below lo."""
+    free = torch.cuda.mem_get_info(device)[0]
+    return max(lo, min(full, BIN_WORK_LIMIT_BYTES, max(free // 2, lo)))
+
+
 def bin_map(ctx, sky, signal, weight, az, el, transform, dx, dy, stokes_w, channel, msum, mwgt, bucketed=None):
     """``map_sum += (W * D) @ P``, ``map_wgt += W @ |P|`` for one TOD on the device
     (mappers/bin_mapper.py:84-120).  Maps of up to 2048 regions of 64 x 32 pixels take
@@ -41,9 +48,7 @@ def bin_map(ctx, sky, signal, weight, az, el, transform, dx, dy, stokes_w, chann
     if bucketed is True and not fits:
         raise ValueError("the bucketed binning takes maps of at most 2048 regions of 64 x 32 pixels")
     if fits and bucketed is not False:
-        free = torch.cuda.mem_get_info(signal.device)[0]
-        size = max(lo.value, min(full.value, BIN_WORK_LIMIT_BYTES, max(free // 2, lo.value)))
-        work = torch.empty(size, dtype=torch.uint8, device=signal.device)
+        work = torch.empty(_work_bytes(lo.value, full.value, signal.device), dtype=torch.uint8, device=signal.device)
         ctx.call("mrx_bin_map_bucketed", *args, ptr(work), work.numel())
         torch.cuda.current_stream(signal.device).synchronize()  # the buffer goes back to the allocator
         del work
@@ -239,8 +244,7 @@ class _GlsMapper(_GridMapper):
         for shape in shapes:
             lo, full = C.c_size_t(), C.c_size_t()
             if ctx.lib.mrx_map_normal_work_bytes(C.byref(sky), shape[0], shape[1], C.byref(lo), C.byref(full)) == 0:
-                free = torch.cuda.mem_get_info(self.device)[0]
-                need = max(need, lo.value, min(full.value, BIN_WORK_LIMIT_BYTES, max(free // 2, lo.value)))
+                need = max(need, _work_bytes(lo.value, full.value, self.device))
         return torch.empty(need, dtype=torch.uint8, device=self.device) if need else None
 
     def _cg(self, apply, precond, b):

@@ -225,8 +225,9 @@ def test_normal_operator(gpu_ctx, bilinear, shape, pointing_mode):
 
 @pytest.mark.parametrize("bilinear", [False, True])
 def test_blocks_and_block_solve(gpu_ctx, bilinear):
-    """mrx_bin_map_blocks = the block diagonal of P^T W P; mrx_map_block_solve = H^-1 r per pixel, NaN exactly where the
-    block's reciprocal condition number is below rcond (or the pixel has no hits), 0 there in the preconditioner's form."""
+    """mrx_bin_map_blocks = the block diagonal of P^T W P (both forms of the pointing: the float32 chain and the composed
+    rotation); mrx_map_block_solve = H^-1 r per pixel, NaN exactly where the block's reciprocal condition number is below
+    rcond (or the pixel has no hits), 0 there in the preconditioner's form."""
     import torch
 
     from maria_amd._lib import ptr
@@ -235,11 +236,10 @@ def test_blocks_and_block_solve(gpu_ctx, bilinear):
     rng = np.random.default_rng(7)
     w = rng.uniform(0.5, 2.0, (pb.D, pb.T)).astype(np.float32)
     dw = rng.uniform(0.5, 3.0, pb.D)
-    H = pb.blocks(gpu_ctx, _t(w, np.float32), _t(dw, np.float64))
     W = (w.astype(np.float64) * dw[:, None]).ravel()
     full = (pb.P.T @ scipy.sparse.diags(W) @ pb.P).tocsr()
     n, Cn = pb.n_pix, pb.Cn
-    ref = np.zeros(H.shape)
+    ref = np.zeros((6, Cn, pb.n_eta, pb.n_xi))  # H[k, l], k <= l
     idx = 0
     for k in range(3):
         for l in range(k, 3):
@@ -247,8 +247,15 @@ def test_blocks_and_block_solve(gpu_ctx, bilinear):
                 rows, cols = (k * Cn + c) * n + np.arange(n), (l * Cn + c) * n + np.arange(n)
                 ref[idx, c] = np.asarray(full[rows, cols]).reshape(pb.n_eta, pb.n_xi)
             idx += 1
-    got = H.cpu().numpy()
-    _flip_tolerant_close(got, ref, pb.tol, 0.1 if not bilinear else 0.0)
+    for chain in (1, 0):  # the float32 chain (MRX_OPT_POINTING_CHAIN), then the composed rotation (the default)
+        gpu_ctx.set_option(0, chain)
+        try:
+            H = pb.blocks(gpu_ctx, _t(w, np.float32), _t(dw, np.float64))
+        finally:
+            gpu_ctx.set_option(0, 0)
+        got = H.cpu().numpy()
+        assert got.shape == ref.shape
+        _flip_tolerant_close(got, ref, pb.tol, 0.1 if not bilinear else 0.0)
     # a pixel never seen, and one seen by a single detector angle: singular blocks
     Hn = got.copy()
     Hn[:, 0, 0, 0] = 0.0
