@@ -796,6 +796,34 @@ int mrx_bin_map_baselines(mrx_ctx* ctx, const mrx_sky_map* map, const double* d_
                           const double* d_transform, const float* d_dx, const float* d_dy, const double* d_stokes_w,
                           const int32_t* d_channel, int D, double* d_y, void* d_work, size_t work_bytes);
 
+/* ---- the destriper's prior on the offsets (DestripingMapper(baseline_prior=...)) ---------------- */
+
+/* Madam's C_a^-1 for D detectors of nb baselines each: s_d T, T the weighted graph Laplacian over one detector's
+ * baselines (maria_amd/destripe_prior.py),
+ *   (T a)_b = sum_{k=1..K} w_k ( [b + k < nb] (a_b - a_{b+k}) + [b - k >= 0] (a_b - a_{b-k}) ),
+ * T 1 = 0 exactly.  Float64 throughout, independent of the map.  All three refuse (MRX_ERR_INVALID) K outside 1 .. 64,
+ * Kp outside 0 .. 16, nb < 1 and a negative (or NaN) scale; a check of the scales copies them to the host.
+ *  d_w  [K] float64 (signed),  d_scale  [D] float64 >= 0,  d_hits, d_a, d_y, d_r, d_z  [D][nb] float64 */
+
+/* d_y = d_hits * d_a + s_d T d_a (overwritten; d_hits = NULL: no diagonal term).  One workgroup per detector and tile of
+ * 256 baselines, the tile with its K-baseline halo in LDS.  d_y must not be d_a. */
+int mrx_baseline_prior_apply(mrx_ctx* ctx, int D, int nb, int K, const double* d_w, const double* d_scale,
+                             const double* d_hits, const double* d_a, double* d_y);
+
+/* The banded LDL^T of diag(hits) + s_d T_Kp per detector, T_Kp the Laplacian of the first Kp weights (its own diagonal).
+ * d_ok[d] = 1 where every pivot is > 0 and the detector has a hit, else 0 (its factor is then not written).  One lane
+ * per detector, sequential along b, 64 detectors a workgroup with the (Kp + 1)^2 window in LDS.  Layout, by column and
+ * coalesced for the solve:  d_factor[(b (Kp + 1) + j) D + d] = 1 / D_b (j = 0), L[b + j][b] (j >= 1; 0 past nb)
+ *  d_factor  [nb][Kp + 1][D] float64 (D nb (Kp + 1) 8 bytes),  d_ok  [D] uint8;  d_w, d_scale unused when Kp = 0 */
+int mrx_baseline_band_factor(mrx_ctx* ctx, int D, int nb, int Kp, const double* d_w, const double* d_scale,
+                             const double* d_hits, double* d_factor, uint8_t* d_ok);
+
+/* d_z = (diag(hits) + s_d T_Kp)^-1 d_r from mrx_baseline_band_factor's factor; d_z = 0 for the detectors with ok = 0.
+ * One lane per detector (forward and back substitution along b, the band in registers), 64 a workgroup.  d_z may be
+ * d_r. */
+int mrx_baseline_band_solve(mrx_ctx* ctx, int D, int nb, int Kp, const double* d_factor, const uint8_t* d_ok,
+                            const double* d_r, double* d_z);
+
 /* ---- TOD pre-processing for the mappers (tod/processing.py:91-204) --------------------- */
 
 /* remove_slope (D -= linspace(D[:, 0], D[:, -1], T), processing.py:99-105) and / or window

@@ -217,6 +217,9 @@ SIGNATURES = {
     "mrx_map_block_solve": (_i, [_vp, _i, _i, C.c_longlong, _vp, _vp, _d, _i, _vp, _vp]),
     "mrx_baseline_reduce": (_i, [_vp, _vp, _vp, _sz, _vp, _d, _vp, _sz, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "mrx_bin_map_baselines": (_i, [_vp, _vp, _vp, _i, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz]),
+    "mrx_baseline_prior_apply": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mrx_baseline_band_factor": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mrx_baseline_band_solve": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mrx_tod_detrend_window": (_i, [_vp, _vp, _sz, _i, _i, _i, _vp, _vp]),
     "mrx_sosfilt_chunk": (_i, []),
     "mrx_sosfilt_work_doubles": (_i, [_i, _i, _i, C.POINTER(_sz)]),

@@ -16,6 +16,7 @@ import logging
 import numpy as np
 import torch
 
+from . import destripe_prior
 from ._lib import Context, MrxSkyMap, ptr
 from .map import ProjectionMap, mueller_row
 
@@ -349,17 +350,35 @@ class DestripingMapper(_GlsMapper):
     Operators on the device, no TOD-sized intermediate per iteration: ``mrx_bin_map_baselines`` (P^T W F a),
     ``mrx_map_block_solve`` (M^-1) and ``mrx_baseline_reduce`` (F^T W mu (d - alpha P x), and the hits); F^T W mu F a is
     hits times a.  Nearest-pixel pointing only.  MaximumLikelihoodMapper's keywords plus ``baseline_length`` (seconds; at
-    least 16 samples).  ``products`` adds ``baselines`` and ``hits``, one [ndet, nb] array per TOD."""
+    least 16 samples).  ``products`` adds ``baselines`` and ``hits``, one [ndet, nb] array per TOD.
+
+    ``baseline_prior``: None (the above), or ``{"knee": Hz, "alpha": 1.0, "band": 16}`` -- a 1/f prior on the
+    offsets, Madam's C_a, from the simulator's noise law: white plus pink, pink equal to white at the knee, slope alpha in
+    (0, 2] (maria_amd/destripe_prior.py).  ``knee`` is a scalar or one value per detector of each TOD.  Per TOD and
+    detector C_a^-1 = s_d T, T a weighted graph Laplacian over the detector's baselines (K <= 64 signed lags of the inverse
+    covariance of L-sample means), s_d = W_d / knee_d^alpha with W_d the detector weight of ``noise_weights``; then
+
+        A a = hits a - F^T W mu P M^-1 P^T W F a + S T a,
+
+    the first and last terms in one ``mrx_baseline_prior_apply``.  With "inverse_variance" W_d is 1 / var of the whole row,
+    white and 1/f together, so the prior is weaker than the true one where the 1/f part is large.  The preconditioner is
+    (diag(hits) + S T_Kp)^-1, T_Kp the Laplacian of the first ``band`` <= 16 lags (fewer if their symbol goes negative, or
+    if the factor, D nb (Kp + 1) 8 bytes a TOD, does not fit in half the free memory; Kp = 0 is the diagonal), factored
+    once per ``run()`` (``mrx_baseline_band_factor``, ``mrx_baseline_band_solve``); a detector the band cannot factor (no
+    hits, a pivot <= 0) takes 1 / (hits + s_d diag T).  The prior determines offsets with no hits from their neighbours, so
+    the gauge shift applies to every baseline of a detector with any hit.  ``products["prior"]``: per TOD K, Kp and the
+    weights."""
 
     def __init__(self, tods, center, width=None, height=None, resolution=None, stokes="IQU", nu=None, frame="ra/dec", units="K_RJ",
                  degrees=True, bilinear=False, tod_preprocessing=None, noise_weights="inverse_variance", max_iter=100, tol=1e-6, rcond=1e-3,
-                 baseline_length=1.0, device="cuda:0"):
+                 baseline_length=1.0, baseline_prior=None, device="cuda:0"):
         if bilinear:
             raise NotImplementedError("DestripingMapper takes nearest-pixel pointing only (bilinear=False)")
         self._init_grid(tods, center, width, height, resolution, stokes, nu, frame, units, degrees, bilinear, tod_preprocessing, device)
         self._init_gls(stokes, noise_weights, max_iter, tol, rcond)
         self.baseline_length = float(baseline_length)
         self.baseline_samples = []  # L per TOD with detectors
+        self.sample_rates = []  # fs per TOD with detectors
         for tod in self.tods:
             if tod.dets.n == 0:
                 continue
@@ -369,6 +388,33 @@ class DestripingMapper(_GlsMapper):
             if L < 16:
                 raise ValueError(f"baseline_length {self.baseline_length} s is {L} samples at this TOD's sample rate: at least 16")
             self.baseline_samples.append(int(min(L, 1 << 30)))
+            self.sample_rates.append((t.size - 1) / span if span > 0 else 1.0)
+        self.baseline_prior = self._check_prior(baseline_prior)
+
+    def _check_prior(self, prior):
+        """The ``baseline_prior`` keyword, checked: None or {"knee": [ndet] per TOD with detectors, "alpha", "band"}."""
+        if prior is None:
+            return None
+        if not isinstance(prior, dict) or set(prior) - {"knee", "alpha", "band"} or "knee" not in prior:
+            raise ValueError(f"baseline_prior {prior!r}: a dict with 'knee' and optionally 'alpha', 'band'")
+        alpha = float(prior.get("alpha", 1.0))
+        if not 0.0 < alpha <= 2.0:
+            raise ValueError(f"baseline_prior alpha {alpha}: in (0, 2]")
+        band = prior.get("band", 16)
+        if int(band) != band or not 0 <= band <= destripe_prior.MAX_BAND:
+            raise ValueError(f"baseline_prior band {band}: an integer in 0 .. {destripe_prior.MAX_BAND}")
+        knee = np.asarray(prior["knee"], float)
+        knees = []
+        for tod in self.tods:
+            if tod.dets.n == 0:
+                continue
+            if knee.ndim != 0 and knee.shape != (tod.dets.n,):
+                raise ValueError(f"baseline_prior knee has shape {knee.shape}: a scalar or one value per detector ({tod.dets.n})")
+            k = np.broadcast_to(knee, (tod.dets.n,)).astype(float)
+            if not np.all(k > 0) or not np.all(np.isfinite(k)):
+                raise ValueError("baseline_prior knee: every value > 0 (Hz)")
+            knees.append(k)
+        return {"knee": knees, "alpha": alpha, "band": int(band)}
 
     def run(self):
         dev = self.device
@@ -400,17 +446,29 @@ class DestripingMapper(_GlsMapper):
                          0 if work is None else work.numel())
             return y
 
-        def apply(a):  # A a = hits a - F^T W mu P M^-1 P^T W F a
+        prior = None
+
+        def apply(a):  # A a = hits a - F^T W mu P M^-1 P^T W F a (+ S T a)
             u = solve(bin_offsets(a))[0]
-            out = hits * a
+            if prior is None:
+                out = hits * a
+            else:
+                out = torch.empty_like(a)
+                for (D, nb), p, hi, ai, oi in zip(sizes, prior, views(hits), views(a), views(out)):
+                    ctx.call("mrx_baseline_prior_apply", D, nb, p["w"].numel(), ptr(p["w"]), ptr(p["scale"]), ptr(hi), ptr(ai), ptr(oi))
             for i, oi in enumerate(views(out)):
                 reduce(i, u, oi, None)
             return out
 
         for i, (bi, hi) in enumerate(zip(views(b), views(hits))):
             reduce(i, m0, bi, hi, signal=tods[i][0])  # F^T W mu (d - P m0) and the hits
-        inv_hits = torch.where(hits > 0, 1.0 / hits, torch.zeros_like(hits))
-        a, residuals, converged = self._cg(apply, lambda r: inv_hits * r, b)
+        if self.baseline_prior is None:
+            inv_hits = torch.where(hits > 0, 1.0 / hits, torch.zeros_like(hits))
+            precond = lambda r: inv_hits * r  # noqa: E731
+        else:
+            prior = self._prior_operators(ctx, sizes, views(hits), tods)
+            precond = lambda r: self._prior_precond(ctx, sizes, prior, views, r)  # noqa: E731
+        a, residuals, converged = self._cg(apply, precond, b)
         self._fix_gauge(a, hits, views, tods)
         x = m0 - solve(bin_offsets(a))[0]
         x = torch.where(mask, x, torch.full_like(x, float("nan")))
@@ -419,7 +477,44 @@ class DestripingMapper(_GlsMapper):
         self.products = {"data": data, "weight": blocks[:1].cpu().numpy(), "blocks": blocks.cpu().numpy(), "rhs": rhs.cpu().numpy(),
                          "baselines": [v.cpu().numpy() for v in views(a)], "hits": [v.cpu().numpy() for v in views(hits)],
                          "residuals": np.asarray(residuals, float), "n_iter": max(len(residuals) - 1, 0), "converged": bool(converged)}
+        if prior is not None:
+            self.products["prior"] = [{"K": p["w"].numel(), "Kp": p["Kp"], "weights": p["w"].cpu().numpy()} for p in prior]
         return self._projection_map(data, self.products["weight"])
+
+    def _prior_operators(self, ctx, sizes, hits, tods):
+        """Per TOD: the prior's weights and scales on the device, and the preconditioner's band factor (or its diagonal)."""
+        cfg, out = self.baseline_prior, []
+        for i, ((D, nb), hi, (_, _, _, refs)) in enumerate(zip(sizes, hits, tods)):
+            w = destripe_prior.prior_weights(self.sample_rates[i], self.baseline_samples[i], cfg["alpha"], nb)
+            det_w = refs[1]  # the per-detector weight W_d (None: "uniform")
+            W = torch.ones(D, dtype=torch.float64, device=self.device) if det_w is None else det_w.double()
+            scale = (W / torch.as_tensor(cfg["knee"][i] ** cfg["alpha"]).to(self.device)).contiguous()
+            d_w = torch.as_tensor(w).to(self.device)
+            diag_T = torch.as_tensor(destripe_prior.laplacian_diagonal(w, nb)).to(self.device)
+            diag = hi + scale[:, None] * diag_T[None, :]  # the fall-back: 1 / (hits + s diag T)
+            p = {"w": d_w, "scale": scale, "inv_diag": torch.where(diag > 0, 1.0 / diag, torch.zeros_like(diag)), "factor": None}
+            Kp = destripe_prior.band_lags(w, cfg["band"])
+            while Kp > 0 and D * nb * (Kp + 1) * 8 > torch.cuda.mem_get_info(self.device)[0] // 2:
+                Kp -= 1
+            p["Kp"] = Kp
+            if Kp > 0:
+                p["factor"] = torch.empty(D * nb * (Kp + 1), dtype=torch.float64, device=self.device)
+                p["ok"] = torch.empty(D, dtype=torch.uint8, device=self.device)
+                ctx.call("mrx_baseline_band_factor", D, nb, Kp, ptr(d_w), ptr(scale), ptr(hi), ptr(p["factor"]), ptr(p["ok"]))
+                p["inv_diag"].mul_((p["ok"] == 0).double()[:, None])  # the diagonal where the band failed
+            out.append(p)
+        return out
+
+    def _prior_precond(self, ctx, sizes, prior, views, r):
+        """z = (diag(hits) + S T_Kp)^-1 r per TOD (the band solve), 1 / (hits + s diag T) where the band was not factored."""
+        z = torch.empty_like(r)
+        for (D, nb), p, ri, zi in zip(sizes, prior, views(r), views(z)):
+            if p["factor"] is None:
+                torch.mul(p["inv_diag"], ri, out=zi)
+            else:
+                ctx.call("mrx_baseline_band_solve", D, nb, p["Kp"], ptr(p["factor"]), ptr(p["ok"]), ptr(ri), ptr(zi))
+                zi.addcmul_(p["inv_diag"], ri)
+        return z
 
     def _fix_gauge(self, a, hits, views, tods):
         """Per map channel, the offsets made hits-orthogonal to the null directions of A, g_k[d][b] = w_k(d) for every
@@ -437,4 +532,6 @@ class DestripingMapper(_GlsMapper):
         c = (torch.linalg.pinv(G, rtol=1e-12) @ num[:, :, None])[:, :, 0]  # (a channel without hits: G = 0, c = 0)
         for ai, hi, (sw, d_chan) in zip(views(a), views(hits), per_tod):
             shift = (sw * c[d_chan]).sum(dim=1)
-            ai.sub_(torch.where(hi > 0, shift[:, None].expand_as(ai), torch.zeros_like(ai)))  # (offsets with no hits stay 0)
+            # offsets with no hits stay 0; with a prior they are their neighbours' and move with the detector's others
+            seen = hi > 0 if self.baseline_prior is None else (hi > 0).any(dim=1, keepdim=True).expand_as(ai)
+            ai.sub_(torch.where(seen, shift[:, None].expand_as(ai), torch.zeros_like(ai)))
