@@ -824,6 +824,17 @@ int mrx_baseline_band_factor(mrx_ctx* ctx, int D, int nb, int Kp, const double* 
 int mrx_baseline_band_solve(mrx_ctx* ctx, int D, int nb, int Kp, const double* d_factor, const uint8_t* d_ok,
                             const double* d_r, double* d_z);
 
+/* ---- detector noise spectra (maria_amd/noise_estimate.py) ------------------------------------------ */
+
+/* scipy.signal.welch(x, fs, nperseg=nperseg) of every row with scipy's defaults: periodic Hann window, noverlap =
+ * nperseg / 2, each segment's mean (summed in float64) removed before the window, one-sided density, mean over the
+ * (T - nperseg) / (nperseg / 2) + 1 segments (trailing samples dropped, never read).  nperseg a power of two in
+ * 256 .. 8192 (MRX_ERR_UNSUPPORTED otherwise); T < nperseg, ld < T, D < 1, fs <= 0 and null pointers are refused
+ * (MRX_ERR_INVALID) with d_psd untouched.  One workgroup per row reads the row once; a NaN spoils its own row only.
+ *  d_x    [D][ld] float32
+ *  d_psd  [D][nperseg / 2 + 1] float32, signal units^2 / Hz */
+int mrx_tod_welch(mrx_ctx* ctx, const float* d_x, size_t ld, int D, int T, int nperseg, double fs, float* d_psd);
+
 /* ---- TOD pre-processing for the mappers (tod/processing.py:91-204) --------------------- */
 
 /* remove_slope (D -= linspace(D[:, 0], D[:, -1], T), processing.py:99-105) and / or window

@@ -16,7 +16,7 @@ import logging
 import numpy as np
 import torch
 
-from . import destripe_prior
+from . import destripe_prior, noise_estimate
 from ._lib import Context, MrxSkyMap, ptr
 from .map import ProjectionMap, mueller_row
 
@@ -177,26 +177,65 @@ class _GlsMapper(_GridMapper):
     """What the white-noise GLS mappers share: the argument checks, the weights W, b = P^T W d with the block diagonal of
     P^T W P, the block solve and preconditioned conjugate gradients."""
 
-    def _init_gls(self, stokes, noise_weights, max_iter, tol, rcond):
+    def _init_gls(self, stokes, noise_weights, max_iter, tol, rcond, noise_fit=None):
         if not stokes or len(stokes) > 3 or any(s not in "IQU" for s in stokes) or len(set(stokes)) != len(stokes):
             raise ValueError(f"stokes '{stokes}': distinct planes of 'IQU' (the per-pixel solve takes at most three)")
         if isinstance(noise_weights, str):
-            if noise_weights not in ("inverse_variance", "uniform"):
-                raise ValueError(f"noise_weights '{noise_weights}': 'inverse_variance', 'uniform' or an [ndet] array")
+            if noise_weights not in ("inverse_variance", "uniform", "fit"):
+                raise ValueError(f"noise_weights '{noise_weights}': 'inverse_variance', 'uniform', 'fit' (1 / sigma^2 of the fitted "
+                                 "white level) or an [ndet] array")
         else:
             noise_weights = np.asarray(noise_weights, np.float64)
             for tod in self.tods:
                 if noise_weights.shape != (tod.dets.n,):
                     raise ValueError(f"noise_weights has shape {noise_weights.shape}; the TOD has {tod.dets.n} detectors")
         self.noise_weights, self.max_iter, self.tol, self.rcond = noise_weights, int(max_iter), float(tol), float(rcond)
+        if noise_fit is not None:
+            if not isinstance(noise_fit, dict) or set(noise_fit) - {"nperseg", "f_min", "f_max", "n_bins"}:
+                raise ValueError(f"noise_fit {noise_fit!r}: a dict of 'nperseg', 'f_min', 'f_max', 'n_bins'")
+            if noise_fit.get("nperseg") is not None:
+                noise_estimate.check_nperseg(noise_fit["nperseg"], noise_estimate.MAX_NPERSEG)
+        self.noise_fit = None if noise_fit is None else dict(noise_fit)
+        self.noise_fits = []  # per TOD with detectors, when a value needs them: the fitted noise law (noise_estimate)
 
-    def _det_weight(self, signal):
+    def _needs_fit(self):
+        return isinstance(self.noise_weights, str) and self.noise_weights == "fit"
+
+    def _check_noise_fit_used(self):
+        if self.noise_fit is not None and not self._needs_fit():
+            raise ValueError("noise_fit is used only by noise_weights='fit' and baseline_prior={'knee': 'fit'}: neither is set")
+
+    def _fit_noise(self, ctx, signal, tod):
+        """The noise law fitted to the Welch spectrum of every row of the signal the mapper bins; the fit range inside
+        the pass band of a configured 'filter' pre-processing step."""
+        cfg = self.noise_fit or {}
+        t = np.asarray(tod.coords.t, float)
+        fs = (t.size - 1) / (t[-1] - t[0])
+        f, psd = noise_estimate.welch(signal, fs, nperseg=cfg.get("nperseg"), ctx=ctx)
+        f_min, f_max = cfg.get("f_min"), cfg.get("f_max")
+        band = self.tod_preprocessing.get("filter")
+        if band:
+            f_np = f.cpu().numpy()
+            lo, hi = band.get("f_lower"), band.get("f_upper")
+            if lo is not None and lo > 0:
+                f_min = max(float(f_np[1]) if f_min is None else f_min, float(lo))
+            if hi is not None and hi > 0:
+                f_max = min(0.9 * float(f_np[-1]) if f_max is None else f_max, float(hi))
+        return noise_estimate.fit_noise(f, psd, f_min=f_min, f_max=f_max, n_bins=cfg.get("n_bins", 32))
+
+    def _det_weight(self, signal, fit=None):
         if isinstance(self.noise_weights, str):
             if self.noise_weights == "uniform":
                 return None
+            if self.noise_weights == "fit":  # 1 / sigma^2 of the fitted white level; a failed fit weighs 0
+                var = fit["sigma"] ** 2
+                return torch.where(torch.isfinite(var) & (var > 0), 1.0 / var, torch.zeros_like(var)).contiguous()
             var = signal.double().var(dim=1)
             return torch.where(var > 0, 1.0 / var, torch.zeros_like(var)).contiguous()
         return torch.as_tensor(self.noise_weights).to(self.device)
+
+    def _noise_products(self):
+        return [{k: v.cpu().numpy() for k, v in fit.items() if k in ("white", "knee", "alpha", "sigma")} for fit in self.noise_fits]
 
     def _normal_inputs(self, ctx, sky, keep):
         """rhs = P^T W d and the blocks of P^T W P over the TODs; per kept TOD ``(signal, wargs, point, refs)``: the weight
@@ -209,13 +248,18 @@ class _GlsMapper(_GridMapper):
         scratch = torch.zeros_like(rhs)  # (the binning's |P| weight: not used here)
         blocks = torch.zeros((S * (S + 1) // 2, Cn, self.n_eta, self.n_xi), dtype=torch.float64, device=dev)
         kept = []
+        self.noise_fits = []
         for tod in self.tods:
             if tod.dets.n == 0:
                 continue
             # a TOD in K_RJ is calibrated per detector to a unit response to I (TOD.to divides by the Mueller [0, 0]
             # element): its pointing matrix carries the Mueller row over that element; in pW the row itself
             signal, weight, az, el, transform, dx, dy, stokes_w, d_chan = self._tod_inputs(tod, ctx, unit_i_response=self.units == "K_RJ")
-            det_w = self._det_weight(signal)
+            fit = None
+            if self._needs_fit():
+                fit = self._fit_noise(ctx, signal, tod)
+                self.noise_fits.append(fit)
+            det_w = self._det_weight(signal, fit)
             D, T = signal.shape
             # b = P^T W d: the binning's sum, the per-detector weight folded into the sample weight
             w_bin = weight
@@ -286,14 +330,19 @@ class MaximumLikelihoodMapper(_GlsMapper):
     number below ``rcond`` (unobserved, or seen at one polarisation angle) is left out and is NaN in the map.
 
     The reference's class name with BinMapper's grid keywords, plus ``noise_weights`` ("inverse_variance": 1 / var of
-    each pre-processed detector row; "uniform"; or an [ndet] array), ``max_iter``, ``tol`` (on |r| / |b|) and ``rcond``.
+    each pre-processed detector row; "uniform"; "fit": 1 / sigma^2 of the white level fitted to each pre-processed
+    row's Welch spectrum, maria_amd/noise_estimate.py, 0 where the fit fails; or an [ndet] array), ``max_iter``, ``tol``
+    (on |r| / |b|), ``rcond`` and ``noise_fit`` (``{"nperseg", "f_min", "f_max", "n_bins"}`` for "fit"; a configured
+    'filter' step keeps the fit range inside its pass band).  With "fit" ``products["noise"]`` holds, per TOD, the
+    fitted ``white``, ``knee``, ``alpha`` and ``sigma`` (numpy arrays).
     Not converging is not an error: ``products["converged"]`` is False and a warning goes to the "maria" logger."""
 
     def __init__(self, tods, center, width=None, height=None, resolution=None, stokes="IQU", nu=None, frame="ra/dec", units="K_RJ",
                  degrees=True, bilinear=False, tod_preprocessing=None, noise_weights="inverse_variance", max_iter=100, tol=1e-6, rcond=1e-3,
-                 device="cuda:0"):
+                 device="cuda:0", noise_fit=None):
         self._init_grid(tods, center, width, height, resolution, stokes, nu, frame, units, degrees, bilinear, tod_preprocessing, device)
-        self._init_gls(stokes, noise_weights, max_iter, tol, rcond)
+        self._init_gls(stokes, noise_weights, max_iter, tol, rcond, noise_fit)
+        self._check_noise_fit_used()
 
     def run(self):
         dev = self.device
@@ -313,6 +362,8 @@ class MaximumLikelihoodMapper(_GlsMapper):
         self.products = {"data": data, "weight": blocks[:1].cpu().numpy(),  # H[0, 0]: [1, C, eta, xi]
                          "blocks": blocks.cpu().numpy(), "rhs": rhs.cpu().numpy(), "residuals": np.asarray(residuals, float),
                          "n_iter": max(len(residuals) - 1, 0), "converged": bool(converged)}
+        if self.noise_fits:
+            self.products["noise"] = self._noise_products()
         return self._projection_map(data, self.products["weight"])
 
     def _pcg(self, ctx, sky, ops, rhs, mask, solve):
@@ -361,21 +412,26 @@ class DestripingMapper(_GlsMapper):
         A a = hits a - F^T W mu P M^-1 P^T W F a + S T a,
 
     the first and last terms in one ``mrx_baseline_prior_apply``.  With "inverse_variance" W_d is 1 / var of the whole row,
-    white and 1/f together, so the prior is weaker than the true one where the 1/f part is large.  The preconditioner is
+    white and 1/f together, so the prior is weaker than the true one where the 1/f part is large; "fit" takes the
+    fitted white level, the prior's own.  The preconditioner is
     (diag(hits) + S T_Kp)^-1, T_Kp the Laplacian of the first ``band`` <= 16 lags (fewer if their symbol goes negative, or
     if the factor, D nb (Kp + 1) 8 bytes a TOD, does not fit in half the free memory; Kp = 0 is the diagonal), factored
     once per ``run()`` (``mrx_baseline_band_factor``, ``mrx_baseline_band_solve``); a detector the band cannot factor (no
     hits, a pivot <= 0) takes 1 / (hits + s_d diag T).  The prior determines offsets with no hits from their neighbours, so
     the gauge shift applies to every baseline of a detector with any hit.  ``products["prior"]``: per TOD K, Kp and the
-    weights."""
+    weights.
+
+    ``{"knee": "fit"}`` takes each detector's knee from the noise law fitted to its row (``noise_weights="fit"``'s fit,
+    ``noise_fit`` its settings) and alpha as the median fitted slope unless ``"alpha"`` is given (``"alpha": "fit"`` is
+    the same as leaving it out); the lag table stays shared by all detectors.  ``products["noise"]`` then holds the fits."""
 
     def __init__(self, tods, center, width=None, height=None, resolution=None, stokes="IQU", nu=None, frame="ra/dec", units="K_RJ",
                  degrees=True, bilinear=False, tod_preprocessing=None, noise_weights="inverse_variance", max_iter=100, tol=1e-6, rcond=1e-3,
-                 baseline_length=1.0, baseline_prior=None, device="cuda:0"):
+                 baseline_length=1.0, baseline_prior=None, device="cuda:0", noise_fit=None):
         if bilinear:
             raise NotImplementedError("DestripingMapper takes nearest-pixel pointing only (bilinear=False)")
         self._init_grid(tods, center, width, height, resolution, stokes, nu, frame, units, degrees, bilinear, tod_preprocessing, device)
-        self._init_gls(stokes, noise_weights, max_iter, tol, rcond)
+        self._init_gls(stokes, noise_weights, max_iter, tol, rcond, noise_fit)
         self.baseline_length = float(baseline_length)
         self.baseline_samples = []  # L per TOD with detectors
         self.sample_rates = []  # fs per TOD with detectors
@@ -390,19 +446,36 @@ class DestripingMapper(_GlsMapper):
             self.baseline_samples.append(int(min(L, 1 << 30)))
             self.sample_rates.append((t.size - 1) / span if span > 0 else 1.0)
         self.baseline_prior = self._check_prior(baseline_prior)
+        self._check_noise_fit_used()
+
+    def _needs_fit(self):
+        return super()._needs_fit() or (self.baseline_prior is not None and self.baseline_prior["knee"] == "fit")
 
     def _check_prior(self, prior):
-        """The ``baseline_prior`` keyword, checked: None or {"knee": [ndet] per TOD with detectors, "alpha", "band"}."""
+        """The ``baseline_prior`` keyword, checked: None or {"knee": [ndet] per TOD with detectors, or "fit", "alpha",
+        "band"}."""
         if prior is None:
             return None
         if not isinstance(prior, dict) or set(prior) - {"knee", "alpha", "band"} or "knee" not in prior:
             raise ValueError(f"baseline_prior {prior!r}: a dict with 'knee' and optionally 'alpha', 'band'")
-        alpha = float(prior.get("alpha", 1.0))
-        if not 0.0 < alpha <= 2.0:
-            raise ValueError(f"baseline_prior alpha {alpha}: in (0, 2]")
+        fit = isinstance(prior["knee"], str)
+        if fit and prior["knee"] != "fit":
+            raise ValueError(f"baseline_prior knee '{prior['knee']}': 'fit', a scalar or one value per detector (Hz)")
+        alpha = prior.get("alpha", "fit" if fit else 1.0)
+        if isinstance(alpha, str):
+            if alpha != "fit":
+                raise ValueError(f"baseline_prior alpha '{alpha}': 'fit' or a number in (0, 2]")
+            if not fit:
+                raise ValueError("baseline_prior alpha 'fit' needs knee 'fit': the slope comes from the same noise fit")
+        else:
+            alpha = float(alpha)
+            if not 0.0 < alpha <= 2.0:
+                raise ValueError(f"baseline_prior alpha {alpha}: in (0, 2]")
         band = prior.get("band", 16)
         if int(band) != band or not 0 <= band <= destripe_prior.MAX_BAND:
             raise ValueError(f"baseline_prior band {band}: an integer in 0 .. {destripe_prior.MAX_BAND}")
+        if fit:
+            return {"knee": "fit", "alpha": alpha, "band": int(band)}
         knee = np.asarray(prior["knee"], float)
         knees = []
         for tod in self.tods:
@@ -466,7 +539,7 @@ class DestripingMapper(_GlsMapper):
             inv_hits = torch.where(hits > 0, 1.0 / hits, torch.zeros_like(hits))
             precond = lambda r: inv_hits * r  # noqa: E731
         else:
-            prior = self._prior_operators(ctx, sizes, views(hits), tods)
+            prior = self._prior_operators(ctx, sizes, views(hits), tods, self._resolved_prior())
             precond = lambda r: self._prior_precond(ctx, sizes, prior, views, r)  # noqa: E731
         a, residuals, converged = self._cg(apply, precond, b)
         self._fix_gauge(a, hits, views, tods)
@@ -479,11 +552,31 @@ class DestripingMapper(_GlsMapper):
                          "residuals": np.asarray(residuals, float), "n_iter": max(len(residuals) - 1, 0), "converged": bool(converged)}
         if prior is not None:
             self.products["prior"] = [{"K": p["w"].numel(), "Kp": p["Kp"], "weights": p["w"].cpu().numpy()} for p in prior]
+        if self.noise_fits:
+            self.products["noise"] = self._noise_products()
         return self._projection_map(data, self.products["weight"])
 
-    def _prior_operators(self, ctx, sizes, hits, tods):
+    def _resolved_prior(self):
+        """baseline_prior with knee "fit" replaced by the fitted knees (a failed fit takes the median of the others) and
+        alpha "fit" by the median fitted alpha over every detector of every TOD."""
+        cfg = self.baseline_prior
+        if cfg["knee"] != "fit":
+            return cfg
+        alpha = cfg["alpha"]
+        if alpha == "fit":
+            a = torch.cat([fit["alpha"] for fit in self.noise_fits]).cpu().numpy()
+            a = a[np.isfinite(a)]
+            alpha = float(np.median(a)) if a.size else 1.0
+        knees = []
+        for fit in self.noise_fits:
+            k = fit["knee"].cpu().numpy()
+            ok = np.isfinite(k) & (k > 0)
+            knees.append(np.where(ok, k, float(np.median(k[ok])) if ok.any() else 1.0))
+        return {"knee": knees, "alpha": alpha, "band": cfg["band"]}
+
+    def _prior_operators(self, ctx, sizes, hits, tods, cfg):
         """Per TOD: the prior's weights and scales on the device, and the preconditioner's band factor (or its diagonal)."""
-        cfg, out = self.baseline_prior, []
+        out = []
         for i, ((D, nb), hi, (_, _, _, refs)) in enumerate(zip(sizes, hits, tods)):
             w = destripe_prior.prior_weights(self.sample_rates[i], self.baseline_samples[i], cfg["alpha"], nb)
             det_w = refs[1]  # the per-detector weight W_d (None: "uniform")

@@ -172,6 +172,31 @@ class TOD:
     def time(self):
         return self.coords.t
 
+    def psd(self, nperseg=None, field=None, ctx=None, device="cuda:0"):
+        """The Welch spectrum of every detector's row of ``field`` (default: the signal, the sum of the fields) on the
+        device: ``(f, psd)``, maria_amd.noise_estimate.welch."""
+        import torch
+
+        from .noise_estimate import welch
+
+        fields = [self.data[field]] if field is not None else list(self.data.values())
+        x = None
+        for v in fields:
+            v = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
+            dev = v.device if v.is_cuda else torch.device(device)
+            x = v.to(dev, torch.float32).clone() if x is None else x.add_(v.to(x.device, torch.float32))
+        t = np.asarray(self.coords.t, float)
+        fs = (t.size - 1) / (t[-1] - t[0])
+        return welch(x.contiguous(), fs, nperseg=nperseg, ctx=ctx)
+
+    def fit_noise(self, nperseg=None, field=None, f_min=None, f_max=None, n_bins=32, ctx=None, device="cuda:0"):
+        """Per detector, the noise law fitted to :meth:`psd` (maria_amd.noise_estimate.fit_noise): a dict of ``white``,
+        ``knee``, ``alpha``, ``sigma`` and ``knee_at_floor`` tensors."""
+        from .noise_estimate import fit_noise
+
+        f, p = self.psd(nperseg=nperseg, field=field, ctx=ctx, device=device)
+        return fit_noise(f, p, f_min=f_min, f_max=f_max, n_bins=n_bins)
+
     def to(self, units):
         """tod/tod.py:106-142 between "pW" and "K_RJ" (``mrx_tod_to_krj`` / ``mrx_tod_from_krj`` on
         every field), for a TOD that came out of ``Simulation.run``; other units stay with maria's
