@@ -835,6 +835,20 @@ int mrx_baseline_band_solve(mrx_ctx* ctx, int D, int nb, int Kp, const double* d
  *  d_psd  [D][nperseg / 2 + 1] float32, signal units^2 / Hz */
 int mrx_tod_welch(mrx_ctx* ctx, const float* d_x, size_t ld, int D, int T, int nperseg, double fs, float* d_psd);
 
+/* ---- the inverse-noise filter of the correlated-noise GLS map (maria_amd/noise_filter.py) ------------ */
+
+/* y[d] = s ⊙ (k_d ⊛ (s ⊙ x[d])): the linear (non-circular) convolution of each row with a symmetric per-detector kernel of
+ * lags k_d[0..K] (k_d[-t] = k_d[t]), samples outside [0, T) zero (a finite Toeplitz section).  Overlap-save in float32
+ * transforms of 4096 (K <= 512) or 8192 points; one workgroup per row reads each sample once, so d_y == d_x (with
+ * ld_y == ld_x) filters in place.  A NaN spoils its own row only.
+ *  d_x, d_y   [D][ld] float32
+ *  d_lags     [D][K + 1] float64
+ *  d_sqrt_w   [D][ld_w] float32 per-sample factor s (ld_w = 0: one row shared by every detector), or NULL (ones)
+ * 0 <= K <= 2048; anything else, null pointers, D < 1, T < 1, ld < T, or d_y == d_x with ld_y != ld_x -> MRX_ERR_INVALID
+ * with d_y untouched */
+int mrx_tod_noise_filter(mrx_ctx* ctx, const float* d_x, size_t ld_x, float* d_y, size_t ld_y, int D, int T,
+                         const double* d_lags, int K, const float* d_sqrt_w, size_t ld_w);
+
 /* ---- TOD pre-processing for the mappers (tod/processing.py:91-204) --------------------- */
 
 /* remove_slope (D -= linspace(D[:, 0], D[:, -1], T), processing.py:99-105) and / or window

@@ -16,7 +16,7 @@ import logging
 import numpy as np
 import torch
 
-from . import destripe_prior, noise_estimate
+from . import destripe_prior, noise_estimate, noise_filter
 from ._lib import Context, MrxSkyMap, ptr
 from .map import ProjectionMap, mueller_row
 
@@ -335,20 +335,83 @@ class MaximumLikelihoodMapper(_GlsMapper):
     (on |r| / |b|), ``rcond`` and ``noise_fit`` (``{"nperseg", "f_min", "f_max", "n_bins"}`` for "fit"; a configured
     'filter' step keeps the fit range inside its pass band).  With "fit" ``products["noise"]`` holds, per TOD, the
     fitted ``white``, ``knee``, ``alpha`` and ``sigma`` (numpy arrays).
-    Not converging is not an error: ``products["converged"]`` is False and a warning goes to the "maria" logger."""
+    Not converging is not an error: ``products["converged"]`` is False and a warning goes to the "maria" logger.
+
+    ``noise_model`` replaces W by a stationary inverse-noise filter per detector, the GLS map under
+    correlated (1/f) noise:  (P^T N^-1 P) m = P^T N^-1 d,  N^-1 = diag(s) K_d diag(s),  K_d the Toeplitz section of the
+    lags of maria_amd/noise_filter.py for the detector's law P(f) = white (1 + (knee / f)^alpha) and s the square root of
+    the pre-processing's per-sample weight.  "fit" fits the law to every pre-processed row (``noise_fit`` configures it);
+    a dict ``{"white", "knee", "alpha"}`` gives it (scalars or [ndet] arrays; knee 0 is white noise, alpha is then not
+    needed).  ``noise_filter_length`` (seconds) sets the kernel's half length K = round(length fs) <= 2048 samples
+    (default min(2048, T - 1)).  The map is solved by conjugate gradients with nearest and bilinear pointing alike (N^-1
+    couples pixels), preconditioned by the block diagonal of P^T diag(s^2 k_d[0]) P.  N^-1 carries the detector weight:
+    ``noise_weights`` must keep its default.  ``products["noise_filter"]`` holds per TOD ``K`` and the [D, K + 1]
+    ``lags``; with "fit" ``products["noise"]`` the fitted laws."""
 
     def __init__(self, tods, center, width=None, height=None, resolution=None, stokes="IQU", nu=None, frame="ra/dec", units="K_RJ",
                  degrees=True, bilinear=False, tod_preprocessing=None, noise_weights="inverse_variance", max_iter=100, tol=1e-6, rcond=1e-3,
-                 device="cuda:0", noise_fit=None):
+                 device="cuda:0", noise_fit=None, noise_model=None, noise_filter_length=None):
         self._init_grid(tods, center, width, height, resolution, stokes, nu, frame, units, degrees, bilinear, tod_preprocessing, device)
         self._init_gls(stokes, noise_weights, max_iter, tol, rcond, noise_fit)
+        self._init_noise_model(noise_model, noise_filter_length)
         self._check_noise_fit_used()
+
+    def _init_noise_model(self, model, length):
+        self.noise_model, self.noise_filter_length = model, length
+        if model is None:
+            if length is not None:
+                raise ValueError("noise_filter_length is used only with noise_model")
+            return
+        if not (isinstance(self.noise_weights, str) and self.noise_weights == "inverse_variance"):
+            raise ValueError("noise_weights cannot be set with noise_model: the inverse-noise filter carries the detector weight")
+        if isinstance(model, str):
+            if model != "fit":
+                raise ValueError(f"noise_model '{model}': 'fit' or a dict of 'white', 'knee', 'alpha'")
+        elif isinstance(model, dict):
+            if set(model) - {"white", "knee", "alpha"} or not {"white", "knee"} <= set(model):
+                raise ValueError(f"noise_model keys {sorted(model)}: 'white', 'knee' and (for a knee > 0) 'alpha'")
+            law = {k: np.asarray(v, np.float64) for k, v in model.items()}
+            if "alpha" not in law:
+                if np.any(law["knee"] != 0):
+                    raise ValueError("noise_model: 'alpha' is needed where the knee is not 0")
+                law["alpha"] = np.ones(())
+            for k, v in law.items():
+                for tod in self.tods:
+                    if v.ndim and v.shape != (tod.dets.n,):
+                        raise ValueError(f"noise_model['{k}'] has shape {v.shape}; the TOD has {tod.dets.n} detectors")
+            self.noise_model = law
+        else:
+            raise ValueError(f"noise_model {model!r}: 'fit' or a dict of 'white', 'knee', 'alpha'")
+        if length is not None and not (np.isfinite(length) and length >= 0):
+            raise ValueError(f"noise_filter_length {length!r}: a finite number of seconds >= 0")
+        for tod in self.tods:
+            self._filter_K(tod)
+
+    def _filter_K(self, tod):
+        T = tod.coords.t.size
+        if self.noise_filter_length is None:
+            return noise_filter.default_K(T)
+        K = int(round(self.noise_filter_length * self._fs(tod)))
+        if not 0 <= K <= noise_filter.MAX_LAG:
+            raise ValueError(f"noise_filter_length {self.noise_filter_length} s is {K} samples at {self._fs(tod):.6g} Hz: "
+                             f"0 .. {noise_filter.MAX_LAG}")
+        return K
+
+    @staticmethod
+    def _fs(tod):
+        t = np.asarray(tod.coords.t, float)
+        return (t.size - 1) / (t[-1] - t[0])
+
+    def _needs_fit(self):
+        return super()._needs_fit() or (isinstance(self.noise_model, str) and self.noise_model == "fit")
 
     def run(self):
         dev = self.device
         ctx = Context(dev.index or 0)
         ctx.set_stream(torch.cuda.current_stream(dev))
         sky = self._sky()
+        if self.noise_model is not None:
+            return self._run_filtered(ctx, sky)
         # per TOD (bilinear): the normal operator's arguments
         rhs, blocks, ops = self._normal_inputs(ctx, sky, "op" if self.bilinear else "none")
         solve = lambda r, nan: self._block_solve(ctx, blocks, r, nan)  # noqa: E731
@@ -378,6 +441,90 @@ class MaximumLikelihoodMapper(_GlsMapper):
 
         precond = lambda r: solve(r, False)[0]  # noqa: E731
         return self._cg(normal, precond, torch.where(mask, rhs, torch.zeros_like(rhs)))
+
+    def _run_filtered(self, ctx, sky):
+        """The GLS map under the stationary noise model: b = P^T N^-1 d, then conjugate gradients on the solved pixels with
+        the operator project -> filter (in place in one float32 TOD, sized for the largest) -> routed binning."""
+        dev = self.device
+        S, Cn = len(self.stokes), len(self.nu)
+        shape = (S, Cn, self.n_eta, self.n_xi)
+        rhs = torch.zeros(shape, dtype=torch.float64, device=dev)
+        wgt = torch.zeros_like(rhs)  # (the binning's |P| weight: not used here)
+        blocks = torch.zeros((S * (S + 1) // 2, Cn, self.n_eta, self.n_xi), dtype=torch.float64, device=dev)
+        ops, self.noise_fits = [], []
+        for tod in self.tods:
+            if tod.dets.n == 0:
+                continue
+            signal, weight, az, el, transform, dx, dy, stokes_w, d_chan = self._tod_inputs(tod, ctx, unit_i_response=self.units == "K_RJ")
+            D, T = signal.shape
+            if self._needs_fit():
+                law = self._fit_noise(ctx, signal, tod)
+                self.noise_fits.append(law)
+            else:
+                law = self.noise_model
+            K = self._filter_K(tod)
+            lag = noise_filter.lags(law["white"], law["knee"], law["alpha"], self._fs(tod), K, device=dev)
+            if lag.shape[0] == 1:
+                lag = lag.expand(D, -1)
+            lag = lag.contiguous()
+            sqrt_w = None
+            if weight is not None:  # the pre-processing's window: one row shared by every detector, as a rule
+                sqrt_w = weight[0].sqrt().contiguous() if bool((weight == weight[:1]).all()) else weight.sqrt()
+            det_w = lag[:, 0].contiguous()
+            point = (ptr(az), ptr(el), T, ptr(transform), ptr(dx), ptr(dy), ptr(stokes_w), ptr(d_chan), D)
+            ctx.call("mrx_bin_map_blocks", C.byref(sky), ptr(weight), 0 if weight is None else weight.stride(0), ptr(det_w), *point,
+                     ptr(blocks))
+            ops.append({"D": D, "T": T, "K": K, "lag": lag, "sqrt_w": sqrt_w, "point": point,
+                        "refs": (signal, weight, az, el, transform, dx, dy, stokes_w, d_chan)})
+        work = self._bin_work(ctx, sky, [(op["D"], op["T"]) for op in ops])
+        tod_buf = torch.empty(max([op["D"] * op["T"] for op in ops], default=0), dtype=torch.float32, device=dev)
+
+        def bin_into(y, buf, op):  # y += P^T buf
+            args = (C.byref(sky), ptr(buf), op["T"], None, 0, *op["point"][:-1], op["D"], ptr(y), ptr(wgt))
+            if work is None:
+                ctx.call("mrx_bin_map", *args)
+            else:
+                ctx.call("mrx_bin_map_bucketed", *args, ptr(work), work.numel())
+
+        for op in ops:  # b = P^T N^-1 d
+            buf = tod_buf[: op["D"] * op["T"]].view(op["D"], op["T"])
+            noise_filter.apply(ctx, op["refs"][0], op["lag"], op["sqrt_w"], out=buf)
+            bin_into(rhs, buf, op)
+            op["refs"] = op["refs"][1:]  # the signal is not needed any more
+        solve = lambda r, nan: self._block_solve(ctx, blocks, r, nan)  # noqa: E731
+        x, mask = solve(rhs, True)
+        residuals, converged = [], True
+        if ops:
+            def normal(v):  # P^T N^-1 P v on the solved pixels
+                y = torch.zeros_like(v)
+                for op in ops:
+                    buf = tod_buf[: op["D"] * op["T"]].view(op["D"], op["T"])
+                    ctx.call("mrx_map_project", C.byref(sky), ptr(v), *op["point"], 1.0, 0.0, ptr(buf), op["T"])
+                    noise_filter.apply(ctx, buf, op["lag"], op["sqrt_w"], out=buf)
+                    bin_into(y, buf, op)
+                return torch.where(mask, y, torch.zeros_like(y))
+
+            precond = lambda r: solve(r, False)[0]  # noqa: E731
+            x, residuals, converged = self._cg(normal, precond, torch.where(mask, rhs, torch.zeros_like(rhs)))
+        x = torch.where(mask, x, torch.full_like(x, float("nan")))
+        torch.cuda.current_stream(dev).synchronize()
+        data = x.cpu().numpy()
+        self.products = {"data": data, "weight": blocks[:1].cpu().numpy(), "blocks": blocks.cpu().numpy(), "rhs": rhs.cpu().numpy(),
+                         "residuals": np.asarray(residuals, float), "n_iter": max(len(residuals) - 1, 0), "converged": bool(converged),
+                         "noise_filter": [{"K": op["K"], "lags": op["lag"].cpu().numpy()} for op in ops]}
+        if self.noise_fits:
+            self.products["noise"] = self._noise_products()
+        return self._projection_map(data, self.products["weight"])
+
+    def _bin_work(self, ctx, sky, shapes):
+        """The routed binning's work buffer for TODs of these [D, T] shapes (None: the atomic form, mrx_bin_map)."""
+        need = 0
+        for D, T in shapes:
+            lo, full = C.c_size_t(), C.c_size_t()
+            if ctx.lib.mrx_bin_map_work_bytes(C.byref(sky), D, T, C.byref(lo), C.byref(full)) != 0:
+                return None
+            need = max(need, _work_bytes(lo.value, full.value, self.device))
+        return torch.empty(need, dtype=torch.uint8, device=self.device) if need else None
 
 
 class DestripingMapper(_GlsMapper):
