@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the atmosphere -> TOD hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config atlast_10k] [--scaling strong|weak] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config atlast_10k] [--scaling strong|weak] [--dump-outputs DIR] [--full]
 
 One step = one full pass of the path over one observation's worth of synthetic
 input for this rank's detectors: generate + smooth the turbulent screens
@@ -29,7 +29,11 @@ over ranks.  N = 1 is the named configuration on one GPU (atlast_50k: its per-GP
   * atlast_50k (config 5) is WEAK scaling (the configuration per GPU; its 288 GB TOD
     cannot be gathered onto one GPU).  --scaling overrides either default.
 
-Prints ONE JSON line on rank 0, including
+Prints ONE JSON line on rank 0.  A plain run does what that figure needs and no more: it sets up, warms up, times the K
+steps, writes --dump-outputs, times the all-gather where `value` includes it (N > 1, strong scaling), and prints the line --
+the headline, the workload, and what the timed steps' own events say (gpu_ms_per_step, stage_ms, path_hbm_gbps).
+Everything that takes runs of its own comes with --full, and the line then also holds
+  stage_ms.serial_breakdown : the step's launches back to back on one stream, outside the timed region
   roofline      : the dominant kernel -- the one-launch synthesis (atm_tod_kernel: sampler and writer roles, the HBM-bound
                   streaming write sets its time) where DevicePath.run() takes that form, else the writer (spline solve + cubic
                   upsample) --, timed live with events on the launch stream
@@ -66,10 +70,14 @@ def parse_args(argv=None):
     ap.add_argument("--scaling", choices=["strong", "weak"], default=None,
                     help="N > 1: strong = the named configuration's detectors in total (default for atlast_10k), "
                     "weak = the named configuration per GPU (default for atlast_50k)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what takes runs of its own: the serial per-stage breakdown, the roofline "
+                         "and second-kernel figures, the CPU baselines with their parity against the GPU rows, and the front end's "
+                         "wall clock (off by default: a plain run prints the headline figure)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-dets", type=int, default=2048, help="detector rows of the one-core CPU-baseline sample")
     ap.add_argument("--cpu-procs", type=int, default=0, help="processes of the all-core CPU baseline (0 = the physical cores, or the cgroup's CPU quota where smaller)")
-    ap.add_argument("--no-frontend", action="store_true", help="skip the Simulation(...).run() wall-clock section")
+    ap.add_argument("--no-frontend", action="store_true", help="with --full: skip the Simulation(...).run() wall-clock section")
     ap.add_argument("--no-screens-in-step", action="store_true", help="time TOD synthesis only (screens generated once)")
     ap.add_argument("--shard-screens", action="store_true",
                     help="N > 1: each rank generates its round-robin share of the layers and the owners broadcast them "
@@ -619,49 +627,101 @@ def run(args):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
 
-    # outside the timed region: the screens alone (on the stream they run on), then the stages back to back on one
-    # stream, for the breakdown
-    scr_ms = []
-    for k in range(4):
-        gen_stream = path._la["stream"] if lookahead else torch.cuda.current_stream()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(gen_stream)
-        screens()
-        e1.record(gen_stream)
-        torch.cuda.synchronize()
-        scr_ms.append(e0.elapsed_time(e1))
-    screens_alone_ms = float(np.median(scr_ms[1:]))
-    # (round 6: one untimed pass, then the MEDIAN of seven -- the mean of three passes, the first of them cold, scattered by
-    # +-4 % from run to run on one box, more than the differences it was read for: profiles/r06_writer_bisect.txt)
-    n_serial = 7
-    serial_step([])
-    torch.cuda.synchronize()
-    sev = []
-    for k in range(n_serial):
-        serial_step(sev)
-    torch.cuda.synchronize()
-    # per stage: the sum over a step's block launches in a pass, the median over the passes
-    per_pass = np.array([[t[i].elapsed_time(t[i + 1]) for i in range(2)] for t in sev]).reshape(n_serial, -1, 2).sum(axis=1)
-    serial_ms = np.median(per_pass, axis=0)
-    serial_up_launch_ms = float(np.median([t[1].elapsed_time(t[2]) for t in sev]))
     step_ms = np.array([[ev[k][i].elapsed_time(ev[k][i + 1]) for i in range(2)] for k in range(args.steps)]).mean(axis=0)
-    # the dominant kernel, timed live in the timed region on the stream it runs on: one launch
-    # per detector block when the step is pipelined (its rows x T samples each)
     n_launch = max(1, n_blocks if n_blocks > 1 else 1)
-    if writer_events:
-        up_ms = float(np.mean([a.elapsed_time(b) for a, b in writer_events]))
-        rows_per_launch = D / n_launch
+    if lookahead:
+        # with overlapping steps the screens run on a stream of their own, which the events on the caller's stream do not
+        # bracket: time them alone on theirs, outside the timed region
+        scr_ms = []
+        for k in range(4):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(path._la["stream"])
+            screens()
+            e1.record(path._la["stream"])
+            torch.cuda.synchronize()
+            scr_ms.append(e0.elapsed_time(e1))
+        screens_ms = float(np.median(scr_ms[1:]))
     else:
-        up_ms, rows_per_launch = serial_up_launch_ms, D / n_launch
-    writer_bytes = 4.0 * rows_per_launch * T + 4.0 * rows_per_launch * Ta + 8.0 * T  # TOD write + coarse loading read + sample times read
-    # one launch: the kernel IS the atmosphere -> TOD path (SURVEY 8(d)'s B_alg: TOD + coarse loading written and read +
-    # every screen once + inputs); otherwise the writer's launch
-    up_bytes = float(path.algorithmic_bytes()) if one_launch else writer_bytes
-    achieved = up_bytes / (up_ms * 1e-3) / 1e9
-    alone = writer_bytes / (serial_up_launch_ms * 1e-3) / 1e9
-    # the sampler: 4 B/det-step written + each screen read once + inputs (it is not HBM-bound)
-    sm_ms = float(serial_ms[0])
-    sm_bytes = 4.0 * D * Ta + 4.0 * sum(len(l["extrusion"]) * len(l["cross_section"]) for l in problem["layers"]) + 8.0 * Ta + 8.0 * D
+        screens_ms = float(step_ms[0])
+
+    def kernel_figures():
+        """--full: the stages back to back on one stream, outside the timed region; returns the serial breakdown, the
+        roofline of the dominant kernel and the second kernel's figures."""
+        # (round 6: one untimed pass, then the MEDIAN of seven -- the mean of three passes, the first of them cold, scattered by
+        # +-4 % from run to run on one box, more than the differences it was read for: profiles/r06_writer_bisect.txt)
+        n_serial = 7
+        serial_step([])
+        torch.cuda.synchronize()
+        sev = []
+        for k in range(n_serial):
+            serial_step(sev)
+        torch.cuda.synchronize()
+        # per stage: the sum over a step's block launches in a pass, the median over the passes
+        per_pass = np.array([[t[i].elapsed_time(t[i + 1]) for i in range(2)] for t in sev]).reshape(n_serial, -1, 2).sum(axis=1)
+        serial_ms = np.median(per_pass, axis=0)
+        serial_up_launch_ms = float(np.median([t[1].elapsed_time(t[2]) for t in sev]))
+        # the dominant kernel, timed live in the timed region on the stream it runs on: one launch
+        # per detector block when the step is pipelined (its rows x T samples each)
+        if writer_events:
+            up_ms = float(np.mean([a.elapsed_time(b) for a, b in writer_events]))
+            rows_per_launch = D / n_launch
+        else:
+            up_ms, rows_per_launch = serial_up_launch_ms, D / n_launch
+        writer_bytes = 4.0 * rows_per_launch * T + 4.0 * rows_per_launch * Ta + 8.0 * T  # TOD write + coarse loading read + sample times read
+        # one launch: the kernel IS the atmosphere -> TOD path (SURVEY 8(d)'s B_alg: TOD + coarse loading written and read +
+        # every screen once + inputs); otherwise the writer's launch
+        up_bytes = float(path.algorithmic_bytes()) if one_launch else writer_bytes
+        achieved = up_bytes / (up_ms * 1e-3) / 1e9
+        alone = writer_bytes / (serial_up_launch_ms * 1e-3) / 1e9
+        # the sampler: 4 B/det-step written + each screen read once + inputs (it is not HBM-bound)
+        sm_ms = float(serial_ms[0])
+        sm_bytes = 4.0 * D * Ta + 4.0 * sum(len(l["extrusion"]) * len(l["cross_section"]) for l in problem["layers"]) + 8.0 * Ta + 8.0 * D
+        serial_breakdown = {"sample": sm_ms, "upsample_with_spline_solve": float(serial_ms[1]),
+                            "note": "the same block launches back to back on one stream, outside the timed region; sums over the blocks, "
+                                    "median of seven passes after an untimed one"}
+        roofline = {
+            "kernel": "atm_tod_kernel" if one_launch else "spline_upsample_fused_kernel",
+            "bound": "hbm",
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBPS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBPS,
+            "traffic": None,
+            "bytes_per_launch": up_bytes,
+            "ms_per_launch": up_ms,
+            "launches_per_step": n_launch,
+            "note": ("the whole atmosphere -> TOD synthesis in one launch, timed in the timed region: its algorithmic bytes are the "
+                     "path's (TOD + coarse loading + screens + inputs); the stand-alone writer (spline_upsample_fused_kernel, "
+                     "serial breakdown) reaches frac_alone on its own bytes") if one_launch else
+                    "timed in the timed region, where each launch shares the chip with the next block's sampler; "
+                    "the same launches back to back on one stream (serial breakdown) reach frac_alone",
+            "frac_alone": alone / HBM_PEAK_GBPS,
+        }
+        second_kernel = {
+            "kernel": "atm_sample_px_kernel",
+            "bound": "valu + vector-memory latency (not hbm): see DESIGN 3.2 and profiles/r04_50k_kernel_pmc.txt",
+            "ms_per_step": sm_ms,
+            "launches_per_step": n_launch,
+            "note": "sum over the step's block launches run back to back on one stream (serial breakdown)",
+            "bytes_per_step": sm_bytes,
+            "achieved_GBps": sm_bytes / (sm_ms * 1e-3) / 1e9,
+            "layer_samples_per_s": D * Ta * L / (sm_ms * 1e-3),
+        }
+        # HBM bytes per launch of the dominant kernel from the PMC counters: collected in separate rocprofv3 --pmc
+        # passes (counters are never collected inside a timed run), stored with their method under profiles/, and
+        # quoted here for the matching configuration
+        for name in TRAFFIC_FILES:
+            traffic_file = os.path.join(ROOT, "profiles", name)
+            if not os.path.exists(traffic_file):
+                continue
+            with open(traffic_file) as f:
+                tr = json.load(f)
+            if tr.get("config") == args.config and tr.get("kernel") == roofline["kernel"] and world == 1:
+                # per launch of the profiled run; scaled by rows when this run cuts the shard differently
+                roofline["traffic"] = tr["hbm_bytes_per_launch"] * tr.get("launches_per_step", 1) / n_launch
+                roofline["traffic_source"] = tr["source"]
+                break
+        return serial_breakdown, roofline, second_kernel
 
     n_step = n_total if world > 1 and scaling == "strong" else D * world
     result = {
@@ -698,70 +758,26 @@ def run(args):
         # wall-clock figure above should sit within a few per cent of it; a host hiccup inside the timed region shows here
         "gpu_ms_per_step": float(ev[0][0].elapsed_time(ev[-1][2])) / args.steps,
         "stage_ms": {
-            "screens": screens_alone_ms if lookahead else float(step_ms[0]),
+            "screens": screens_ms,
             "tod_synthesis_pipelined": float(step_ms[1]),
             "note": ("screens: alone on their stream, outside the timed region; tod_synthesis_pipelined: between the events around "
                      "DevicePath.run() on the caller's stream -- with overlapping steps these intervals overlap too and do not add up to ms_per_step")
             if lookahead else "events on the caller's stream around the two stages of every timed step",
-            "serial_breakdown": {"sample": sm_ms, "upsample_with_spline_solve": float(serial_ms[1]),
-                                 "note": "the same block launches back to back on one stream, outside the timed region; sums over the blocks, "
-                                         "median of seven passes after an untimed one"},
             "detector_blocks": n_launch,
             "form": ("one launch (mrx_atm_synthesize): sampler and writer as two roles of one grid, hand-over on the device"
                      if one_launch else "detector blocks pipelined on two streams" if n_blocks > 1 else "stages back to back on one stream"),
         },
         "path_hbm_gbps": path.algorithmic_bytes() / (float(ev[0][0].elapsed_time(ev[-1][2])) / args.steps * 1e-3) / 1e9,
-        "roofline": {
-            "kernel": "atm_tod_kernel" if one_launch else "spline_upsample_fused_kernel",
-            "bound": "hbm",
-            "achieved": achieved,
-            "peak": HBM_PEAK_GBPS,
-            "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBPS,
-            "traffic": None,
-            "bytes_per_launch": up_bytes,
-            "ms_per_launch": up_ms,
-            "launches_per_step": n_launch,
-            "note": ("the whole atmosphere -> TOD synthesis in one launch, timed in the timed region: its algorithmic bytes are the "
-                     "path's (TOD + coarse loading + screens + inputs); the stand-alone writer (spline_upsample_fused_kernel, "
-                     "serial breakdown) reaches frac_alone on its own bytes") if one_launch else
-                    "timed in the timed region, where each launch shares the chip with the next block's sampler; "
-                    "the same launches back to back on one stream (serial breakdown) reach frac_alone",
-            "frac_alone": alone / HBM_PEAK_GBPS,
-        },
-        "second_kernel": {
-            "kernel": "atm_sample_px_kernel",
-            "bound": "valu + vector-memory latency (not hbm): see DESIGN 3.2 and profiles/r04_50k_kernel_pmc.txt",
-            "ms_per_step": sm_ms,
-            "launches_per_step": n_launch,
-            "note": "sum over the step's block launches run back to back on one stream (serial breakdown)",
-            "bytes_per_step": sm_bytes,
-            "achieved_GBps": sm_bytes / (sm_ms * 1e-3) / 1e9,
-            "layer_samples_per_s": D * Ta * L / (sm_ms * 1e-3),
-        },
         "flags": int(flags),
     }
     if weak_unit:
         result["config"]["weak_unit"] = weak_unit
     if dumped is not None:
         result["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped, "seed": DUMP_SEED}
+    if args.full:
+        result["stage_ms"]["serial_breakdown"], result["roofline"], result["second_kernel"] = kernel_figures()
 
-    # HBM bytes per launch of the dominant kernel from the PMC counters: collected in
-    # separate rocprofv3 --pmc passes (gpurun refuses --pmc inside an ordinary run), stored
-    # with their method under profiles/, and quoted here for the matching configuration
-    for name in TRAFFIC_FILES:
-        traffic_file = os.path.join(ROOT, "profiles", name)
-        if not os.path.exists(traffic_file):
-            continue
-        with open(traffic_file) as f:
-            tr = json.load(f)
-        if tr.get("config") == args.config and tr.get("kernel") == result["roofline"]["kernel"] and world == 1:
-            # per launch of the profiled run; scaled by rows when this run cuts the shard differently
-            result["roofline"]["traffic"] = tr["hbm_bytes_per_launch"] * tr.get("launches_per_step", 1) / n_launch
-            result["roofline"]["traffic_source"] = tr["source"]
-            break
-
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import threadpoolctl
 
         n_sub = min(args.cpu_dets, D)
@@ -799,7 +815,7 @@ def run(args):
         except Exception as exc:  # pragma: no cover - depends on the host
             result["cpu_baseline"]["all_cores"] = {"error": f"{type(exc).__name__}: {exc}"[:300]}
 
-    if rank == 0 and world == 1 and not args.no_frontend and args.config == "atlast_10k":
+    if args.full and rank == 0 and world == 1 and not args.no_frontend and args.config == "atlast_10k":
         del tod
         path._pipe = None
         torch.cuda.empty_cache()

@@ -4,7 +4,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 TAG=$1; shift
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- python3 $ROOT/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-frontend "$@" > $OUT/bench.json 2> $OUT/stats.log || { tail -5 $OUT/stats.log; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- python3 $ROOT/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-frontend "$@" > $OUT/bench.json 2> $OUT/stats.log || { tail -5 $OUT/stats.log; exit 1; }
 python3 - $OUT <<'PY'
 import csv, sys, glob
 f = glob.glob(sys.argv[1] + "/stats/**/run_kernel_stats.csv", recursive=True)[0]

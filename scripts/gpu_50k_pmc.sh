@@ -6,7 +6,7 @@ TAG=${1:-pmc50k}; BLOCKS=${2:-1}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --config atlast_50k --no-cpu-baseline --no-frontend --steps 2 --warmup 1 --blocks $BLOCKS"
+B="python3 $ROOT/bench.py --full --config atlast_50k --no-cpu-baseline --no-frontend --steps 2 --warmup 1 --blocks $BLOCKS"
 i=0
 for set in "TCP_TCC_READ_REQ_sum TCC_HIT_sum TCC_MISS_sum" "FETCH_SIZE" "WRITE_SIZE" "SQ_WAIT_ANY SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_SALU" "TA_TA_BUSY_sum TA_BUSY_avr TCP_TOTAL_CACHE_ACCESSES_sum GRBM_GUI_ACTIVE"; do
   i=$((i+1))

@@ -8,7 +8,9 @@ mkdir -p $OUT
 for rep in $(seq 1 $REPS); do
   for tree in $(ls -d $ROOT/scripts/ab/trees/*/ 2>/dev/null) $ROOT/; do
     cd $tree
-    timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-frontend --steps 20 --warmup 5 "$@" > $OUT/b.json 2> $OUT/b.err || { tail -5 $OUT/b.err; exit 1; }
+    # the breakdown read below: behind --full where the tree's bench.py has that option, printed by default before it
+    FULL=$(grep -qs -- '"--full"' bench.py && echo --full)
+    timeout -k 10 300 python3 bench.py $FULL --no-cpu-baseline --no-frontend --steps 20 --warmup 5 "$@" > $OUT/b.json 2> $OUT/b.err || { tail -5 $OUT/b.err; exit 1; }
     python3 -c "
 import json; r = json.load(open('$OUT/b.json')); sb = r['stage_ms']['serial_breakdown']
 print('$(basename $tree)'.ljust(10), 'ms_per_step %.3f' % r['ms_per_step'], 'kernel %.3f' % r['roofline']['ms_per_launch'], 'frac %.3f' % r['roofline']['frac'],

@@ -12,7 +12,7 @@ if [ -n "$TESTS" ]; then
   timeout -k 10 900 python3 -m pytest $TESTS -x -q -m gpu > $OUT/pytest.log 2>&1
   echo "pytest rc=$?"; tail -4 $OUT/pytest.log
 fi
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 "$@" > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 3 "$@" > $OUT/bench.json 2> $OUT/bench.err
 echo "bench rc=$?"
 python3 - $OUT/bench.json <<'PY'
 import json, sys

@@ -5,7 +5,7 @@ TAG=$1; shift
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o run -- python3 $ROOT/bench.py --no-cpu-baseline --no-frontend --steps 6 --warmup 2 "$@" > $OUT/trace_bench.json 2> $OUT/trace.log
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o run -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-frontend --steps 6 --warmup 2 "$@" > $OUT/trace_bench.json 2> $OUT/trace.log
 F=$(ls $OUT/trace/*/run_kernel_trace.csv $OUT/trace/run_kernel_trace.csv 2>/dev/null | head -1)
 python3 - "$F" <<'PY'
 import csv, sys

@@ -71,7 +71,7 @@ def main():
                     cnt[(name, row["Counter_Name"])] += 1
         except OSError:
             continue
-        lines.append(f"# pass {sub}: rocprofv3 --kernel-trace --pmc <counters below> -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-frontend")
+        lines.append(f"# pass {sub}: rocprofv3 --kernel-trace --pmc <counters below> -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-frontend")
         for k in sorted(tot):
             if k.startswith("__amd") or k.startswith("at::") or k.startswith("plan_"):
                 continue

@@ -9,7 +9,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --no-cpu-baseline --no-frontend"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-frontend"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- $B --steps 10 --warmup 3 > $OUT/bench_under_rocprof.json 2> $OUT/stats.log
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o run -- $B --steps 3 --warmup 1 > $OUT/pmc_fetch.json 2> $OUT/pmc_fetch.log
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o run -- $B --steps 3 --warmup 1 > $OUT/pmc_write.json 2> $OUT/pmc_write.log
@@ -25,5 +25,5 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/frontend_map -o run
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/gauss -o run -- python3 $ROOT/scripts/gauss_bench.py 10 > $OUT/gauss_bench.log 2>&1
 cd $ROOT
 MRX_GAUSS_ACCUM=1 python3 scripts/gauss_bench.py 10 > $OUT/gauss_bench_exact.log 2>&1
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.log
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.log
 tail -c 400 $OUT/bench.json

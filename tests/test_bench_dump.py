@@ -76,3 +76,9 @@ def test_steps_and_dump_arguments():
     assert bench.parse_args([]).dump_outputs is None
     with pytest.raises(SystemExit):
         bench.parse_args(["--steps", "0"])
+
+
+def test_full_is_off_by_default():
+    assert bench.parse_args([]).full is False
+    args = bench.parse_args(["--steps", "7", "--warmup", "0", "--full", "--no-frontend"])
+    assert args.full and args.no_frontend and args.steps == 7 and args.warmup == 0
