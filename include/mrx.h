@@ -849,6 +849,25 @@ int mrx_tod_welch(mrx_ctx* ctx, const float* d_x, size_t ld, int D, int T, int n
 int mrx_tod_noise_filter(mrx_ctx* ctx, const float* d_x, size_t ld_x, float* d_y, size_t ld_y, int D, int T,
                          const double* d_lags, int K, const float* d_sqrt_w, size_t ld_w);
 
+/* ---- noise shared across detectors in the GLS map: m common modes (maria_amd/noise_modes.py) --------- */
+
+/* y[d] = s ⊙ (k_d ⊛ (s ⊙ (x[d] - sum_j U[d, j] b[j]))): mrx_tod_noise_filter of the rows less their rank-m part.  Two
+ * passes: y = x - U b (float32, streaming: x read once, y written once), then the filter of y in place; d_y == d_x (with
+ * ld_y == ld_x) works in place.  m = 0 is mrx_tod_noise_filter, bit for bit (U and b are not read).
+ *  d_U  [D][m] float64 coupling of detector d to mode j
+ *  d_b  [m][T] float32 mode series
+ * mrx_tod_noise_filter's refusals, m outside 0 .. 16, or (m > 0) a null U or b -> MRX_ERR_INVALID with d_y untouched */
+int mrx_tod_noise_filter_modes(mrx_ctx* ctx, const float* d_x, size_t ld_x, float* d_y, size_t ld_y, int D, int T,
+                               const double* d_lags, int K, const float* d_sqrt_w, size_t ld_w, const double* d_U, int m,
+                               const float* d_b);
+
+/* a[j, t] = sum_d U[d, j] x[d, t], summed in float64: the projection of a [D][ld_x] float32 TOD onto m <= 16 detector
+ * patterns, reading every sample once.  Deterministic (no atomics: the partial sums of a sample meet in one workgroup).
+ *  d_U  [D][m] float64
+ *  d_a  [m][T] float64
+ * null pointers, D < 1, T < 1, m outside 1 .. 16 or ld_x < T -> MRX_ERR_INVALID with d_a untouched */
+int mrx_tod_mode_project(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, const double* d_U, int m, double* d_a);
+
 /* ---- TOD pre-processing for the mappers (tod/processing.py:91-204) --------------------- */
 
 /* remove_slope (D -= linspace(D[:, 0], D[:, -1], T), processing.py:99-105) and / or window

@@ -16,7 +16,7 @@ import logging
 import numpy as np
 import torch
 
-from . import destripe_prior, noise_estimate, noise_filter
+from . import destripe_prior, noise_estimate, noise_filter, noise_modes
 from ._lib import Context, MrxSkyMap, ptr
 from .map import ProjectionMap, mueller_row
 
@@ -346,18 +346,32 @@ class MaximumLikelihoodMapper(_GlsMapper):
     (default min(2048, T - 1)).  The map is solved by conjugate gradients with nearest and bilinear pointing alike (N^-1
     couples pixels), preconditioned by the block diagonal of P^T diag(s^2 k_d[0]) P.  N^-1 carries the detector weight:
     ``noise_weights`` must keep its default.  ``products["noise_filter"]`` holds per TOD ``K`` and the [D, K + 1]
-    ``lags``; with "fit" ``products["noise"]`` the fitted laws."""
+    ``lags``; with "fit" ``products["noise"]`` the fitted laws.
+
+    Noise shared across detectors: N = (S A S)^-1 + U C U^T, m <= 16 stationary 1/f modes that detector d
+    sees with the constant weight U[d, j] (maria_amd/noise_modes.py).  ``noise_modes=m`` with noise_model="fit" fits
+    them to every TOD (the top m eigenvectors of the whitened rows' Gram, the mode laws fitted to their series, the
+    detector laws refitted without them); a dict model gives them as ``"modes"`` (a [D, m] coupling in the TOD's units)
+    and ``"mode_law"`` (``{"white", "knee", "alpha"}``, scalars or [m] arrays).  Modes need one pre-processing weight row
+    shared by every detector.  ``products["noise_modes"]`` holds per TOD ``modes``, ``mode_law``, ``dropped`` (the
+    fitted modes whose law failed) and the inner solve's iterations (``inner_iter_max``, ``inner_iter_total``)."""
 
     def __init__(self, tods, center, width=None, height=None, resolution=None, stokes="IQU", nu=None, frame="ra/dec", units="K_RJ",
                  degrees=True, bilinear=False, tod_preprocessing=None, noise_weights="inverse_variance", max_iter=100, tol=1e-6, rcond=1e-3,
-                 device="cuda:0", noise_fit=None, noise_model=None, noise_filter_length=None):
+                 device="cuda:0", noise_fit=None, noise_model=None, noise_filter_length=None, noise_modes=None):
         self._init_grid(tods, center, width, height, resolution, stokes, nu, frame, units, degrees, bilinear, tod_preprocessing, device)
         self._init_gls(stokes, noise_weights, max_iter, tol, rcond, noise_fit)
         self._init_noise_model(noise_model, noise_filter_length)
+        self._init_noise_modes(noise_modes)
         self._check_noise_fit_used()
 
     def _init_noise_model(self, model, length):
         self.noise_model, self.noise_filter_length = model, length
+        self.mode_model = None  # a dict model's (coupling [D, m], mode law)
+        if isinstance(model, dict) and ("modes" in model or "mode_law" in model):
+            model = dict(model)
+            coupling, mode_law = model.pop("modes", None), model.pop("mode_law", None)
+            self.mode_model = self._check_mode_model(coupling, mode_law)
         if model is None:
             if length is not None:
                 raise ValueError("noise_filter_length is used only with noise_model")
@@ -386,6 +400,55 @@ class MaximumLikelihoodMapper(_GlsMapper):
             raise ValueError(f"noise_filter_length {length!r}: a finite number of seconds >= 0")
         for tod in self.tods:
             self._filter_K(tod)
+
+    def _check_mode_model(self, coupling, mode_law):
+        if coupling is None:
+            raise ValueError("noise_model: 'mode_law' is used only with 'modes'")
+        if mode_law is None:
+            raise ValueError("noise_model: 'modes' needs 'mode_law' ({'white', 'knee', 'alpha'})")
+        U = np.asarray(coupling, np.float64)
+        if U.ndim != 2:
+            raise ValueError(f"noise_model['modes'] has shape {U.shape}: [ndet, m]")
+        m = U.shape[1]
+        for tod in self.tods:
+            if U.shape[0] != tod.dets.n:
+                raise ValueError(f"noise_model['modes'] has shape {U.shape}; the TOD has {tod.dets.n} detectors")
+        self._check_mode_count(m)
+        if not np.all(np.isfinite(U)):
+            raise ValueError("noise_model['modes'] must be finite")
+        if not isinstance(mode_law, dict) or set(mode_law) - {"white", "knee", "alpha"} or not {"white", "knee"} <= set(mode_law):
+            raise ValueError(f"noise_model['mode_law'] {mode_law!r}: a dict of 'white', 'knee' and (for a knee > 0) 'alpha'")
+        law = {k: np.asarray(v, np.float64) for k, v in mode_law.items()}
+        if "alpha" not in law:
+            if np.any(law["knee"] != 0):
+                raise ValueError("noise_model['mode_law']: 'alpha' is needed where the knee is not 0")
+            law["alpha"] = np.ones(())
+        for k, v in law.items():
+            if v.ndim and v.shape != (m,):
+                raise ValueError(f"noise_model['mode_law']['{k}'] has shape {v.shape}; there are {m} modes")
+        return U, law
+
+    def _check_mode_count(self, m):
+        if not 1 <= m <= noise_modes.MAX_MODES:
+            raise ValueError(f"{m} noise modes: 1 .. {noise_modes.MAX_MODES}")
+        for tod in self.tods:
+            if tod.dets.n and m >= tod.dets.n:
+                raise ValueError(f"{m} noise modes for a TOD of {tod.dets.n} detectors: fewer modes than detectors")
+
+    def _init_noise_modes(self, modes):
+        self.noise_modes = modes
+        if modes is None:
+            return
+        if self.noise_model is None:
+            raise ValueError("noise_modes is used only with noise_model='fit'")
+        if self.mode_model is not None:
+            raise ValueError("noise_modes fits the modes; the noise_model dict gives them ('modes'): not both")
+        if not (isinstance(self.noise_model, str) and self.noise_model == "fit"):
+            raise ValueError("noise_modes is used only with noise_model='fit' (a dict gives the modes as 'modes' and 'mode_law')")
+        if isinstance(modes, bool) or not isinstance(modes, (int, np.integer)):
+            raise ValueError(f"noise_modes {modes!r}: an integer number of modes")
+        self._check_mode_count(int(modes))
+        self.noise_modes = int(modes)
 
     def _filter_K(self, tod):
         T = tod.coords.t.size
@@ -452,16 +515,26 @@ class MaximumLikelihoodMapper(_GlsMapper):
         wgt = torch.zeros_like(rhs)  # (the binning's |P| weight: not used here)
         blocks = torch.zeros((S * (S + 1) // 2, Cn, self.n_eta, self.n_xi), dtype=torch.float64, device=dev)
         ops, self.noise_fits = [], []
+        mode_products = []
         for tod in self.tods:
             if tod.dets.n == 0:
                 continue
             signal, weight, az, el, transform, dx, dy, stokes_w, d_chan = self._tod_inputs(tod, ctx, unit_i_response=self.units == "K_RJ")
             D, T = signal.shape
-            if self._needs_fit():
+            U = mode_law = None
+            dropped = np.zeros(0, np.int64)
+            if self._needs_fit() and self.noise_modes:
+                fitted = noise_modes.fit(ctx, signal, self.noise_modes, lambda rows: self._fit_noise(ctx, rows, tod))  # noqa: B023
+                law, U, mode_law, dropped = fitted["law"], fitted["modes"], fitted["mode_law"], fitted["dropped"]
+                self.noise_fits.append(law)
+            elif self._needs_fit():
                 law = self._fit_noise(ctx, signal, tod)
                 self.noise_fits.append(law)
             else:
                 law = self.noise_model
+                if self.mode_model is not None:
+                    U = torch.as_tensor(self.mode_model[0]).to(dev)
+                    mode_law = self.mode_model[1]
             K = self._filter_K(tod)
             lag = noise_filter.lags(law["white"], law["knee"], law["alpha"], self._fs(tod), K, device=dev)
             if lag.shape[0] == 1:
@@ -470,14 +543,33 @@ class MaximumLikelihoodMapper(_GlsMapper):
             sqrt_w = None
             if weight is not None:  # the pre-processing's window: one row shared by every detector, as a rule
                 sqrt_w = weight[0].sqrt().contiguous() if bool((weight == weight[:1]).all()) else weight.sqrt()
+            model = None
+            if U is not None:
+                if sqrt_w is not None and sqrt_w.dim() == 2:
+                    raise ValueError("noise modes need one pre-processing weight row shared by every detector; this TOD's differ by row")
+                if U.shape[1]:
+                    beta = noise_modes.mode_lags(mode_law, self._fs(tod), K, device=dev)
+                    if beta.shape[0] == 1:
+                        beta = beta.expand(U.shape[1], -1)
+                    model = noise_modes.ModeModel(U, beta.contiguous(), lag, sqrt_w, T, noise_modes.inner_tol(self.tol))
+                mode_products.append({"modes": U, "mode_law": mode_law, "dropped": dropped, "model": model})
             det_w = lag[:, 0].contiguous()
             point = (ptr(az), ptr(el), T, ptr(transform), ptr(dx), ptr(dy), ptr(stokes_w), ptr(d_chan), D)
             ctx.call("mrx_bin_map_blocks", C.byref(sky), ptr(weight), 0 if weight is None else weight.stride(0), ptr(det_w), *point,
                      ptr(blocks))
-            ops.append({"D": D, "T": T, "K": K, "lag": lag, "sqrt_w": sqrt_w, "point": point,
+            ops.append({"D": D, "T": T, "K": K, "lag": lag, "sqrt_w": sqrt_w, "point": point, "modes": model,
                         "refs": (signal, weight, az, el, transform, dx, dy, stokes_w, d_chan)})
         work = self._bin_work(ctx, sky, [(op["D"], op["T"]) for op in ops])
         tod_buf = torch.empty(max([op["D"] * op["T"] for op in ops], default=0), dtype=torch.float32, device=dev)
+        # the modes' second TOD, z = A' x of step 1 (noise_modes.apply)
+        mode_buf = torch.empty(max([op["D"] * op["T"] for op in ops if op["modes"] is not None], default=0), dtype=torch.float32, device=dev)
+
+        def inv_noise(x, buf, op):  # buf = N^-1 x (buf may be x)
+            if op["modes"] is None:
+                noise_filter.apply(ctx, x, op["lag"], op["sqrt_w"], out=buf)
+            else:
+                scratch = mode_buf[: op["D"] * op["T"]].view(op["D"], op["T"])
+                noise_modes.apply(ctx, x, op["lag"], op["sqrt_w"], op["modes"], out=buf, scratch=scratch)
 
         def bin_into(y, buf, op):  # y += P^T buf
             args = (C.byref(sky), ptr(buf), op["T"], None, 0, *op["point"][:-1], op["D"], ptr(y), ptr(wgt))
@@ -488,7 +580,7 @@ class MaximumLikelihoodMapper(_GlsMapper):
 
         for op in ops:  # b = P^T N^-1 d
             buf = tod_buf[: op["D"] * op["T"]].view(op["D"], op["T"])
-            noise_filter.apply(ctx, op["refs"][0], op["lag"], op["sqrt_w"], out=buf)
+            inv_noise(op["refs"][0], buf, op)
             bin_into(rhs, buf, op)
             op["refs"] = op["refs"][1:]  # the signal is not needed any more
         solve = lambda r, nan: self._block_solve(ctx, blocks, r, nan)  # noqa: E731
@@ -500,7 +592,7 @@ class MaximumLikelihoodMapper(_GlsMapper):
                 for op in ops:
                     buf = tod_buf[: op["D"] * op["T"]].view(op["D"], op["T"])
                     ctx.call("mrx_map_project", C.byref(sky), ptr(v), *op["point"], 1.0, 0.0, ptr(buf), op["T"])
-                    noise_filter.apply(ctx, buf, op["lag"], op["sqrt_w"], out=buf)
+                    inv_noise(buf, buf, op)
                     bin_into(y, buf, op)
                 return torch.where(mask, y, torch.zeros_like(y))
 
@@ -514,7 +606,16 @@ class MaximumLikelihoodMapper(_GlsMapper):
                          "noise_filter": [{"K": op["K"], "lags": op["lag"].cpu().numpy()} for op in ops]}
         if self.noise_fits:
             self.products["noise"] = self._noise_products()
+        if mode_products:
+            self.products["noise_modes"] = [self._mode_product(p) for p in mode_products]
         return self._projection_map(data, self.products["weight"])
+
+    @staticmethod
+    def _mode_product(p):
+        as_np = lambda v: v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)  # noqa: E731
+        its = p["model"].inner.iterations if p["model"] is not None else []
+        return {"modes": as_np(p["modes"]), "mode_law": {k: as_np(v) for k, v in p["mode_law"].items()}, "dropped": as_np(p["dropped"]),
+                "inner_iter_max": max(its, default=0), "inner_iter_total": int(sum(its))}
 
     def _bin_work(self, ctx, sky, shapes):
         """The routed binning's work buffer for TODs of these [D, T] shapes (None: the atomic form, mrx_bin_map)."""
