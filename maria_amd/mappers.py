@@ -6,12 +6,15 @@ mappers/base.py:138 does; the map post-processing pipeline stays with maria's fr
 
 ``MaximumLikelihoodMapper`` (maria/mappers/ml_mapper.py): the white-noise GLS map, I, Q and U solved jointly, on the
 same grid and pointing, with the operators of DESIGN 3.12 (``mrx_bin_map_blocks``, ``mrx_map_block_solve``,
-``mrx_map_normal_apply``)."""
+``mrx_map_normal_apply``).  It and ``DestripingMapper`` share one assembly loop over the TODs (``_assemble``, with
+``_tod_weights`` the step the noise model decides), one solve (``_solve``) and one set of products (``_finish``)."""
 
 from __future__ import annotations
 
 import ctypes as C
 import logging
+from types import SimpleNamespace
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -35,15 +38,40 @@ def _work_bytes(lo, full, device):
     return max(lo, min(full, BIN_WORK_LIMIT_BYTES, max(free // 2, lo)))
 
 
-def bin_map(ctx, sky, signal, weight, az, el, transform, dx, dy, stokes_w, channel, msum, mwgt, bucketed=None):
-    """``map_sum += (W * D) @ P``, ``map_wgt += W @ |P|`` for one TOD on the device
+class TodInputs(NamedTuple):
+    """One TOD on the device: the signal [D, T] a mapper bins, its per-sample weight (None for ones) and the pointing."""
+
+    signal: torch.Tensor
+    weight: torch.Tensor | None
+    az: torch.Tensor
+    el: torch.Tensor
+    transform: torch.Tensor | None
+    dx: torch.Tensor
+    dy: torch.Tensor
+    stokes_w: torch.Tensor
+    channel: torch.Tensor
+
+    @property
+    def shape(self):
+        return tuple(self.signal.shape)
+
+    @property
+    def point(self):
+        """The pointing arguments of the map operators, from the boresight to the detector count."""
+        D, T = self.signal.shape
+        return (ptr(self.az), ptr(self.el), T, ptr(self.transform), ptr(self.dx), ptr(self.dy), ptr(self.stokes_w), ptr(self.channel), D)
+
+
+def bin_map(ctx, sky, inp, msum, mwgt, bucketed=None):
+    """``map_sum += (W * D) @ P``, ``map_wgt += W @ |P|`` for one TOD on the device, ``inp`` its ``TodInputs``
     (mappers/bin_mapper.py:84-120).  Maps of up to 2048 regions of 64 x 32 pixels take
     ``mrx_bin_map_bucketed`` (samples routed to map regions, summed in LDS: no scattered global
     atomics); larger ones ``mrx_bin_map`` (float64 atomics).  ``bucketed``: force (True) or
     forbid (False) the first form."""
+    signal, weight = inp.signal, inp.weight
     D, T = signal.shape
-    args = (C.byref(sky), ptr(signal), signal.stride(0), ptr(weight), 0 if weight is None else weight.stride(0),
-            ptr(az), ptr(el), T, ptr(transform), ptr(dx), ptr(dy), ptr(stokes_w), ptr(channel), D, ptr(msum), ptr(mwgt))
+    args = (C.byref(sky), ptr(signal), signal.stride(0), ptr(weight), 0 if weight is None else weight.stride(0), *inp.point,
+            ptr(msum), ptr(mwgt))
     lo, full = C.c_size_t(), C.c_size_t()
     fits = ctx.lib.mrx_bin_map_work_bytes(C.byref(sky), D, T, C.byref(lo), C.byref(full)) == 0
     if bucketed is True and not fits:
@@ -90,8 +118,13 @@ class _GridMapper:
         return MrxSkyMap(None, len(self.nu), len(self.stokes), self.n_eta, self.n_xi, float(self.eta[0]), float(deta), float(self.xi[0]),
                          float(dxi), float(self.center[0]), float(self.center[1]), 1 if self.bilinear else 0, 0)
 
+    def _context(self):
+        ctx = Context(self.device.index or 0)
+        ctx.set_stream(torch.cuda.current_stream(self.device))
+        return ctx
+
     def _tod_inputs(self, tod, ctx, unit_i_response=False):
-        """(signal, weight, az, el, transform, dx, dy, stokes_w, channel) of one TOD on the device; weight None for ones.
+        """The ``TodInputs`` (signal, weight, az, el, transform, dx, dy, stokes_w, channel) of one TOD; weight None for ones.
         ``unit_i_response``: the Stokes weights over the detector's I weight (its Mueller [0, 0])."""
         from .sim import sky_transform_stack
 
@@ -127,7 +160,7 @@ class _GridMapper:
         d_chan = torch.as_tensor(chan).to(dev)
         az, el = f32(coords._baz), f32(coords._bel)
         dx, dy = f32(coords.offsets[:, 0]), f32(coords.offsets[:, 1])
-        return signal, weight, az, el, transform, dx, dy, stokes_w, d_chan
+        return TodInputs(signal, weight, az, el, transform, dx, dy, stokes_w, d_chan)
 
     def _projection_map(self, data, weight):
         out = ProjectionMap.__new__(ProjectionMap)
@@ -156,8 +189,7 @@ class BinMapper(_GridMapper):
 
     def run(self):
         dev = self.device
-        ctx = Context(dev.index or 0)
-        ctx.set_stream(torch.cuda.current_stream(dev))
+        ctx = self._context()
         S, Cn = len(self.stokes), len(self.nu)
         msum = torch.zeros((S, Cn, self.n_eta, self.n_xi), dtype=torch.float64, device=dev)
         mwgt = torch.zeros_like(msum)
@@ -165,8 +197,7 @@ class BinMapper(_GridMapper):
         for tod in self.tods:
             if tod.dets.n == 0:
                 continue
-            signal, weight, az, el, transform, dx, dy, stokes_w, d_chan = self._tod_inputs(tod, ctx)
-            bin_map(ctx, sky, signal, weight, az, el, transform, dx, dy, stokes_w, d_chan, msum, mwgt)
+            bin_map(ctx, sky, self._tod_inputs(tod, ctx), msum, mwgt)
             torch.cuda.current_stream(dev).synchronize()
         data = (msum / mwgt).cpu().numpy()  # 0/0 = nan where nothing was observed, as numpy gives the reference
         self.products = {"data": data, "weight": mwgt.cpu().numpy(), "sum": msum.cpu().numpy()}
@@ -234,45 +265,70 @@ class _GlsMapper(_GridMapper):
             return torch.where(var > 0, 1.0 / var, torch.zeros_like(var)).contiguous()
         return torch.as_tensor(self.noise_weights).to(self.device)
 
-    def _noise_products(self):
-        return [{k: v.cpu().numpy() for k, v in fit.items() if k in ("white", "knee", "alpha", "sigma")} for fit in self.noise_fits]
-
-    def _normal_inputs(self, ctx, sky, keep):
-        """rhs = P^T W d and the blocks of P^T W P over the TODs; per kept TOD ``(signal, wargs, point, refs)``: the weight
-        and pointing arguments of the operators and the tensors behind them (``keep``: "none", "op" -- without the
-        signal -- or "all")."""
+    def _assemble(self, ctx, sky, records=True):
+        """rhs, the binning's scratch weight plane and the blocks of P^T W P over the TODs, and per TOD with detectors (if
+        ``records``) its record: ``inputs`` (the ``TodInputs``), ``shape`` (D, T), the operators' arguments ``point`` and
+        ``wargs`` (the sample weight, its stride, ``det_w``), and what ``_tod_weights`` sets."""
         dev = self.device
         S, Cn = len(self.stokes), len(self.nu)
         shape = (S, Cn, self.n_eta, self.n_xi)
         rhs = torch.zeros(shape, dtype=torch.float64, device=dev)
         scratch = torch.zeros_like(rhs)  # (the binning's |P| weight: not used here)
         blocks = torch.zeros((S * (S + 1) // 2, Cn, self.n_eta, self.n_xi), dtype=torch.float64, device=dev)
-        kept = []
+        recs = []
         self.noise_fits = []
         for tod in self.tods:
             if tod.dets.n == 0:
                 continue
             # a TOD in K_RJ is calibrated per detector to a unit response to I (TOD.to divides by the Mueller [0, 0]
             # element): its pointing matrix carries the Mueller row over that element; in pW the row itself
-            signal, weight, az, el, transform, dx, dy, stokes_w, d_chan = self._tod_inputs(tod, ctx, unit_i_response=self.units == "K_RJ")
-            fit = None
-            if self._needs_fit():
-                fit = self._fit_noise(ctx, signal, tod)
-                self.noise_fits.append(fit)
-            det_w = self._det_weight(signal, fit)
-            D, T = signal.shape
-            # b = P^T W d: the binning's sum, the per-detector weight folded into the sample weight
-            w_bin = weight
-            if det_w is not None:
-                w_bin = (det_w[:, None] * (1.0 if weight is None else weight.double())).float().expand(D, T).contiguous()
-            bin_map(ctx, sky, signal, w_bin, az, el, transform, dx, dy, stokes_w, d_chan, rhs, scratch)
-            point = (ptr(az), ptr(el), T, ptr(transform), ptr(dx), ptr(dy), ptr(stokes_w), ptr(d_chan), D)
-            wargs = (ptr(weight), 0 if weight is None else weight.stride(0), ptr(det_w))
-            ctx.call("mrx_bin_map_blocks", C.byref(sky), *wargs, *point, ptr(blocks))
-            if keep != "none":
-                kept.append((signal if keep == "all" else signal.shape, wargs, point,
-                             (weight, det_w, az, el, transform, dx, dy, stokes_w, d_chan)))
-        return rhs, blocks, kept
+            inp = self._tod_inputs(tod, ctx, unit_i_response=self.units == "K_RJ")
+            rec = SimpleNamespace(inputs=inp, shape=inp.shape, point=inp.point, fit=None, det_w=None)
+            self._tod_weights(ctx, sky, tod, rec, rhs, scratch)
+            if rec.fit is not None:
+                self.noise_fits.append(rec.fit)
+            rec.wargs = (ptr(inp.weight), 0 if inp.weight is None else inp.weight.stride(0), ptr(rec.det_w))
+            ctx.call("mrx_bin_map_blocks", C.byref(sky), *rec.wargs, *rec.point, ptr(blocks))
+            if records:
+                recs.append(rec)
+        return rhs, scratch, blocks, recs
+
+    def _tod_weights(self, ctx, sky, tod, rec, rhs, scratch):
+        """``_assemble``'s step that depends on the noise model: the TOD's detector weight ``rec.det_w`` (with ``rec.fit``,
+        the noise law fitted for it, if any) and its share of rhs.  Here W of ``noise_weights`` and P^T W d."""
+        signal, weight = rec.inputs.signal, rec.inputs.weight
+        if self._needs_fit():
+            rec.fit = self._fit_noise(ctx, signal, tod)
+        rec.det_w = self._det_weight(signal, rec.fit)
+        # b = P^T W d: the binning's sum, the per-detector weight folded into the sample weight
+        w_bin = weight
+        if rec.det_w is not None:
+            w_bin = (rec.det_w[:, None] * (1.0 if weight is None else weight.double())).float().expand(rec.shape).contiguous()
+        bin_map(ctx, sky, rec.inputs._replace(weight=w_bin), rhs, scratch)
+
+    def _solve(self, ctx, blocks, rhs, normal=None):
+        """(x, mask, |r| / |b| per iteration, converged): x = H^-1 rhs per pixel, NaN where the block is not solved (mask
+        False); with ``normal`` (v -> P^T N^-1 P v) conjugate gradients on the solved pixels, preconditioned by the block
+        diagonal, from the block solve."""
+        x, mask = self._block_solve(ctx, blocks, rhs, True)
+        residuals, converged = [], True
+        if normal is not None:
+            on_solved = lambda v: torch.where(mask, v, torch.zeros_like(v))  # noqa: E731
+            precond = lambda r: self._block_solve(ctx, blocks, r, False)[0]  # noqa: E731
+            x, residuals, converged = self._cg(lambda v: on_solved(normal(v)), precond, on_solved(rhs))
+        return torch.where(mask, x, torch.full_like(x, float("nan"))), mask, residuals, converged
+
+    def _finish(self, x, blocks, rhs, residuals, converged, **extra):
+        """The products every GLS mapper gives (and ``extra``), on the host, and the map."""
+        torch.cuda.current_stream(self.device).synchronize()
+        data = x.cpu().numpy()
+        self.products = {"data": data, "weight": blocks[:1].cpu().numpy(),  # H[0, 0]: [1, C, eta, xi]
+                         "blocks": blocks.cpu().numpy(), "rhs": rhs.cpu().numpy(), "residuals": np.asarray(residuals, float),
+                         "n_iter": max(len(residuals) - 1, 0), "converged": bool(converged), **extra}
+        if self.noise_fits:
+            self.products["noise"] = [{k: v.cpu().numpy() for k, v in fit.items() if k in ("white", "knee", "alpha", "sigma")}
+                                      for fit in self.noise_fits]
+        return self._projection_map(data, self.products["weight"])
 
     def _block_solve(self, ctx, blocks, r, nan_invalid):
         """z = H^-1 r per pixel and channel; the mask [S, C, eta, xi] (bool, one plane repeated) of the solved blocks."""
@@ -283,12 +339,12 @@ class _GlsMapper(_GridMapper):
                  ptr(z), ptr(mask))
         return z, mask.bool().unsqueeze(0).expand(r.shape)
 
-    def _work(self, ctx, sky, shapes):
-        """The routed operators' work buffer for TODs of these [D, T] shapes (None: the atomic form)."""
+    def _work(self, ctx, sky, recs):
+        """The routed operators' work buffer for the TODs of these records, by their [D, T] shapes (None: the atomic form)."""
         need = 0
-        for shape in shapes:
+        for rec in recs:
             lo, full = C.c_size_t(), C.c_size_t()
-            if ctx.lib.mrx_map_normal_work_bytes(C.byref(sky), shape[0], shape[1], C.byref(lo), C.byref(full)) == 0:
+            if ctx.lib.mrx_map_normal_work_bytes(C.byref(sky), *rec.shape, C.byref(lo), C.byref(full)) == 0:
                 need = max(need, _work_bytes(lo.value, full.value, self.device))
         return torch.empty(need, dtype=torch.uint8, device=self.device) if need else None
 
@@ -469,146 +525,113 @@ class MaximumLikelihoodMapper(_GlsMapper):
         return super()._needs_fit() or (isinstance(self.noise_model, str) and self.noise_model == "fit")
 
     def run(self):
-        dev = self.device
-        ctx = Context(dev.index or 0)
-        ctx.set_stream(torch.cuda.current_stream(dev))
+        ctx = self._context()
         sky = self._sky()
         if self.noise_model is not None:
             return self._run_filtered(ctx, sky)
         # per TOD (bilinear): the normal operator's arguments
-        rhs, blocks, ops = self._normal_inputs(ctx, sky, "op" if self.bilinear else "none")
-        solve = lambda r, nan: self._block_solve(ctx, blocks, r, nan)  # noqa: E731
-        x, mask = solve(rhs, True)
-        residuals, converged = [], True
-        if self.bilinear and ops:
-            x, residuals, converged = self._pcg(ctx, sky, ops, rhs, mask, solve)
-        x = torch.where(mask, x, torch.full_like(x, float("nan")))
-        torch.cuda.current_stream(dev).synchronize()
-        data = x.cpu().numpy()
-        self.products = {"data": data, "weight": blocks[:1].cpu().numpy(),  # H[0, 0]: [1, C, eta, xi]
-                         "blocks": blocks.cpu().numpy(), "rhs": rhs.cpu().numpy(), "residuals": np.asarray(residuals, float),
-                         "n_iter": max(len(residuals) - 1, 0), "converged": bool(converged)}
-        if self.noise_fits:
-            self.products["noise"] = self._noise_products()
-        return self._projection_map(data, self.products["weight"])
+        rhs, _, blocks, ops = self._assemble(ctx, sky, records=self.bilinear)
+        normal = None
+        if ops:
+            work = self._work(ctx, sky, ops)
 
-    def _pcg(self, ctx, sky, ops, rhs, mask, solve):
-        """Conjugate gradients on the solved pixels, preconditioned by the block diagonal, from the block solve."""
-        work = self._work(ctx, sky, [shape for shape, *_ in ops])
+            def normal(v):  # P^T W P v
+                y = torch.zeros_like(v)
+                for op in ops:
+                    ctx.call("mrx_map_normal_apply", C.byref(sky), ptr(v), *op.wargs, *op.point, ptr(y), ptr(work),
+                             0 if work is None else work.numel())
+                return y
 
-        def normal(v):
-            y = torch.zeros_like(v)
-            for _, wargs, point, _keep in ops:
-                ctx.call("mrx_map_normal_apply", C.byref(sky), ptr(v), *wargs, *point, ptr(y), ptr(work), 0 if work is None else work.numel())
-            return torch.where(mask, y, torch.zeros_like(y))
+        x, _, residuals, converged = self._solve(ctx, blocks, rhs, normal)
+        return self._finish(x, blocks, rhs, residuals, converged)
 
-        precond = lambda r: solve(r, False)[0]  # noqa: E731
-        return self._cg(normal, precond, torch.where(mask, rhs, torch.zeros_like(rhs)))
+    def _tod_weights(self, ctx, sky, tod, rec, rhs, scratch):
+        """Without ``noise_model`` the white step, and the signal let go.  With it N^-1: ``rec.K``, ``rec.lag``, ``rec.sqrt_w``
+        (the window's root), the mode model ``rec.modes`` (``rec.mode_product``: what the products report of it) and
+        det_w = k_d[0]; b = P^T N^-1 d follows in ``_run_filtered``, through the buffers the TODs share."""
+        if self.noise_model is None:
+            super()._tod_weights(ctx, sky, tod, rec, rhs, scratch)
+            rec.inputs = rec.inputs._replace(signal=None)
+            return
+        dev = self.device
+        signal, weight = rec.inputs.signal, rec.inputs.weight
+        D, T = rec.shape
+        U = mode_law = None
+        dropped = np.zeros(0, np.int64)
+        if self._needs_fit() and self.noise_modes:
+            fitted = noise_modes.fit(ctx, signal, self.noise_modes, lambda rows: self._fit_noise(ctx, rows, tod))
+            rec.fit, U, mode_law, dropped = fitted["law"], fitted["modes"], fitted["mode_law"], fitted["dropped"]
+        elif self._needs_fit():
+            rec.fit = self._fit_noise(ctx, signal, tod)
+        elif self.mode_model is not None:
+            U = torch.as_tensor(self.mode_model[0]).to(dev)
+            mode_law = self.mode_model[1]
+        law = rec.fit or self.noise_model  # the fitted law, else the given one
+        K = self._filter_K(tod)
+        lag = noise_filter.lags(law["white"], law["knee"], law["alpha"], self._fs(tod), K, device=dev)
+        if lag.shape[0] == 1:
+            lag = lag.expand(D, -1)
+        lag = lag.contiguous()
+        sqrt_w = None
+        if weight is not None:  # the pre-processing's window: one row shared by every detector, as a rule
+            sqrt_w = weight[0].sqrt().contiguous() if bool((weight == weight[:1]).all()) else weight.sqrt()
+        model = rec.mode_product = None
+        if U is not None:
+            if sqrt_w is not None and sqrt_w.dim() == 2:
+                raise ValueError("noise modes need one pre-processing weight row shared by every detector; this TOD's differ by row")
+            if U.shape[1]:
+                beta = noise_modes.mode_lags(mode_law, self._fs(tod), K, device=dev)
+                if beta.shape[0] == 1:
+                    beta = beta.expand(U.shape[1], -1)
+                model = noise_modes.ModeModel(U, beta.contiguous(), lag, sqrt_w, T, noise_modes.inner_tol(self.tol))
+            rec.mode_product = {"modes": U, "mode_law": mode_law, "dropped": dropped, "model": model}
+        rec.K, rec.lag, rec.sqrt_w, rec.modes = K, lag, sqrt_w, model
+        rec.det_w = lag[:, 0].contiguous()
 
     def _run_filtered(self, ctx, sky):
         """The GLS map under the stationary noise model: b = P^T N^-1 d, then conjugate gradients on the solved pixels with
         the operator project -> filter (in place in one float32 TOD, sized for the largest) -> routed binning."""
         dev = self.device
-        S, Cn = len(self.stokes), len(self.nu)
-        shape = (S, Cn, self.n_eta, self.n_xi)
-        rhs = torch.zeros(shape, dtype=torch.float64, device=dev)
-        wgt = torch.zeros_like(rhs)  # (the binning's |P| weight: not used here)
-        blocks = torch.zeros((S * (S + 1) // 2, Cn, self.n_eta, self.n_xi), dtype=torch.float64, device=dev)
-        ops, self.noise_fits = [], []
-        mode_products = []
-        for tod in self.tods:
-            if tod.dets.n == 0:
-                continue
-            signal, weight, az, el, transform, dx, dy, stokes_w, d_chan = self._tod_inputs(tod, ctx, unit_i_response=self.units == "K_RJ")
-            D, T = signal.shape
-            U = mode_law = None
-            dropped = np.zeros(0, np.int64)
-            if self._needs_fit() and self.noise_modes:
-                fitted = noise_modes.fit(ctx, signal, self.noise_modes, lambda rows: self._fit_noise(ctx, rows, tod))  # noqa: B023
-                law, U, mode_law, dropped = fitted["law"], fitted["modes"], fitted["mode_law"], fitted["dropped"]
-                self.noise_fits.append(law)
-            elif self._needs_fit():
-                law = self._fit_noise(ctx, signal, tod)
-                self.noise_fits.append(law)
-            else:
-                law = self.noise_model
-                if self.mode_model is not None:
-                    U = torch.as_tensor(self.mode_model[0]).to(dev)
-                    mode_law = self.mode_model[1]
-            K = self._filter_K(tod)
-            lag = noise_filter.lags(law["white"], law["knee"], law["alpha"], self._fs(tod), K, device=dev)
-            if lag.shape[0] == 1:
-                lag = lag.expand(D, -1)
-            lag = lag.contiguous()
-            sqrt_w = None
-            if weight is not None:  # the pre-processing's window: one row shared by every detector, as a rule
-                sqrt_w = weight[0].sqrt().contiguous() if bool((weight == weight[:1]).all()) else weight.sqrt()
-            model = None
-            if U is not None:
-                if sqrt_w is not None and sqrt_w.dim() == 2:
-                    raise ValueError("noise modes need one pre-processing weight row shared by every detector; this TOD's differ by row")
-                if U.shape[1]:
-                    beta = noise_modes.mode_lags(mode_law, self._fs(tod), K, device=dev)
-                    if beta.shape[0] == 1:
-                        beta = beta.expand(U.shape[1], -1)
-                    model = noise_modes.ModeModel(U, beta.contiguous(), lag, sqrt_w, T, noise_modes.inner_tol(self.tol))
-                mode_products.append({"modes": U, "mode_law": mode_law, "dropped": dropped, "model": model})
-            det_w = lag[:, 0].contiguous()
-            point = (ptr(az), ptr(el), T, ptr(transform), ptr(dx), ptr(dy), ptr(stokes_w), ptr(d_chan), D)
-            ctx.call("mrx_bin_map_blocks", C.byref(sky), ptr(weight), 0 if weight is None else weight.stride(0), ptr(det_w), *point,
-                     ptr(blocks))
-            ops.append({"D": D, "T": T, "K": K, "lag": lag, "sqrt_w": sqrt_w, "point": point, "modes": model,
-                        "refs": (signal, weight, az, el, transform, dx, dy, stokes_w, d_chan)})
-        work = self._bin_work(ctx, sky, [(op["D"], op["T"]) for op in ops])
-        tod_buf = torch.empty(max([op["D"] * op["T"] for op in ops], default=0), dtype=torch.float32, device=dev)
+        rhs, wgt, blocks, ops = self._assemble(ctx, sky)
+        work = self._work(ctx, sky, ops)
+        size = lambda op: op.shape[0] * op.shape[1]  # noqa: E731
+        tod_buf = torch.empty(max([size(op) for op in ops], default=0), dtype=torch.float32, device=dev)
         # the modes' second TOD, z = A' x of step 1 (noise_modes.apply)
-        mode_buf = torch.empty(max([op["D"] * op["T"] for op in ops if op["modes"] is not None], default=0), dtype=torch.float32, device=dev)
+        mode_buf = torch.empty(max([size(op) for op in ops if op.modes is not None], default=0), dtype=torch.float32, device=dev)
 
         def inv_noise(x, buf, op):  # buf = N^-1 x (buf may be x)
-            if op["modes"] is None:
-                noise_filter.apply(ctx, x, op["lag"], op["sqrt_w"], out=buf)
+            if op.modes is None:
+                noise_filter.apply(ctx, x, op.lag, op.sqrt_w, out=buf)
             else:
-                scratch = mode_buf[: op["D"] * op["T"]].view(op["D"], op["T"])
-                noise_modes.apply(ctx, x, op["lag"], op["sqrt_w"], op["modes"], out=buf, scratch=scratch)
+                noise_modes.apply(ctx, x, op.lag, op.sqrt_w, op.modes, out=buf, scratch=mode_buf[: size(op)].view(op.shape))
 
         def bin_into(y, buf, op):  # y += P^T buf
-            args = (C.byref(sky), ptr(buf), op["T"], None, 0, *op["point"][:-1], op["D"], ptr(y), ptr(wgt))
+            args = (C.byref(sky), ptr(buf), op.shape[1], None, 0, *op.point, ptr(y), ptr(wgt))
             if work is None:
                 ctx.call("mrx_bin_map", *args)
             else:
                 ctx.call("mrx_bin_map_bucketed", *args, ptr(work), work.numel())
 
         for op in ops:  # b = P^T N^-1 d
-            buf = tod_buf[: op["D"] * op["T"]].view(op["D"], op["T"])
-            inv_noise(op["refs"][0], buf, op)
+            buf = tod_buf[: size(op)].view(op.shape)
+            inv_noise(op.inputs.signal, buf, op)
             bin_into(rhs, buf, op)
-            op["refs"] = op["refs"][1:]  # the signal is not needed any more
-        solve = lambda r, nan: self._block_solve(ctx, blocks, r, nan)  # noqa: E731
-        x, mask = solve(rhs, True)
-        residuals, converged = [], True
-        if ops:
-            def normal(v):  # P^T N^-1 P v on the solved pixels
-                y = torch.zeros_like(v)
-                for op in ops:
-                    buf = tod_buf[: op["D"] * op["T"]].view(op["D"], op["T"])
-                    ctx.call("mrx_map_project", C.byref(sky), ptr(v), *op["point"], 1.0, 0.0, ptr(buf), op["T"])
-                    inv_noise(buf, buf, op)
-                    bin_into(y, buf, op)
-                return torch.where(mask, y, torch.zeros_like(y))
+            op.inputs = op.inputs._replace(signal=None)  # the signal is not needed any more
 
-            precond = lambda r: solve(r, False)[0]  # noqa: E731
-            x, residuals, converged = self._cg(normal, precond, torch.where(mask, rhs, torch.zeros_like(rhs)))
-        x = torch.where(mask, x, torch.full_like(x, float("nan")))
-        torch.cuda.current_stream(dev).synchronize()
-        data = x.cpu().numpy()
-        self.products = {"data": data, "weight": blocks[:1].cpu().numpy(), "blocks": blocks.cpu().numpy(), "rhs": rhs.cpu().numpy(),
-                         "residuals": np.asarray(residuals, float), "n_iter": max(len(residuals) - 1, 0), "converged": bool(converged),
-                         "noise_filter": [{"K": op["K"], "lags": op["lag"].cpu().numpy()} for op in ops]}
-        if self.noise_fits:
-            self.products["noise"] = self._noise_products()
-        if mode_products:
-            self.products["noise_modes"] = [self._mode_product(p) for p in mode_products]
-        return self._projection_map(data, self.products["weight"])
+        def normal(v):  # P^T N^-1 P v
+            y = torch.zeros_like(v)
+            for op in ops:
+                buf = tod_buf[: size(op)].view(op.shape)
+                ctx.call("mrx_map_project", C.byref(sky), ptr(v), *op.point, 1.0, 0.0, ptr(buf), op.shape[1])
+                inv_noise(buf, buf, op)
+                bin_into(y, buf, op)
+            return y
+
+        x, _, residuals, converged = self._solve(ctx, blocks, rhs, normal if ops else None)
+        extra = {"noise_filter": [{"K": op.K, "lags": op.lag.cpu().numpy()} for op in ops]}
+        if any(op.mode_product for op in ops):
+            extra["noise_modes"] = [self._mode_product(op.mode_product) for op in ops if op.mode_product]
+        return self._finish(x, blocks, rhs, residuals, converged, **extra)
 
     @staticmethod
     def _mode_product(p):
@@ -616,16 +639,6 @@ class MaximumLikelihoodMapper(_GlsMapper):
         its = p["model"].inner.iterations if p["model"] is not None else []
         return {"modes": as_np(p["modes"]), "mode_law": {k: as_np(v) for k, v in p["mode_law"].items()}, "dropped": as_np(p["dropped"]),
                 "inner_iter_max": max(its, default=0), "inner_iter_total": int(sum(its))}
-
-    def _bin_work(self, ctx, sky, shapes):
-        """The routed binning's work buffer for TODs of these [D, T] shapes (None: the atomic form, mrx_bin_map)."""
-        need = 0
-        for D, T in shapes:
-            lo, full = C.c_size_t(), C.c_size_t()
-            if ctx.lib.mrx_bin_map_work_bytes(C.byref(sky), D, T, C.byref(lo), C.byref(full)) != 0:
-                return None
-            need = max(need, _work_bytes(lo.value, full.value, self.device))
-        return torch.empty(need, dtype=torch.uint8, device=self.device) if need else None
 
 
 class DestripingMapper(_GlsMapper):
@@ -739,32 +752,29 @@ class DestripingMapper(_GlsMapper):
 
     def run(self):
         dev = self.device
-        ctx = Context(dev.index or 0)
-        ctx.set_stream(torch.cuda.current_stream(dev))
+        ctx = self._context()
         sky = self._sky()
-        rhs, blocks, tods = self._normal_inputs(ctx, sky, "all")
+        rhs, _, blocks, tods = self._assemble(ctx, sky)
         solve = lambda r: self._block_solve(ctx, blocks, r, False)  # noqa: E731  (0 in unsolved pixels)
         m0, mask = solve(rhs)
         mu = mask[0].to(torch.uint8).contiguous()  # [C, eta, xi]
         # the offsets of all TODs in one vector, [D, nb] views per TOD
-        sizes = [(sig.shape[0], -(-sig.shape[1] // L)) for (sig, *_), L in zip(tods, self.baseline_samples)]
+        sizes = [(tod.shape[0], -(-tod.shape[1] // L)) for tod, L in zip(tods, self.baseline_samples)]
         offs = np.cumsum([0] + [D * nb for D, nb in sizes])
         views = lambda v: [v[offs[i]:offs[i + 1]].view(sizes[i]) for i in range(len(sizes))]  # noqa: E731
         n = int(offs[-1])
         b, hits = torch.zeros(n, dtype=torch.float64, device=dev), torch.zeros(n, dtype=torch.float64, device=dev)
-        work = self._work(ctx, sky, [sig.shape for sig, *_ in tods])
+        work = self._work(ctx, sky, tods)
 
-        def reduce(tod, x, y, h, signal=None):
-            (_, wargs, point, _refs), L = tods[tod], self.baseline_samples[tod]
-            ctx.call("mrx_baseline_reduce", C.byref(sky), ptr(signal), 0 if signal is None else signal.stride(0), ptr(x), 1.0, *wargs,
-                     ptr(mu), L, *point, ptr(y), ptr(h))
+        def reduce(i, x, y, h, signal=None):
+            ctx.call("mrx_baseline_reduce", C.byref(sky), ptr(signal), 0 if signal is None else signal.stride(0), ptr(x), 1.0,
+                     *tods[i].wargs, ptr(mu), self.baseline_samples[i], *tods[i].point, ptr(y), ptr(h))
 
         def bin_offsets(a):  # P^T W F a
             y = torch.zeros_like(rhs)
             for i, ai in enumerate(views(a)):
-                _, wargs, point, _refs = tods[i]
-                ctx.call("mrx_bin_map_baselines", C.byref(sky), ptr(ai), self.baseline_samples[i], *wargs, *point, ptr(y), ptr(work),
-                         0 if work is None else work.numel())
+                ctx.call("mrx_bin_map_baselines", C.byref(sky), ptr(ai), self.baseline_samples[i], *tods[i].wargs, *tods[i].point, ptr(y),
+                         ptr(work), 0 if work is None else work.numel())
             return y
 
         prior = None
@@ -782,7 +792,7 @@ class DestripingMapper(_GlsMapper):
             return out
 
         for i, (bi, hi) in enumerate(zip(views(b), views(hits))):
-            reduce(i, m0, bi, hi, signal=tods[i][0])  # F^T W mu (d - P m0) and the hits
+            reduce(i, m0, bi, hi, signal=tods[i].inputs.signal)  # F^T W mu (d - P m0) and the hits
         if self.baseline_prior is None:
             inv_hits = torch.where(hits > 0, 1.0 / hits, torch.zeros_like(hits))
             precond = lambda r: inv_hits * r  # noqa: E731
@@ -793,16 +803,10 @@ class DestripingMapper(_GlsMapper):
         self._fix_gauge(a, hits, views, tods)
         x = m0 - solve(bin_offsets(a))[0]
         x = torch.where(mask, x, torch.full_like(x, float("nan")))
-        torch.cuda.current_stream(dev).synchronize()
-        data = x.cpu().numpy()
-        self.products = {"data": data, "weight": blocks[:1].cpu().numpy(), "blocks": blocks.cpu().numpy(), "rhs": rhs.cpu().numpy(),
-                         "baselines": [v.cpu().numpy() for v in views(a)], "hits": [v.cpu().numpy() for v in views(hits)],
-                         "residuals": np.asarray(residuals, float), "n_iter": max(len(residuals) - 1, 0), "converged": bool(converged)}
+        extra = {"baselines": [v.cpu().numpy() for v in views(a)], "hits": [v.cpu().numpy() for v in views(hits)]}
         if prior is not None:
-            self.products["prior"] = [{"K": p["w"].numel(), "Kp": p["Kp"], "weights": p["w"].cpu().numpy()} for p in prior]
-        if self.noise_fits:
-            self.products["noise"] = self._noise_products()
-        return self._projection_map(data, self.products["weight"])
+            extra["prior"] = [{"K": p["w"].numel(), "Kp": p["Kp"], "weights": p["w"].cpu().numpy()} for p in prior]
+        return self._finish(x, blocks, rhs, residuals, converged, **extra)
 
     def _resolved_prior(self):
         """baseline_prior with knee "fit" replaced by the fitted knees (a failed fit takes the median of the others) and
@@ -825,9 +829,9 @@ class DestripingMapper(_GlsMapper):
     def _prior_operators(self, ctx, sizes, hits, tods, cfg):
         """Per TOD: the prior's weights and scales on the device, and the preconditioner's band factor (or its diagonal)."""
         out = []
-        for i, ((D, nb), hi, (_, _, _, refs)) in enumerate(zip(sizes, hits, tods)):
+        for i, ((D, nb), hi, tod) in enumerate(zip(sizes, hits, tods)):
             w = destripe_prior.prior_weights(self.sample_rates[i], self.baseline_samples[i], cfg["alpha"], nb)
-            det_w = refs[1]  # the per-detector weight W_d (None: "uniform")
+            det_w = tod.det_w  # the per-detector weight W_d (None: "uniform")
             W = torch.ones(D, dtype=torch.float64, device=self.device) if det_w is None else det_w.double()
             scale = (W / torch.as_tensor(cfg["knee"][i] ** cfg["alpha"]).to(self.device)).contiguous()
             d_w = torch.as_tensor(w).to(self.device)
@@ -864,8 +868,8 @@ class DestripingMapper(_GlsMapper):
         G = torch.zeros((Cn, S, S), dtype=torch.float64, device=a.device)
         num = torch.zeros((Cn, S), dtype=torch.float64, device=a.device)
         per_tod = []
-        for ai, hi, (_, _, _, refs) in zip(views(a), views(hits), tods):
-            sw, d_chan = refs[7], refs[8].long()
+        for ai, hi, tod in zip(views(a), views(hits), tods):
+            sw, d_chan = tod.inputs.stokes_w, tod.inputs.channel.long()
             hs, ha = hi.sum(dim=1), (hi * ai).sum(dim=1)
             G.index_add_(0, d_chan, sw[:, :, None] * sw[:, None, :] * hs[:, None, None])
             num.index_add_(0, d_chan, sw * ha[:, None])
