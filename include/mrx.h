@@ -895,6 +895,26 @@ int mrx_sosfilt(mrx_ctx* ctx, const double* sos, int n_sections, const double* d
                 const float* d_in, size_t ld_in, int D, int T, int remove_slope, float* d_out,
                 size_t ld_out, double* d_work);
 
+/* The transpose of mrx_tod_detrend_window, x = S^T diag(w) y in place on a [D][ld] float32 TOD: the adjoint of
+ * remove_slope (processing.py:99-105) after that of window (processing.py:139-146), for the filter-aware map's
+ * F^T.  u = w y in float64, stored as float32; S^T u = u - e_0 sum_t (1 - t/(T-1)) u_t
+ * - e_{T-1} sum_t t/(T-1) u_t, the two sums per row in float64 by a fixed tree (no atomics: bit-identical run to
+ * run) and the two end samples rounded once.  Either part is optional.
+ *  d_window [T] float64 window or NULL */
+int mrx_tod_detrend_window_transpose(mrx_ctx* ctx, float* d_data, size_t ld, int D, int T, int remove_slope,
+                                     const double* d_window);
+
+/* The transpose of mrx_sosfilt, out = [S^T] H^T in: H^T = J H J with J the time reversal (H of
+ * utils/signal/filters.py:46-69 is causal with zero initial state), then, with remove_slope, the adjoint S^T of the
+ * slope removal mrx_sosfilt does first (processing.py:151).  mrx_sosfilt's arguments, scratch size, time-parallel scheme
+ * (the chunks stay aligned from sample 0, each is walked backwards and they are chained from the last to the first
+ * with the same chunk matrix) and refusals.  The two row sums of S^T are taken as <H a, in> and <H b, in>, a and b the
+ * line's weights: float64 trees over the input, bit-identical run to run; H a and H b are filtered serially on the
+ * host once per (cascade, T) and kept on the device by the context. */
+int mrx_sosfilt_transpose(mrx_ctx* ctx, const double* sos, int n_sections, const double* d_chunk_matrix,
+                          const float* d_in, size_t ld_in, int D, int T, int remove_slope, float* d_out,
+                          size_t ld_out, double* d_work);
+
 /* Test hook for the in-LDS inverse FFT both generators are built on: `rows` independent rows
  * of n << interleave_log2 complex float32 values, each holding 2^interleave_log2 interleaved
  * sequences of length n (a power of two >= 4; at most 8192 values per row); unnormalised

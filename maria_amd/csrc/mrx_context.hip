@@ -127,6 +127,8 @@ int mrx_destroy(mrx_ctx* ctx) {
     if (slot.d_taps) (void)hipFree(slot.d_taps);
   for (auto& slot : ctx->fresp)
     if (slot.d_resp) (void)hipFree(slot.d_resp);
+  for (auto& slot : ctx->slope_resp)
+    if (slot.d_resp) (void)hipFree(slot.d_resp);
   if (ctx->d_reduce) (void)hipFree(ctx->d_reduce);
   if (ctx->d_synth_ctl) (void)hipFree(ctx->d_synth_ctl);
   if (ctx->d_bin_order) (void)hipFree(ctx->d_bin_order);

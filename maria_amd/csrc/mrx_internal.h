@@ -52,6 +52,15 @@ struct mrx_ctx {
     unsigned long long pinned = 0;
   } fresp[kFRespSlots];
   int fresp_next = 0;
+  // mrx_sosfilt_transpose with remove_slope (mrx_tod.hip: get_slope_resp): H a and H b of the line's two weight rows,
+  // 2 * round4(T) doubles per (cascade, T), from a serial float64 loop on the host
+  static constexpr int kSlopeRespSlots = 8;
+  struct SlopeRespSlot {
+    double coef[40] = {0.0};  // b0, b1, b2, a1, a2 of up to 8 sections
+    int n_sections = 0, T = 0;
+    double* d_resp = nullptr;
+  } slope_resp[kSlopeRespSlots];
+  int slope_resp_next = 0;
   int options[MRX_OPT_COUNT] = {0};
   // map sampling: the map's row pairs interleaved (mrx_map.hip: map_pairs_kernel), rebuilt by every call from the caller's
   // planes; the event orders the rebuild behind the sampler that last read the copy, whatever stream the context has since

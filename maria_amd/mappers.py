@@ -123,19 +123,24 @@ class _GridMapper:
         ctx.set_stream(torch.cuda.current_stream(self.device))
         return ctx
 
-    def _tod_inputs(self, tod, ctx, unit_i_response=False):
+    def _tod_inputs(self, tod, ctx, unit_i_response=False, with_operator=False):
         """The ``TodInputs`` (signal, weight, az, el, transform, dx, dy, stokes_w, channel) of one TOD; weight None for ones.
-        ``unit_i_response``: the Stokes weights over the detector's I weight (its Mueller [0, 0])."""
+        ``unit_i_response``: the Stokes weights over the detector's I weight (its Mueller [0, 0]).  ``with_operator``:
+        ``(TodInputs, op)``, op the pre-processing as a ``tod_processing.PreprocessOperator`` (no steps: the identity)."""
         from .sim import sky_transform_stack
 
         dev = self.device
         dets, coords = tod.dets, tod.coords
         f32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float32)).to(dev)  # noqa: E731
-        weight = None
-        if self.tod_preprocessing:
-            from .tod_processing import process_tod
+        weight = operator = None
+        if self.tod_preprocessing or with_operator:
+            from .tod_processing import preprocess_operator, process_tod
 
-            done = process_tod(tod, config={k: dict(v) for k, v in self.tod_preprocessing.items()}, ctx=ctx, device=dev)
+            config = {k: dict(v) for k, v in self.tod_preprocessing.items()}
+            if with_operator:
+                done, operator = preprocess_operator(tod, config=config, ctx=ctx, device=dev)
+            else:
+                done = process_tod(tod, config=config, ctx=ctx, device=dev)
             signal = done.data["total"]
             if not np.all(done.weight == 1.0):  # the window is the processed TOD's weight (processing.py:193)
                 weight = torch.as_tensor(np.ascontiguousarray(done.weight, np.float32)).to(dev).expand(signal.shape[0], -1).contiguous()
@@ -160,7 +165,8 @@ class _GridMapper:
         d_chan = torch.as_tensor(chan).to(dev)
         az, el = f32(coords._baz), f32(coords._bel)
         dx, dy = f32(coords.offsets[:, 0]), f32(coords.offsets[:, 1])
-        return TodInputs(signal, weight, az, el, transform, dx, dy, stokes_w, d_chan)
+        inputs = TodInputs(signal, weight, az, el, transform, dx, dy, stokes_w, d_chan)
+        return (inputs, operator) if with_operator else inputs
 
     def _projection_map(self, data, weight):
         out = ProjectionMap.__new__(ProjectionMap)
@@ -207,6 +213,8 @@ class BinMapper(_GridMapper):
 class _GlsMapper(_GridMapper):
     """What the white-noise GLS mappers share: the argument checks, the weights W, b = P^T W d with the block diagonal of
     P^T W P, the block solve and preconditioned conjugate gradients."""
+
+    filter_aware = False  # MaximumLikelihoodMapper's keyword: ``_assemble`` then keeps every TOD's pre-processing operator
 
     def _init_gls(self, stokes, noise_weights, max_iter, tol, rcond, noise_fit=None):
         if not stokes or len(stokes) > 3 or any(s not in "IQU" for s in stokes) or len(set(stokes)) != len(stokes):
@@ -268,7 +276,8 @@ class _GlsMapper(_GridMapper):
     def _assemble(self, ctx, sky, records=True):
         """rhs, the binning's scratch weight plane and the blocks of P^T W P over the TODs, and per TOD with detectors (if
         ``records``) its record: ``inputs`` (the ``TodInputs``), ``shape`` (D, T), the operators' arguments ``point`` and
-        ``wargs`` (the sample weight, its stride, ``det_w``), and what ``_tod_weights`` sets."""
+        ``wargs`` (the sample weight, its stride, ``det_w``), ``pre`` (with ``filter_aware`` the pre-processing operator F,
+        else None) and what ``_tod_weights`` sets."""
         dev = self.device
         S, Cn = len(self.stokes), len(self.nu)
         shape = (S, Cn, self.n_eta, self.n_xi)
@@ -282,8 +291,9 @@ class _GlsMapper(_GridMapper):
                 continue
             # a TOD in K_RJ is calibrated per detector to a unit response to I (TOD.to divides by the Mueller [0, 0]
             # element): its pointing matrix carries the Mueller row over that element; in pW the row itself
-            inp = self._tod_inputs(tod, ctx, unit_i_response=self.units == "K_RJ")
-            rec = SimpleNamespace(inputs=inp, shape=inp.shape, point=inp.point, fit=None, det_w=None)
+            inp = self._tod_inputs(tod, ctx, unit_i_response=self.units == "K_RJ", with_operator=self.filter_aware)
+            inp, pre = inp if self.filter_aware else (inp, None)
+            rec = SimpleNamespace(inputs=inp, shape=inp.shape, point=inp.point, fit=None, det_w=None, pre=pre)
             self._tod_weights(ctx, sky, tod, rec, rhs, scratch)
             if rec.fit is not None:
                 self.noise_fits.append(rec.fit)
@@ -297,14 +307,18 @@ class _GlsMapper(_GridMapper):
         """``_assemble``'s step that depends on the noise model: the TOD's detector weight ``rec.det_w`` (with ``rec.fit``,
         the noise law fitted for it, if any) and its share of rhs.  Here W of ``noise_weights`` and P^T W d."""
         signal, weight = rec.inputs.signal, rec.inputs.weight
-        if self._needs_fit():
-            rec.fit = self._fit_noise(ctx, signal, tod)
-        rec.det_w = self._det_weight(signal, rec.fit)
+        self._white_weight(ctx, tod, rec)
         # b = P^T W d: the binning's sum, the per-detector weight folded into the sample weight
         w_bin = weight
         if rec.det_w is not None:
             w_bin = (rec.det_w[:, None] * (1.0 if weight is None else weight.double())).float().expand(rec.shape).contiguous()
         bin_map(ctx, sky, rec.inputs._replace(weight=w_bin), rhs, scratch)
+
+    def _white_weight(self, ctx, tod, rec):
+        """W of ``noise_weights``: ``rec.det_w`` and, for "fit", ``rec.fit``."""
+        if self._needs_fit():
+            rec.fit = self._fit_noise(ctx, rec.inputs.signal, tod)
+        rec.det_w = self._det_weight(rec.inputs.signal, rec.fit)
 
     def _solve(self, ctx, blocks, rhs, normal=None):
         """(x, mask, |r| / |b| per iteration, converged): x = H^-1 rhs per pixel, NaN where the block is not solved (mask
@@ -410,11 +424,24 @@ class MaximumLikelihoodMapper(_GlsMapper):
     detector laws refitted without them); a dict model gives them as ``"modes"`` (a [D, m] coupling in the TOD's units)
     and ``"mode_law"`` (``{"white", "knee", "alpha"}``, scalars or [m] arrays).  Modes need one pre-processing weight row
     shared by every detector.  ``products["noise_modes"]`` holds per TOD ``modes``, ``mode_law``, ``dropped`` (the
-    fitted modes whose law failed) and the inner solve's iterations (``inner_iter_max``, ``inner_iter_total``)."""
+    fitted modes whose law failed) and the inner solve's iterations (``inner_iter_max``, ``inner_iter_total``).
+
+    ``filter_aware=True`` solves through ``tod_preprocessing`` instead of binning the filtered TOD:
+    m = argmin (F d - F P m)^T W (F d - F P m),  (P^T F^T W F P) m = P^T F^T W F d,  F the linear operator that
+    ``process_tod`` applied to this TOD (``tod_processing.preprocess_operator``; ``remove_modes`` frozen at the modes and
+    row norms the data gave) and W as above.  Conjugate gradients with nearest and bilinear pointing alike (F couples
+    pixels), preconditioned by the blocks of P^T W P, from the block solve.  ``products["filter_aware"]`` is True and
+    ``products["preprocessing"]`` holds per TOD the ``steps`` applied and, for remove_modes, ``modes`` (U [D, m]) and
+    ``row_norms``.  An empty ``tod_preprocessing`` is F = I, the plain map.  Not with ``noise_model`` or ``noise_modes``."""
 
     def __init__(self, tods, center, width=None, height=None, resolution=None, stokes="IQU", nu=None, frame="ra/dec", units="K_RJ",
                  degrees=True, bilinear=False, tod_preprocessing=None, noise_weights="inverse_variance", max_iter=100, tol=1e-6, rcond=1e-3,
-                 device="cuda:0", noise_fit=None, noise_model=None, noise_filter_length=None, noise_modes=None):
+                 device="cuda:0", noise_fit=None, noise_model=None, noise_filter_length=None, noise_modes=None, filter_aware=False):
+        if not isinstance(filter_aware, (bool, np.bool_)):
+            raise ValueError(f"filter_aware {filter_aware!r}: True or False")
+        if filter_aware and (noise_model is not None or noise_modes is not None):
+            raise ValueError("filter_aware cannot be set with noise_model or noise_modes: F^T N^-1 F is not built")
+        self.filter_aware = bool(filter_aware)
         self._init_grid(tods, center, width, height, resolution, stokes, nu, frame, units, degrees, bilinear, tod_preprocessing, device)
         self._init_gls(stokes, noise_weights, max_iter, tol, rcond, noise_fit)
         self._init_noise_model(noise_model, noise_filter_length)
@@ -527,7 +554,7 @@ class MaximumLikelihoodMapper(_GlsMapper):
     def run(self):
         ctx = self._context()
         sky = self._sky()
-        if self.noise_model is not None:
+        if self.noise_model is not None or self.filter_aware:
             return self._run_filtered(ctx, sky)
         # per TOD (bilinear): the normal operator's arguments
         rhs, _, blocks, ops = self._assemble(ctx, sky, records=self.bilinear)
@@ -549,6 +576,10 @@ class MaximumLikelihoodMapper(_GlsMapper):
         """Without ``noise_model`` the white step, and the signal let go.  With it N^-1: ``rec.K``, ``rec.lag``, ``rec.sqrt_w``
         (the window's root), the mode model ``rec.modes`` (``rec.mode_product``: what the products report of it) and
         det_w = k_d[0]; b = P^T N^-1 d follows in ``_run_filtered``, through the buffers the TODs share."""
+        if self.filter_aware:  # W as in the white step; b = P^T F^T W F d follows in ``_run_filtered``
+            self._white_weight(ctx, tod, rec)
+            rec.modes = None
+            return
         if self.noise_model is None:
             super()._tod_weights(ctx, sky, tod, rec, rhs, scratch)
             rec.inputs = rec.inputs._replace(signal=None)
@@ -590,7 +621,9 @@ class MaximumLikelihoodMapper(_GlsMapper):
 
     def _run_filtered(self, ctx, sky):
         """The GLS map under the stationary noise model: b = P^T N^-1 d, then conjugate gradients on the solved pixels with
-        the operator project -> filter (in place in one float32 TOD, sized for the largest) -> routed binning."""
+        the operator project -> filter (in place in one float32 TOD, sized for the largest) -> routed binning.
+        With ``filter_aware`` the same loop with F^T W F in the middle: b = P^T F^T W (F d), F d the pre-processed signal,
+        and project -> F -> W -> F^T -> routed binning."""
         dev = self.device
         rhs, wgt, blocks, ops = self._assemble(ctx, sky)
         work = self._work(ctx, sky, ops)
@@ -599,8 +632,16 @@ class MaximumLikelihoodMapper(_GlsMapper):
         # the modes' second TOD, z = A' x of step 1 (noise_modes.apply)
         mode_buf = torch.empty(max([size(op) for op in ops if op.modes is not None], default=0), dtype=torch.float32, device=dev)
 
-        def inv_noise(x, buf, op):  # buf = N^-1 x (buf may be x)
-            if op.modes is None:
+        def inv_noise(x, buf, op):  # buf = N^-1 x (buf may be x); filter-aware: buf = F^T W x
+            if self.filter_aware:
+                if op.det_w is not None:
+                    torch.mul(x, op.det_w.float()[:, None], out=buf)
+                elif buf is not x:
+                    buf.copy_(x)
+                if op.inputs.weight is not None:
+                    buf.mul_(op.inputs.weight)
+                op.pre.apply_transpose(buf)
+            elif op.modes is None:
                 noise_filter.apply(ctx, x, op.lag, op.sqrt_w, out=buf)
             else:
                 noise_modes.apply(ctx, x, op.lag, op.sqrt_w, op.modes, out=buf, scratch=mode_buf[: size(op)].view(op.shape))
@@ -623,11 +664,15 @@ class MaximumLikelihoodMapper(_GlsMapper):
             for op in ops:
                 buf = tod_buf[: size(op)].view(op.shape)
                 ctx.call("mrx_map_project", C.byref(sky), ptr(v), *op.point, 1.0, 0.0, ptr(buf), op.shape[1])
+                if self.filter_aware:
+                    op.pre.apply(buf)
                 inv_noise(buf, buf, op)
                 bin_into(y, buf, op)
             return y
 
         x, _, residuals, converged = self._solve(ctx, blocks, rhs, normal if ops else None)
+        if self.filter_aware:
+            return self._finish(x, blocks, rhs, residuals, converged, filter_aware=True, preprocessing=[op.pre.product() for op in ops])
         extra = {"noise_filter": [{"K": op.K, "lags": op.lag.cpu().numpy()} for op in ops]}
         if any(op.mode_product for op in ops):
             extra["noise_modes"] = [self._mode_product(op.mode_product) for op in ops if op.mode_product]

@@ -155,6 +155,102 @@ def process_tod(tod, config=None, ctx=None, device="cuda:0", **kwargs):
     host or the device); returns a :class:`ProcessedTOD` whose ``data["total"]`` is a float32
     device tensor.  Operations run in the reference's order: remove_slope, remove_spline,
     window, filter, remove_modes."""
+    return _process(tod, config, ctx, device, kwargs, None)
+
+
+def preprocess_operator(tod, config=None, ctx=None, device="cuda:0", **kwargs):
+    """``process_tod`` and, next to the processed TOD, the linear operator F it applied to this TOD's signal, a
+    :class:`PreprocessOperator`: ``(ProcessedTOD, op)``.  The one data-dependent step, remove_modes, is frozen in
+    ``op`` at the modes and row norms this TOD's data gave."""
+    dev = torch.device(device)
+    ctx = ctx or Context(dev.index or 0)
+    op = PreprocessOperator(ctx, dev)
+    return _process(tod, config, ctx, device, kwargs, op), op
+
+
+class PreprocessOperator:
+    """F of one TOD as an operator on float32 ``[D, T]`` device tensors, in place: ``apply`` runs the recorded steps in
+    ``process_tod``'s order, ``apply_transpose`` their transposes in reverse order.
+
+        remove_slope   S x = x - line through the buffer's own end points;  S^T u = u - e_0 sum (1 - t/(T-1)) u_t
+                       - e_{T-1} sum t/(T-1) u_t                                  (mrx_tod_detrend_window[_transpose])
+        remove_spline  Q = I - B^T (B B^T)^-1 B                                   (float64 GEMMs, as process_tod's)
+        window         diag(w), its own transpose                                 (mrx_tod_detrend_window[_transpose])
+        filter         H S, H = sosfilt; (H S)^T = S^T J H J, J the time reversal (mrx_sosfilt[_transpose])
+        remove_modes   R = I - diag(n) U U^T diag(1/n), R^T = I - diag(1/n) U U^T diag(n), U [D, m] and the row norms n
+                       those of the processed data, frozen                        (float64 GEMMs over blocks of columns)
+    """
+
+    def __init__(self, ctx, device):
+        self.ctx, self.device = ctx, device
+        self.steps = []  # (name, what the step needs on the device), in process_tod's order
+        self.shape = None
+        self._anchors = None
+
+    @property
+    def names(self):
+        return [name for name, _ in self.steps]
+
+    def product(self):
+        """What a mapper reports of F: the step names and, for remove_modes, U and the row norms (numpy)."""
+        out = {"steps": self.names}
+        for name, p in self.steps:
+            if name == "remove_modes":
+                out["modes"], out["row_norms"] = p["U"].cpu().numpy(), p["norms"].cpu().numpy()
+        return out
+
+    def _check(self, buf):
+        if not (isinstance(buf, torch.Tensor) and buf.dtype == torch.float32 and buf.dim() == 2 and buf.is_cuda
+                and tuple(buf.shape) == self.shape and (buf.shape[1] == 1 or buf.stride(1) == 1)):
+            raise ValueError(f"the operator acts on a float32 {self.shape} device tensor with unit column stride")
+        self.ctx.set_stream(torch.cuda.current_stream(buf.device))
+        if self._anchors is None:
+            self._anchors = torch.empty(2 * self.shape[0] + 16, dtype=torch.float64, device=buf.device)
+
+    def apply(self, buf):
+        """buf <- F buf."""
+        self._check(buf)
+        for name, p in self.steps:
+            self._step(name, p, buf, False)
+        return buf
+
+    def apply_transpose(self, buf):
+        """buf <- F^T buf."""
+        self._check(buf)
+        for name, p in reversed(self.steps):
+            self._step(name, p, buf, True)
+        return buf
+
+    def _step(self, name, p, X, transpose):
+        n_det, n_samp = X.shape
+        ctx = self.ctx
+        if name in ("remove_slope", "window") or (name == "filter" and p["plan"] is None):
+            slope, d_w = int(name != "window"), p.get("window")
+            if transpose:
+                ctx.call("mrx_tod_detrend_window_transpose", ptr(X), X.stride(0), n_det, n_samp, slope, ptr(d_w))
+            else:
+                ctx.call("mrx_tod_detrend_window", ptr(X), X.stride(0), n_det, n_samp, slope, ptr(d_w), ptr(self._anchors))
+        elif name == "filter":
+            _sos_run(ctx, p["plan"], X, True, transpose)
+        elif name == "remove_spline":
+            rows = max(1, int(2e9 // (8 * n_samp)))
+            for lo in range(0, n_det, rows):
+                blk = X[lo : lo + rows].to(torch.float64)
+                fit = (blk @ p["B"].T) @ p["proj"] if transpose else (blk @ p["proj"].T) @ p["B"]
+                X[lo : lo + rows] = (blk - fit).to(torch.float32)
+        elif name == "remove_modes":
+            U, norms = p["U"], p["norms"]
+            left, right = (U / norms[:, None], U * norms[:, None]) if transpose else (U * norms[:, None], U / norms[:, None])
+            cols = max(1, int(2e9 // (8 * n_det)))
+            for lo in range(0, n_samp, cols):
+                blk = X[:, lo : lo + cols].to(torch.float64)
+                X[:, lo : lo + cols] = (blk - left @ (right.T @ blk)).to(torch.float32)
+        else:
+            raise ValueError(name)
+
+
+def _process(tod, config, ctx, device, kwargs, op):
+    """``process_tod``; ``op`` (a :class:`PreprocessOperator` or None) takes down every step as it is applied."""
     config = validate_process_config(dict(config) if config else process_operation_kwargs(**kwargs))
     dev = torch.device(device)
     ctx = ctx or Context(dev.index or 0)
@@ -165,6 +261,9 @@ def process_tod(tod, config=None, ctx=None, device="cuda:0", **kwargs):
     sample_rate = 1.0 / np.mean(np.diff(t)) if n_samp > 1 else 1.0
     anchors = torch.empty(2 * n_det + 16, dtype=torch.float64, device=dev)
     weight = np.ones(n_samp)
+    record = (lambda name, **what: op.steps.append((name, what))) if op is not None else (lambda name, **what: None)
+    if op is not None:
+        op.shape = (n_det, n_samp)
 
     def check(name):
         if bool(torch.isnan(D).any()):
@@ -173,6 +272,7 @@ def process_tod(tod, config=None, ctx=None, device="cuda:0", **kwargs):
     if "remove_slope" in config:
         ctx.call("mrx_tod_detrend_window", ptr(D), D.stride(0), n_det, n_samp, 1, None, ptr(anchors))
         check("remove_slope")
+        record("remove_slope")
 
     if "remove_spline" in config:
         sub = config["remove_spline"]
@@ -193,6 +293,7 @@ def process_tod(tod, config=None, ctx=None, device="cuda:0", **kwargs):
             A = blk @ proj.T                      # (inv(B B^T) B D^T)^T
             D[lo : lo + rows] = (blk - A @ Bd).to(torch.float32)
         check("remove_spline")
+        record("remove_spline", proj=proj, B=Bd)
 
     if "window" in config:
         w = getattr(scipy.signal.windows, config["window"]["name"])(n_samp, **config["window"].get("kwargs", {}))
@@ -200,6 +301,7 @@ def process_tod(tod, config=None, ctx=None, device="cuda:0", **kwargs):
         d_w = torch.as_tensor(np.ascontiguousarray(w, np.float64)).to(dev)
         ctx.call("mrx_tod_detrend_window", ptr(D), D.stride(0), n_det, n_samp, 0, ptr(d_w), ptr(anchors))
         check("window")
+        record("window", window=d_w)
 
     if "filter" in config:
         sub = config["filter"]
@@ -209,11 +311,14 @@ def process_tod(tod, config=None, ctx=None, device="cuda:0", **kwargs):
             sections.append(bessel_sos(sub["f_upper"], sample_rate, order, "low"))
         if "f_lower" in sub:
             sections.append(bessel_sos(sub["f_lower"], sample_rate, order, "high"))
+        plan = None
         if sections:
-            sosfilt(ctx, np.concatenate(sections, axis=0), D, remove_slope=True)
+            plan = _sos_plan(ctx, np.concatenate(sections, axis=0), n_det, n_samp, dev)
+            _sos_run(ctx, plan, D, True, False)
         else:  # the reference removes the slope before looking for filters (processing.py:151)
             ctx.call("mrx_tod_detrend_window", ptr(D), D.stride(0), n_det, n_samp, 1, None, ptr(anchors))
         check("filter")
+        record("filter", plan=plan)
 
     if "remove_modes" in config:
         m = config["remove_modes"]["modes_to_remove"]
@@ -231,6 +336,7 @@ def process_tod(tod, config=None, ctx=None, device="cuda:0", **kwargs):
             _, vecs = torch.linalg.eigh(G)
             U = vecs[:, -m:].to(Dn.dtype)  # leading eigenvectors of Dn Dn^T = left singular vectors
             D.sub_(((dnorm[:, None].to(Dn.dtype) * U) @ (U.T @ Dn)).to(torch.float32))
+            record("remove_modes", U=U.to(torch.float64).contiguous(), norms=dnorm.to(torch.float64))
         check("remove_modes")
 
     return ProcessedTOD(tod, D, weight, config)
@@ -246,22 +352,42 @@ def sosfilt(ctx, sos, D, remove_slope=False):
     ``SOS_MAX_SECTIONS`` sections and ``SOS_MAX_ROWS`` rows: a longer cascade runs as
     consecutive calls (float32 between them; only the first removes the slope), more rows as
     row blocks."""
-    sos = np.ascontiguousarray(sos, np.float64).reshape(-1, 6)
     n_det, n_samp = D.shape
     if n_det == 0 or n_samp == 0:
         return D
+    return _sos_run(ctx, _sos_plan(ctx, sos, n_det, n_samp, D.device), D, remove_slope, False)
+
+
+def _sos_plan(ctx, sos, n_det, n_samp, device):
+    """What the launches of one cascade on [n_det, n_samp] rows need: per part of at most ``SOS_MAX_SECTIONS`` sections
+    its host coefficients and chunk matrix (device), and the scratch they share."""
+    sos = np.ascontiguousarray(sos, np.float64).reshape(-1, 6)
     chunk = ctx.lib.mrx_sosfilt_chunk()
-    for k, s0 in enumerate(range(0, len(sos), SOS_MAX_SECTIONS)):
+    rows = max(1, min(n_det, SOS_MAX_ROWS))
+    parts, most = [], 0
+    for s0 in range(0, len(sos), SOS_MAX_SECTIONS):
         part = np.ascontiguousarray(sos[s0 : s0 + SOS_MAX_SECTIONS])
-        M = torch.as_tensor(np.ascontiguousarray(chunk_matrix(part, chunk))).to(D.device)
-        rows = min(n_det, SOS_MAX_ROWS)
+        M = torch.as_tensor(np.ascontiguousarray(chunk_matrix(part, chunk))).to(device)
         need = C.c_size_t()
         rc = ctx.lib.mrx_sosfilt_work_doubles(rows, n_samp, len(part), C.byref(need))
         if rc != 0:
             raise ValueError(f"mrx_sosfilt_work_doubles({rows}, {n_samp}, {len(part)}) failed ({rc})")
-        work = torch.empty(need.value, dtype=torch.float64, device=D.device)
-        for lo in range(0, n_det, rows):
-            blk = D[lo : lo + rows]
-            ctx.call("mrx_sosfilt", part.ctypes.data_as(C.POINTER(C.c_double)), len(part), ptr(M), ptr(blk), blk.stride(0), len(blk),
-                     n_samp, int(remove_slope and k == 0), ptr(blk), blk.stride(0), ptr(work))
+        most = max(most, need.value)
+        parts.append((part, M))
+    return {"parts": parts, "rows": rows, "work": torch.empty(most, dtype=torch.float64, device=device)}
+
+
+def _sos_run(ctx, plan, D, remove_slope, transpose):
+    """The cascade of ``plan`` on ``D`` in place: ``mrx_sosfilt`` part by part, the slope removed by the first; or the
+    transpose, ``mrx_sosfilt_transpose`` from the last part to the first, which ends with the slope's."""
+    n_det, n_samp = D.shape
+    if n_det == 0 or n_samp == 0:
+        return D
+    parts = list(enumerate(plan["parts"]))
+    for k, (part, M) in (reversed(parts) if transpose else parts):
+        for lo in range(0, n_det, plan["rows"]):
+            blk = D[lo : lo + plan["rows"]]
+            ctx.call("mrx_sosfilt_transpose" if transpose else "mrx_sosfilt", part.ctypes.data_as(C.POINTER(C.c_double)), len(part),
+                     ptr(M), ptr(blk), blk.stride(0), len(blk), n_samp, int(remove_slope and k == 0), ptr(blk), blk.stride(0),
+                     ptr(plan["work"]))
     return D
