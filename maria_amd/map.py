@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from ._lib import Context, ptr
+from .pipeline_host import f32_cell
 
 
 def smooth(data, weight=None, sigma=None, fwhm=None, x_res=1.0, y_res=1.0, device="cuda:0", ctx=None):
@@ -58,13 +59,10 @@ def collapse_temperature(table, axis_T, base_temperature):
     """Host part of the channel calibration (band/band.py:235-255): the (T, pwv, el) grid of a
     channel's transmission integral collapsed at the scalar base temperature with jax's float32
     index/weight rule -> [npwv, nel] float32 (NaN when the temperature is off the grid)."""
-    g = np.asarray(axis_T, np.float32)
-    x = np.float32(base_temperature)
-    i = min(max(int(np.searchsorted(g, x, side="left")) - 1, 0), len(g) - 2)
-    w = np.float32((x - g[i]) / (g[i + 1] - g[i]))
+    i, w, oob = f32_cell(axis_T, base_temperature)
     v = np.asarray(table, np.float32)
     out = (np.float32(1) - w) * v[i] + w * v[i + 1]
-    if x < g[0] or x > g[-1]:
+    if oob:
         out = np.full_like(out, np.nan)
     return out.astype(np.float32)
 

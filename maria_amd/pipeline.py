@@ -14,12 +14,14 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, pipeline_host
 from ._lib import Context, MrxBandTable, MrxError, MrxLayer, ptr
+from .pipeline_host import matern_log_tables, morton_order, table_cubic_cells, table_slabs  # noqa: F401 (also this module's names)
 
 
 class _range:
@@ -45,98 +47,22 @@ def _dev(a, dtype, device):
     return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(device)
 
 
-def matern_log_tables(nu, n=8192, lo=1e-6, hi=1e3, eps=1e-10):
-    """log of the exact Matern correlation (functions/__init__.py:30-39) and of its complement at ``n``
-    log-spaced r / r0 -- the construction of the reference's ``approximate_normalized_matern`` (:42-74), eight
-    times denser because the device interpolates it to 1e-11 (``mrx_screen_amplitudes``).  Returns
-    (log_first, log_step, log_cov, log_sf, x_cut); values the float64 range cannot hold (rho underflows
-    beyond r ~ 700 r0) are pinned at log(1e-300); ``x_cut``: the first node where the correlation has fallen
-    below ``eps`` (periodic images farther away are not summed)."""
-    import scipy.special
+class _LastRun(NamedTuple):
+    """What the last sample() / run() left behind, for coarse_loading() and coarse_pwv()."""
 
-    x = np.geomspace(lo, hi, n)
-    z = np.sqrt(2 * nu) * x + 1e-16
-    cov = 2 ** (1 - nu) / scipy.special.gamma(nu) * scipy.special.kv(nu, z) * z**nu
-    with np.errstate(divide="ignore"):
-        log_cov = np.maximum(np.log(cov), np.log(1e-300))
-        log_sf = np.maximum(np.log(1 - cov), np.log(1e-300))
-    lx = np.log(x)
-    x_cut = float(x[np.argmax(cov < eps)]) if (cov < eps).any() else float(hi)
-    return float(lx[0]), float((lx[-1] - lx[0]) / (n - 1)), np.ascontiguousarray(log_cov), np.ascontiguousarray(log_sf), x_cut
-
-
-def morton_order(offsets):
-    """Permutation that sorts focal-plane offsets along a Z-order curve, so that
-    consecutive detectors (the lanes of a wave, the 256 rows of a workgroup) form a
-    compact patch on the sky: their lines of sight then hit the same few cache lines
-    of every screen.  Pure host-side indexing; results do not depend on it."""
-    off = np.asarray(offsets, float)
-    if len(off) < 2:
-        return np.arange(len(off))
-    off = np.where(np.isfinite(off), off, 0.0)  # (a NaN offset sorts anywhere; its samples are NaN whatever its place)
-    lo, span = off.min(axis=0), np.maximum(np.ptp(off, axis=0), 1e-300)
-    q = np.minimum(((off - lo) / span * 65535.0).astype(np.uint64), 65535)
-
-    def spread(v):  # 16 bits -> every other bit of 32
-        v = (v | (v << 8)) & 0x00FF00FF
-        v = (v | (v << 4)) & 0x0F0F0F0F
-        v = (v | (v << 2)) & 0x33333333
-        return (v | (v << 1)) & 0x55555555
-
-    return np.argsort(spread(q[:, 0]) | (spread(q[:, 1]) << 1), kind="stable")
-
-
-def table_slabs(table, T0):
-    """Host part of the emission lookup: the two temperature slabs bracketing
-    ``T0`` and T0's float32 normalised distance, computed exactly as jax's
-    ``_find_indices`` would (band/band.py:283-286)."""
-    Tg = np.asarray(table["T"], np.float32)
-    x = np.float32(T0)
-    i = int(np.searchsorted(Tg, x, side="left")) - 1
-    i = min(max(i, 0), len(Tg) - 2)
-    w = np.float32((x - Tg[i]) / (Tg[i + 1] - Tg[i]))
-    oob = bool(x < Tg[0] or x > Tg[-1])
-    vals = np.asarray(table["values"], np.float32)[i : i + 2]
-    return np.ascontiguousarray(vals), w, oob
-
-
-def table_cubic_cells(table, T0):
-    """Host part of ``interpolation_method="cubic"`` (band/band.py:288-300): the band table
-    interpolated linearly to ``T0`` (scipy ``interp1d``, which raises ValueError outside the
-    temperature axis, as in the reference) and scipy's tensor-product not-a-knot cubic spline on
-    (pwv, el) expanded into one bicubic per grid cell (Taylor coefficients at the cell's lower
-    corner).  Returns the float64 buffer of ``mrx_band_table.d_cubic``:
-    [pwv nodes][el nodes][cells][16]."""
-    import scipy.interpolate
-
-    Tg, x, y = (np.asarray(table[k], float) for k in ("T", "pwv", "el"))
-    V = scipy.interpolate.interp1d(Tg, np.asarray(table["values"], float), kind="linear", axis=0)(T0)  # [n_pwv, n_el]
-    if len(x) < 4 or len(y) < 4:
-        raise ValueError("cubic interpolation needs at least 4 nodes per axis")
-    fact = (1.0, 1.0, 2.0, 6.0)
-    # The reference calls scipy's RegularGridInterpolator(method="cubic").  From scipy 1.13 on that
-    # is an NdBSpline whose coefficients come from an ITERATIVE solver (gcrotmk, atol 1e-6): it
-    # differs from the exact tensor-product spline by ~6e-6 of the table's scale.  To reproduce the
-    # reference and not the textbook, the cells are expanded from scipy's own spline object; older
-    # scipy (recursive 1-D splines, exact) and the fallback below give the exact tensor spline.
-    spline = getattr(scipy.interpolate.RegularGridInterpolator((x, y), V, method="cubic"), "_spline", None)
-    if spline is not None and hasattr(spline, "t"):
-        X0, Y0 = np.meshgrid(x[:-1], y[:-1], indexing="ij")
-        pts = np.stack([X0.ravel(), Y0.ravel()], axis=-1)
-        Cc = np.empty((len(x) - 1, len(y) - 1, 4, 4))
-        for k in range(4):
-            for m in range(4):
-                Cc[:, :, k, m] = spline(pts, nu=(m, k)).reshape(len(x) - 1, len(y) - 1) / (fact[m] * fact[k])
-    else:  # separable operator: Taylor coefficients in el of every pwv row's spline, then along pwv
-        sy = scipy.interpolate.make_interp_spline(y, V, k=3, axis=1)
-        A = np.stack([sy.derivative(k)(y[:-1]) / fact[k] if k else sy(y[:-1]) for k in range(4)], axis=-1)  # [n_pwv, n_el-1, 4]
-        sx = scipy.interpolate.make_interp_spline(x, A, k=3, axis=0)
-        Cc = np.stack([sx.derivative(m)(x[:-1]) / fact[m] if m else sx(x[:-1]) for m in range(4)], axis=-1)  # [.., 4(k), 4(m)]
-    return np.concatenate([x, y, np.ascontiguousarray(Cc).reshape(-1)])
+    # where the coarse loading is: "whole" (d_loading, [Ta][D]), "pipe" (the per-block buffers _pipe["loading"]) or
+    # "blocks" (_coarse_blocks: the one launch's blocks of [Ta][pitch], mrx_atm_synthesize)
+    layout: str = "whole"
+    krj: bool = False  # those buffers hold K_RJ, not pW
+    block_rows: int = 0  # detectors per block of the one launch
+    pwv: str = "stale"  # d_pwv: "stale", "whole" ([Ta][D]) or "blocks" (the one launch's blocks of [Ta][rows])
 
 
 class DevicePath:
     """One observation (or one detector shard of it) on one GPU."""
+
+    COARSE_KRJ_LIMIT = pipeline_host.COARSE_KRJ_LIMIT
+    SPLINE_KINK = pipeline_host.SPLINE_KINK
 
     def __init__(self, problem, device="cuda:0", det_slice=None, ctx=None, keep_pwv=False, locality_sort=True):
         self.device = torch.device(device)
@@ -151,8 +77,7 @@ class DevicePath:
         if method not in ("linear", "cubic"):
             raise ValueError(f"interpolation_method must be 'linear' or 'cubic', not {method!r}")
         self.cubic = method == "cubic"
-        sl = det_slice or slice(0, len(problem["offsets"]))
-        self.det_slice = sl
+        sl = self.det_slice = det_slice or slice(0, len(problem["offsets"]))
         dev = self.device
 
         off = np.asarray(problem["offsets"], float)[sl]
@@ -194,11 +119,22 @@ class DevicePath:
         # the bound screens into a buffer made on first use
         self.keep_pwv = bool(keep_pwv)
         self.d_pwv = torch.empty((self.Ta, self.D), dtype=torch.float64, device=dev) if keep_pwv else None
-        self._pwv_stale = True
+        self._last = _LastRun()  # (nothing sampled yet)
 
-        self._layer_bufs = []
-        self._table_bufs = []
-        self.plan = None
+        # which form run() takes: the caller's switches, and what the library said it does not support
+        self.one_launch = True  # (synthesize_applies)
+        self.block_shares = None  # relative sizes of the pipelined run's detector blocks (None: equal)
+        self._synth_unsupported = self._synth_krj_unsupported = False
+        # made on first use: by enable_lookahead, _pipeline_state and synthesize; by generate_screens (_amp: the amplitude
+        # tables by domain, steps, r0 and nu); by sampled_margins_px and _krj_split; by set_calibration (the key: Simulation's)
+        self._la = self._pipe = self._coarse_blocks = self._synth_tail = None
+        self._gen_screens = self._gen_work = self._gen_tmp = self._beam_in_spectrum = self._beam_smooth = None
+        self._gen_groups, self._gen_volumes, self._gen_fine, self._amp = {}, {}, {}, {}
+        self._margins = self._n_main = None
+        self._cal = self._cal_key = self.d_loading_krj = None
+
+        self.plan = self._layers = None
+        self._layer_bufs, self._table_bufs = [], []
         self._upload_tables()
         if all(l.get("values") is not None for l in problem["layers"]):
             self.set_screens([l["values"] for l in problem["layers"]])
@@ -225,13 +161,8 @@ class DevicePath:
             self._table_bufs.append(tuple(bufs))
 
     def layer_offsets(self, layer):
-        """f64 per-time offsets of mrx_layer (include/mrx.h):
-        (cumsum(timestep*(vx,vy,0)) + (0,0,h)) @ transform, columns 0 and 1
-        (atmosphere/atmosphere.py:318-319,346-347)."""
-        dt = self.problem["timestep"]
-        tr = np.cumsum(dt * np.c_[layer["vx"], layer["vy"], np.zeros(len(layer["vx"]))], axis=0)
-        q = (tr + np.array([0.0, 0.0, layer["h"]])) @ np.asarray(layer["transform"], float)
-        return q[:, 0], q[:, 1]
+        """f64 per-time offsets of mrx_layer (include/mrx.h; pipeline_host.layer_offsets)."""
+        return pipeline_host.layer_offsets(self.problem["timestep"], layer)
 
     def set_screens(self, screens):
         """Bind one smoothed screen per layer (numpy arrays or device tensors [E,C])."""
@@ -291,10 +222,16 @@ class DevicePath:
         cross = layer["gen"]["cross"] if layer.get("gen") is not None else layer["cross_section"]
         return de, float(cross[1] - cross[0])
 
+    @staticmethod
+    def _layer_steps(layer):
+        """(extrusion step, cross-section step) of the layer's OWN grid: what the beam's sigmas in pixels and the margin
+        test are formed with.  Like _grid_steps, the difference of the first two nodes."""
+        return float(layer["extrusion"][1] - layer["extrusion"][0]), float(layer["cross_section"][1] - layer["cross_section"][0])
+
     def _amplitude_table(self, nh, ny, nx, dh, dy, dx, r0, nu):
         """The device table of ``mrx_screen_amplitudes`` for one periodic domain, built on first use; None when the
         path was asked for the power-law spectrum."""
-        if getattr(self, "_amp", None) is None or self.problem.get("turbulence_spectrum", "covariance") != "covariance":
+        if self.problem.get("turbulence_spectrum", "covariance") != "covariance":
             return None
         key = (nh, ny, nx, dh, dy, dx, r0, nu)
         if key not in self._amp:
@@ -310,40 +247,10 @@ class DevicePath:
         return self._amp[key]
 
     def sampled_margins_px(self):
-        """Per layer, the smallest distance in pixels between any line of sight of the observation and an edge of the
-        layer's grid: (margin along the extrusion axis, margin across).  Of the WHOLE focal plane, not of this path's
-        detector shard: the margins decide how a screen is generated (the beam as a stencil or as a factor of the
-        spectrum, generate_screens), screens are shared by all shards -- regenerated by every rank or, layer-sharded,
-        made by one rank for all --, and a shard's TOD must not depend on how the detectors were cut.  Host-side and
-        conservative: the boresight track with a ring of 24 directions around the focal plane's outermost detector,
-        pushed out to circumscribe the circle, through the float64 form of the pointing
-        (coords/transforms.py:10-29) and the layer's projection (atmosphere/atmosphere.py:346-347)."""
-        if getattr(self, "_margins", None) is None:
-            p = self.problem
-            off = np.asarray(p["offsets"], float)
-            rad = float(np.hypot(off[:, 0], off[:, 1]).max()) if len(off) else 0.0
-            ang = np.linspace(0.0, 2.0 * np.pi, 24, endpoint=False)
-            ring = np.r_[np.zeros((1, 2)), (rad / np.cos(np.pi / 24) * 1.001 + 1e-9) * np.c_[np.cos(ang), np.sin(ang)]]
-            az, el = np.asarray(p["az_a"], float), np.asarray(p["el_a"], float)
-            dx, dy = ring[:, 0][:, None], ring[:, 1][:, None]
-            r, q = np.hypot(dx, dy), np.arctan2(-dx, -dy)
-            z = (np.sin(r) * np.cos(q) + 1j * np.cos(r)) * np.exp(1j * (el[None, :] - np.pi / 2))
-            phi, theta = np.arctan2(np.sin(r) * np.sin(q), z.real) + az[None, :], np.arcsin(z.imag)
-            with np.errstate(divide="ignore", invalid="ignore"):
-                px, py = np.cos(phi) / np.tan(theta), np.sin(phi) / np.tan(theta)
-            out = []
-            for layer in p["layers"]:
-                oe, oc = self.layer_offsets(layer)
-                R = np.asarray(layer["transform"], float)
-                e = layer["h"] * (px * R[0, 0] + py * R[1, 0]) + oe[None, :]
-                c = layer["h"] * (px * R[0, 1] + py * R[1, 1]) + oc[None, :]
-                ex, cs = np.asarray(layer["extrusion"], float), np.asarray(layer["cross_section"], float)
-                de, dc = (ex[-1] - ex[0]) / (len(ex) - 1), (cs[-1] - cs[0]) / (len(cs) - 1)
-                if not (np.isfinite(e).all() and np.isfinite(c).all()):
-                    out.append((-np.inf, -np.inf))
-                    continue
-                out.append((float(min(e.min() - ex[0], ex[-1] - e.max()) / de), float(min(c.min() - cs[0], cs[-1] - c.max()) / dc)))
-            self._margins = out
+        """Per layer, the margins in pixels between the lines of sight of the WHOLE focal plane and the edges of the
+        layer's grid (pipeline_host.sampled_margins_px)."""
+        if self._margins is None:
+            self._margins = pipeline_host.sampled_margins_px(self.problem)
         return self._margins
 
     def generate_screens(self, smooth=True, only=None, exchange=None):
@@ -356,93 +263,17 @@ class DevicePath:
         other ranks' layers (maria_amd.dist), run on the stream the screens are generated on -- with
         enable_lookahead() the exchange of the next observation's screens then rides beside this one's
         synthesis.  Returns the device tensors."""
-        dev = self.device
         layers = self.problem["layers"]
-        la = getattr(self, "_la", None)
+        la = self._la
         shapes = [(len(l["extrusion"]), len(l["cross_section"])) for l in layers]
         # a layer may ask for a larger periodic FFT domain ("fft_shape") than its grid:
         # the screen is then the top-left block of it (atmosphere.py ribbons are not
         # periodic; the padding decorrelates opposite edges)
         fft_shapes = [tuple(l.get("fft_shape") or sh) for l, sh in zip(layers, shapes)]
-        if getattr(self, "_gen_screens", None) is None:
-            self._gen_screens = [torch.empty(sh, dtype=torch.float32, device=dev) for sh in shapes]
-            # layers that are slices of one 3-D volume (model="3d") are generated together;
-            # the others in groups that share a 2-D FFT domain
-            self._gen_groups, self._gen_volumes = {}, {}
-            for l, (layer, f) in enumerate(zip(layers, fft_shapes)):
-                vol = layer.get("volume")
-                if vol is not None:
-                    self._gen_volumes.setdefault((vol["id"], vol["nh"], f), []).append(l)
-                else:
-                    self._gen_groups.setdefault(f, []).append(l)
-            need = 0
-            n = C.c_size_t()
-            for (fe, fc), members in self._gen_groups.items():
-                _lib.load().mrx_screen_work_floats(fe, fc, len(members), C.byref(n))
-                need = max(need, n.value)
-            for (_, nh, (fe, fc)), members in self._gen_volumes.items():
-                _lib.load().mrx_screen3d_work_floats(nh, fe, fc, len(members), C.byref(n))
-                need = max(need, n.value)
-            self._gen_work = torch.empty(need, dtype=torch.float32, device=dev)
-            # amplitude tables (mrx_screen_amplitudes: the eigenvalues of the Matern covariance on the periodic
-            # grid), one per distinct (domain, steps, r0, nu); problem["turbulence_spectrum"] = "power_law" keeps the
-            # closed-form spectrum
-            self._amp = {}
-            if self.problem.get("turbulence_spectrum", "covariance") == "covariance":
-                for (fe, fc), members in self._gen_groups.items():
-                    for l in members:
-                        de, dc = self._grid_steps(layers[l])
-                        self._amplitude_table(0, fe, fc, 0.0, de, dc, float(layers[l]["r0"]), float(layers[l]["nu"]))
-                for (_, nh, (fe, fc)), members in self._gen_volumes.items():
-                    first = layers[members[0]]
-                    de, dc = self._grid_steps(first)
-                    self._amplitude_table(nh, fe, fc, float(first["volume"]["dh"]), de, dc, float(first["r0"]), float(first["nu"]))
-            # model="3d" with per-layer cross-section grids (layer["gen"]): the volume's planes are generated on
-            # the process's generation grid, then resampled onto each layer's own grid and smoothed there
-            self._gen_fine = {}
-            for l, layer in enumerate(layers):
-                g = layer.get("gen")
-                if g is not None:
-                    ne, n_l = shapes[l]
-                    self._gen_fine[l] = dict(
-                        plane=torch.empty((ne, len(g["cross"])), dtype=torch.float32, device=dev),
-                        idx=_dev(g["idx"], torch.int32, dev), w=_dev(g["w"], torch.float32, dev), scale=_dev(g["scale"], torch.float32, dev))
-            if self._gen_fine:
-                ne = max(shapes[l][0] for l in self._gen_fine)
-                nc = max(shapes[l][1] for l in self._gen_fine)
-                self._gen_tmp = torch.empty((2, ne * nc), dtype=torch.float32, device=dev)
-            self.set_screens(self._gen_screens)
-        # The beam as a factor of the spectrum (mrx_screen_desc.periodic_beam: no stencils, a third of the generator's
-        # arithmetic less) where every line of sight of the observation keeps at least the stencil's radius + 2 pixels
-        # from the edges of the layer's grid: what those pixels hold is then scipy's reflect-mode result to rounding,
-        # and the pixels that differ (the rim) are never sampled.  The reference's own ribbons leave a margin of one or
-        # two pixels (atmosphere.py:208-245): they keep the stencils, and scipy's edges.
-        if getattr(self, "_beam_in_spectrum", None) is None or getattr(self, "_beam_smooth", None) != smooth:
-            self._beam_smooth = smooth
-            self._beam_in_spectrum = [False] * len(layers)
-            if smooth and self.problem.get("beam_in_spectrum", True):
-                margins = None
-                for l, layer in enumerate(layers):
-                    sigma = float(layer.get("beam_sigma", 0) or 0)
-                    if sigma <= 0 or layer.get("volume") is not None or l in self._gen_fine:
-                        continue
-                    if margins is None:
-                        margins = self.sampled_margins_px()
-                    de = float(layer["extrusion"][1] - layer["extrusion"][0])
-                    dc = float(layer["cross_section"][1] - layer["cross_section"][0])
-                    ry, rx = int(4.0 * sigma / de + 0.5), int(4.0 * sigma / float(layer.get("res") or dc) + 0.5)
-                    fe, fc = fft_shapes[l]
-                    self._beam_in_spectrum[l] = bool(margins[l][0] >= ry + 2 and margins[l][1] >= rx + 2 and ry < fe // 2 and rx < fc // 2)
-
-        def pixel_sigmas(layer):
-            """(sigma_e, sigma_c) of the beam in pixels as the reference forms them (atmosphere.py:338-339):
-            beam sigma / mean extrusion step and beam sigma / layer.res -- the layer's RESOLUTION, which the
-            step of its linspace grid exceeds slightly (synthetic layers without a "res": the grid step)."""
-            de = float(layer["extrusion"][1] - layer["extrusion"][0])
-            dc = float(layer["cross_section"][1] - layer["cross_section"][0])
-            sigma = float(layer.get("beam_sigma", 0) or 0) if smooth else 0.0
-            return sigma / de, sigma / float(layer.get("res") or dc)
-
+        if self._gen_screens is None:
+            self._gen_setup(shapes, fft_shapes)
+        if self._beam_in_spectrum is None or self._beam_smooth != smooth:
+            self._choose_beam_in_spectrum(smooth, fft_shapes)
         # look-ahead (enable_lookahead): this call fills the OTHER set of screens on the screens' own stream, behind
         # the samplers that last read that set; run() then samples it behind an event
         gen_ctx, target = self.ctx, self._gen_screens
@@ -451,21 +282,117 @@ class DevicePath:
             target, gen_ctx = la["screens"][which], la["ctx"]
             if la["sampled"][which]:
                 la["stream"].wait_event(la["samplers_done"][which])
+        self._launch_generation(smooth, only, fft_shapes, target, gen_ctx)
+        if la is not None:
+            if exchange is not None:
+                with torch.cuda.stream(la["stream"]):
+                    exchange(target)
+            la["screens_done"][which].record(la["stream"])
+            la["count"] += 1
+            la["current"] = which
+            self.plan, self._layers, self._layer_bufs = la["plans"][which]
+            self._gen_screens = target
+            return target
+        if exchange is not None:
+            exchange(self._gen_screens)
+        return self._gen_screens
+
+    def _gen_setup(self, shapes, fft_shapes):
+        """generate_screens' first call: the screen buffers (bound as the path's screens), the groups of layers that are
+        generated together, their work buffer, the amplitude tables and the fine planes."""
+        dev = self.device
+        layers = self.problem["layers"]
+        self._gen_screens = [torch.empty(sh, dtype=torch.float32, device=dev) for sh in shapes]
+        # layers that are slices of one 3-D volume (model="3d") are generated together;
+        # the others in groups that share a 2-D FFT domain
+        for l, (layer, f) in enumerate(zip(layers, fft_shapes)):
+            vol = layer.get("volume")
+            if vol is not None:
+                self._gen_volumes.setdefault((vol["id"], vol["nh"], f), []).append(l)
+            else:
+                self._gen_groups.setdefault(f, []).append(l)
+        need = 0
+        n = C.c_size_t()
+        for (fe, fc), members in self._gen_groups.items():
+            _lib.load().mrx_screen_work_floats(fe, fc, len(members), C.byref(n))
+            need = max(need, n.value)
+        for (_, nh, (fe, fc)), members in self._gen_volumes.items():
+            _lib.load().mrx_screen3d_work_floats(nh, fe, fc, len(members), C.byref(n))
+            need = max(need, n.value)
+        self._gen_work = torch.empty(need, dtype=torch.float32, device=dev)
+        # amplitude tables (mrx_screen_amplitudes: the eigenvalues of the Matern covariance on the periodic
+        # grid), one per distinct (domain, steps, r0, nu); problem["turbulence_spectrum"] = "power_law" keeps the
+        # closed-form spectrum
+        if self.problem.get("turbulence_spectrum", "covariance") == "covariance":
+            for (fe, fc), members in self._gen_groups.items():
+                for l in members:
+                    de, dc = self._grid_steps(layers[l])
+                    self._amplitude_table(0, fe, fc, 0.0, de, dc, float(layers[l]["r0"]), float(layers[l]["nu"]))
+            for (_, nh, (fe, fc)), members in self._gen_volumes.items():
+                first = layers[members[0]]
+                de, dc = self._grid_steps(first)
+                self._amplitude_table(nh, fe, fc, float(first["volume"]["dh"]), de, dc, float(first["r0"]), float(first["nu"]))
+        # model="3d" with per-layer cross-section grids (layer["gen"]): the volume's planes are generated on
+        # the process's generation grid, then resampled onto each layer's own grid and smoothed there
+        for l, layer in enumerate(layers):
+            g = layer.get("gen")
+            if g is not None:
+                ne, n_l = shapes[l]
+                self._gen_fine[l] = dict(
+                    plane=torch.empty((ne, len(g["cross"])), dtype=torch.float32, device=dev),
+                    idx=_dev(g["idx"], torch.int32, dev), w=_dev(g["w"], torch.float32, dev), scale=_dev(g["scale"], torch.float32, dev))
+        if self._gen_fine:
+            ne = max(shapes[l][0] for l in self._gen_fine)
+            nc = max(shapes[l][1] for l in self._gen_fine)
+            self._gen_tmp = torch.empty((2, ne * nc), dtype=torch.float32, device=dev)
+        self.set_screens(self._gen_screens)
+
+    def _choose_beam_in_spectrum(self, smooth, fft_shapes):
+        """Per layer: the beam as a factor of the spectrum (mrx_screen_desc.periodic_beam: no stencils, a third of the
+        generator's arithmetic less) where every line of sight of the observation keeps at least the stencil's radius + 2
+        pixels from the edges of the layer's grid: what those pixels hold is then scipy's reflect-mode result to rounding,
+        and the pixels that differ (the rim) are never sampled.  The reference's own ribbons leave a margin of one or
+        two pixels (atmosphere.py:208-245): they keep the stencils, and scipy's edges."""
+        layers = self.problem["layers"]
+        self._beam_smooth = smooth
+        self._beam_in_spectrum = [False] * len(layers)
+        if smooth and self.problem.get("beam_in_spectrum", True):
+            margins = None
+            for l, layer in enumerate(layers):
+                sigma = float(layer.get("beam_sigma", 0) or 0)
+                if sigma <= 0 or layer.get("volume") is not None or l in self._gen_fine:
+                    continue
+                if margins is None:
+                    margins = self.sampled_margins_px()
+                de, dc = self._layer_steps(layer)
+                ry, rx = int(4.0 * sigma / de + 0.5), int(4.0 * sigma / float(layer.get("res") or dc) + 0.5)
+                fe, fc = fft_shapes[l]
+                self._beam_in_spectrum[l] = bool(margins[l][0] >= ry + 2 and margins[l][1] >= rx + 2 and ry < fe // 2 and rx < fc // 2)
+
+    def _launch_generation(self, smooth, only, fft_shapes, target, gen_ctx):
+        """generate_screens' launches, into the screens ``target``; the 2-D groups through ``gen_ctx``."""
+        layers = self.problem["layers"]
+
+        def pixel_sigmas(layer):
+            """(sigma_e, sigma_c) of the beam in pixels as the reference forms them (atmosphere.py:338-339):
+            beam sigma / mean extrusion step and beam sigma / layer.res -- the layer's RESOLUTION, which the
+            step of its linspace grid exceeds slightly (synthetic layers without a "res": the grid step)."""
+            de, dc = self._layer_steps(layer)
+            sigma = float(layer.get("beam_sigma", 0) or 0) if smooth else 0.0
+            return sigma / de, sigma / float(layer.get("res") or dc)
 
         def describe(members):
             descs = (_lib.MrxScreenDesc * len(members))()
             for d, l in zip(descs, members):
                 layer = layers[l]
-                de = float(layer["extrusion"][1] - layer["extrusion"][0])
+                de, dc = self._grid_steps(layer)
                 fine = self._gen_fine.get(l)
                 if fine is None:
                     out = target[l]
-                    dc = float(layer["cross_section"][1] - layer["cross_section"][0])
                     d.sigma_y, d.sigma_x = pixel_sigmas(layer)
                     d.periodic_beam = int(self._beam_in_spectrum[l])
                 else:  # unsmoothed, on the generation grid
                     out = fine["plane"]
-                    dc = float(layer["gen"]["cross"][1] - layer["gen"]["cross"][0])
                     d.sigma_y = d.sigma_x = 0.0
                 d.d_out, d.stream = out.data_ptr(), l
                 d.out_ny, d.out_nx, d.ld_out = out.shape[0], out.shape[1], out.stride(0)
@@ -491,9 +418,7 @@ class DevicePath:
                     continue
                 first = layers[members[0]]
                 vol = first["volume"]
-                de = float(first["extrusion"][1] - first["extrusion"][0])
-                cross = first["gen"]["cross"] if first.get("gen") is not None else first["cross_section"]
-                dc = float(cross[1] - cross[0])
+                de, dc = self._grid_steps(first)
                 pos = (C.c_double * len(members))(*[layers[l]["volume"]["pos"] for l in members])
                 scl = (C.c_double * len(members))(*[layers[l]["volume"]["scale"] for l in members])
                 amp = self._amplitude_table(nh, fe, fc, float(vol["dh"]), de, dc, float(first["r0"]), float(first["nu"]))
@@ -514,20 +439,6 @@ class DevicePath:
                                   ptr(fine["scale"]), n_l, ptr(dst), n_l)
                     if dst is not out:
                         self.ctx.call("mrx_gauss_smooth2d", ptr(dst), ptr(out), ptr(self._gen_tmp[1]), ne, n_l, sy, sx, 4.0)
-        if la is not None:
-            which = la["count"] % 2
-            if exchange is not None:
-                with torch.cuda.stream(la["stream"]):
-                    exchange(target)
-            la["screens_done"][which].record(la["stream"])
-            la["count"] += 1
-            la["current"] = which
-            self.plan, self._layers, self._layer_bufs = la["plans"][which]
-            self._gen_screens = target
-            return target
-        if exchange is not None:
-            exchange(self._gen_screens)
-        return self._gen_screens
 
     def enable_lookahead(self):
         """Let successive observations overlap (Simulation.run's loop over its plans, sim/simulation.py:201-211;
@@ -538,12 +449,12 @@ class DevicePath:
         launches, ordered by events; the TOD of run() is stream-ordered on the caller's stream as before.  The
         returned screens are NOT ordered against the caller's stream: call wait_screens() before reading them.
         Returns False (and changes nothing) for paths whose screens are planes of a 3-D volume."""
-        if getattr(self, "_la", None) is not None:
+        if self._la is not None:
             return True
         layers = self.problem["layers"]
         if any(l.get("volume") is not None or l.get("gen") is not None for l in layers) or self.keep_pwv:
             return False
-        if getattr(self, "_gen_screens", None) is None:
+        if self._gen_screens is None:
             self.generate_screens()
         torch.cuda.synchronize(self.device)
         main = torch.cuda.current_stream(self.device)
@@ -551,20 +462,17 @@ class DevicePath:
         self.ctx.set_stream(main)
         probe = Context(self.ctx.device)
         probe.set_stream(side)
-        stream = None
         for _ in range(8):  # a hardware queue of its own beside the caller's and the samplers' (HIP has four)
             stream = torch.cuda.Stream(device=self.device)
             if self.ctx.streams_concurrent(stream) and probe.streams_concurrent(stream):
                 break
         ctx3 = Context(self.ctx.device)
         ctx3.set_stream(stream)
-        for opt in (_lib.OPT_SCREEN_STOCKHAM,):
-            ctx3.set_option(opt, self.ctx.get_option(opt))
+        ctx3.set_option(_lib.OPT_SCREEN_STOCKHAM, self.ctx.get_option(_lib.OPT_SCREEN_STOCKHAM))
         other = [torch.empty_like(t) for t in self._gen_screens]
         plans = [(self.plan, self._layers, self._layer_bufs), self._make_plan(other)]
-        ev = lambda: torch.cuda.Event()  # noqa: E731
         self._la = dict(stream=stream, ctx=ctx3, screens=[self._gen_screens, other], plans=plans, count=0, current=0,
-                        screens_done=[ev(), ev()], samplers_done=[ev(), ev()], sampled=[False, False],
+                        screens_done=[torch.cuda.Event(), torch.cuda.Event()], samplers_done=[torch.cuda.Event(), torch.cuda.Event()], sampled=[False, False],
                         writer_done={}, probe=probe)
         # the set bound now holds valid screens (generated above, on the caller's stream)
         self._la["screens_done"][0].record(main)
@@ -575,21 +483,19 @@ class DevicePath:
         """enable_lookahead: everything queued on ``stream`` (default: the current one) so far has read the bound set of
         screens -- the screens' stream may refill that set behind it.  Every reader of the bound screens ends with this
         (sample(), the serial and K_RJ forms of run(), synthesize(); the two-stream pipeline marks its side stream)."""
-        la = getattr(self, "_la", None)
+        la = self._la
         if la is not None:
             la["samplers_done"][la["current"]].record(stream or torch.cuda.current_stream(self.device))
             la["sampled"][la["current"]] = True
 
     def wait_screens(self, stream=None):
         """Order ``stream`` (default: the current one) behind the generation of the screens now bound."""
-        la = getattr(self, "_la", None)
+        la = self._la
         if la is not None:
             (stream or torch.cuda.current_stream(self.device)).wait_event(la["screens_done"][la["current"]])
 
     # -- hot path ------------------------------------------------------------
     def sample(self, want_pwv=False):
-        self._pipelined = False
-        self._synthesized = False
         if self.plan is None:
             raise RuntimeError("no screens bound: call set_screens() or generate_screens() first")
         self.wait_screens()
@@ -598,9 +504,8 @@ class DevicePath:
             ptr(self.d_dx), ptr(self.d_dy), ptr(self.d_band), ptr(self.d_m00), self.D,
             self.pwv0, ptr(self.d_pwv) if (self.keep_pwv or want_pwv) else None, ptr(self.d_loading), ptr(self.d_flags),
         )
-        self._pwv_stale = not (self.keep_pwv or want_pwv)
-        self._pwv_blocked = False
         self._mark_sampled()
+        self._last = _LastRun(pwv="whole" if (self.keep_pwv or want_pwv) else "stale")
 
     def prepare(self, krj=False):
         """Second derivatives of the coarse loading (``krj``: of the coarse loading in K_RJ that
@@ -626,17 +531,12 @@ class DevicePath:
             ptr(self.d_t), n_main, ptr(self.d_gain), ptr(self.d_rows), ptr(out), out.stride(0),
         )
         if krj and n_main < self.T:
-            k = self._krj_tail_knots()
-            self._krj_tail(self.d_loading[self.Ta - k :], self.D, slice(0, self.D), out, ptr(self.d_rows), self.ctx)
+            self._krj_tail(self.d_loading[self.Ta - self._krj_tail_knots() :], self.D, slice(0, self.D), out, ptr(self.d_rows), self.ctx)
 
     def _krj_split(self):
-        """Samples up to the last coarse knot.  Past it the reference EXTRAPOLATES its spline of the loading and divides
-        by the true denominator; the coarse-grid form would extrapolate loading / denominator instead, and an extrapolated
-        cubic misses the denominator's motion by 50x what an interior interval does (9e-5 in the last four samples of a
-        tight fast scan, found by the randomised front-end sweep) -- so those samples, at most one coarse step of them,
-        take the per-sample form: the two-call spline of the last knots and mrx_spline_upsample_krj on that window."""
-        if getattr(self, "_n_main", None) is None:
-            self._n_main = int(np.searchsorted(np.asarray(self.problem["t"], float)[: self.T], float(self.problem["ta"][-1]), side="right"))
+        """Samples up to the last coarse knot: run(krj=True) divides the ones past it one by one (pipeline_host.krj_split)."""
+        if self._n_main is None:
+            self._n_main = pipeline_host.krj_split(self.problem["t"], self.problem["ta"], self.T)
         return self._n_main
 
     def _krj_tail_knots(self):
@@ -650,54 +550,57 @@ class DevicePath:
         ym = torch.empty((k, n, 2), dtype=torch.float32, device=self.device)
         ctx.call("mrx_spline_prepare", ptr(y_tail), n, k, ptr(ym))
         dst = out[:, s0:] if d_rows.value else out[rows, s0:]
-        ctx.call(
-            "mrx_spline_upsample_krj", ptr(ym), n, k, float(self.problem["ta"][self.Ta - k]), self.dta, ptr(self.d_t[s0:]), self.T - s0,
-            None if self.d_gain is None else ptr(self.d_gain[rows]), d_rows, ptr(c["bore_el"][s0:]), ptr(c["dx"][rows]), ptr(c["dy"][rows]),
-            ptr(self.d_band[rows]), ptr(c["axis"]), ptr(c["values"]), c["n_el"], c["n_bands"], ptr(dst), out.stride(0),
-        )
+        ctx.call("mrx_spline_upsample_krj", ptr(ym), n, k, float(self.problem["ta"][self.Ta - k]), self.dta, ptr(self.d_t[s0:]), self.T - s0,
+                 None if self.d_gain is None else ptr(self.d_gain[rows]), d_rows, ptr(c["bore_el"][s0:]), ptr(c["dx"][rows]), ptr(c["dy"][rows]),
+                 ptr(self.d_band[rows]), *self._cal_abi(), ptr(dst), out.stride(0))
 
     def set_gain(self, gain):
         """Per-detector scale of the TOD, in the caller's detector order (or None)."""
         self.d_gain = None if gain is None else _dev(np.asarray(gain, np.float32)[self.order], torch.float32, self.device)
 
+    _synthesized = property(lambda self: self._last.layout == "blocks", doc="was the last run one launch?")
+    _synth_block_rows = property(lambda self: self._last.block_rows, doc="detectors per block of the last one launch")
+
+    def _join_blocks(self, flat, pitch):
+        """[Ta, D] from the one launch's buffer ``flat``: block after block of _last.block_rows detectors (the last one
+        ragged), each a [Ta][pitch(n)] array of which the block's n detectors are the first columns."""
+        parts = []
+        for lo in range(0, self.D, self._last.block_rows):
+            n = min(self._last.block_rows, self.D - lo)
+            parts.append(flat[self.Ta * lo : self.Ta * lo + self.Ta * pitch(n)].view(self.Ta, pitch(n))[:, :n])
+        return torch.cat(parts, dim=1)
+
     def coarse_loading(self):
         """[D, Ta] float32 coarse loading in the caller's detector order (device tensor)."""
-        if getattr(self, "_synthesized", False):  # the last run was one launch: blocks of [Ta][pitch] (mrx_atm_synthesize)
-            if getattr(self, "_synthesized_krj", False):
+        last = self._last
+        if last.layout == "blocks":  # the last run was one launch: blocks of [Ta][pitch] (mrx_atm_synthesize)
+            if last.krj:
                 raise RuntimeError("the last run() wrote its coarse loading in K_RJ: call sample() (pW) before coarse_loading()")
-            br, parts = self._synth_block_rows, []
-            for lo in range(0, self.D, br):
-                n = min(br, self.D - lo)
-                pitch = (n + 31) // 32 * 32
-                parts.append(self._coarse_blocks[self.Ta * lo : self.Ta * lo + self.Ta * pitch].view(self.Ta, pitch)[:, :n])
-            return torch.cat(parts, dim=1).T.index_select(0, self._d_inverse)
-        if getattr(self, "_pipelined", False):  # the last run kept it in per-block buffers
-            if getattr(self, "_pipelined_krj", False):
+            loading = self._join_blocks(self._coarse_blocks, lambda n: (n + 31) // 32 * 32)
+        elif last.layout == "pipe":  # the last run kept it in per-block buffers
+            if last.krj:
                 raise RuntimeError("the last run() converted its coarse buffers to K_RJ in place: call sample() (pW) before coarse_loading()")
-            return torch.cat(self._pipe["loading"], dim=1).T.index_select(0, self._d_inverse)
-        return self.d_loading.T.index_select(0, self._d_inverse)
+            loading = torch.cat(self._pipe["loading"], dim=1)
+        else:
+            loading = self.d_loading
+        return loading.T.index_select(0, self._d_inverse)
 
     def coarse_pwv(self):
         """[D, Ta] float64 zenith-scaled pwv in the caller's detector order (of the screens now bound:
         without ``keep_pwv`` the sampler runs once more to produce it)."""
         if self.d_pwv is None:
             self.d_pwv = torch.empty((self.Ta, self.D), dtype=torch.float64, device=self.device)
-        if self._pwv_stale:
+        if self._last.pwv == "stale":
             self.sample(want_pwv=True)
-        if getattr(self, "_pwv_blocked", False) and self._synth_block_rows < self.D:  # the one-launch form's blocks
-            br, flat, parts = self._synth_block_rows, self.d_pwv.view(-1), []
-            for lo in range(0, self.D, br):
-                n = min(br, self.D - lo)
-                parts.append(flat[self.Ta * lo : self.Ta * (lo + n)].view(self.Ta, n))
-            return torch.cat(parts, dim=1).T.index_select(0, self._d_inverse)
-        return self.d_pwv.T.index_select(0, self._d_inverse)
+        pwv = self._join_blocks(self.d_pwv.view(-1), lambda n: n) if self._last.pwv == "blocks" else self.d_pwv
+        return pwv.T.index_select(0, self._d_inverse)
 
     def coarse_pwv_time_major(self, rows=None):
         """[Ta, n] float64, time-major: the zenith-scaled pwv of the caller's rows ``rows`` (a device int64 tensor; None:
         all of them, in the caller's order) in the layout ``mrx_map_sample`` reads -- one gather along the detector axis of
         the sampler's own [Ta][D] array (which sits in the path's internal detector order) instead of coarse_pwv()'s
         transpose, the caller's row selection and a transpose back: four passes over 480 MB at 10 000 x 6 000."""
-        if self.d_pwv is None or self._pwv_stale or (getattr(self, "_pwv_blocked", False) and self._synth_block_rows < self.D):
+        if self._last.pwv != "whole":
             full = self.coarse_pwv()  # (samples if need be; puts the one launch's detector blocks together)
             return (full if rows is None else full.index_select(0, rows)).T.contiguous()
         cols = self._d_inverse if rows is None else self._d_inverse.index_select(0, rows)
@@ -721,8 +624,8 @@ class DevicePath:
         (MRX_FLAG_HANDOVER: the TOD is then invalid) are reported there.  Simulation.run_obs does."""
         if out is None:
             out = torch.empty((self.D, self.T), dtype=torch.float32, device=self.device)
-        coarse_form = krj and krj != "sample" and self.coarse_krj_bound() <= self.COARSE_KRJ_LIMIT
-        if blocks is None and (not krj or (coarse_form and not getattr(self, "_synth_krj_unsupported", False))) and self.synthesize_applies():
+        form, blocks = self._run_form(blocks, krj)
+        if form == "one launch":
             try:
                 return self.synthesize(out, writer_events=writer_events, krj=bool(krj))
             except MrxError as e:
@@ -730,24 +633,39 @@ class DevicePath:
                     raise
                 # (a layer off a uniform axis, a literal option, cubic tables -- or, in K_RJ, a cell table too large for the
                 #  launch's LDS: the two-call forms)
-                setattr(self, "_synth_krj_unsupported" if krj else "_synth_unsupported", True)
-        if blocks is None:
-            blocks = self.default_blocks()
-        if krj and not self.coarse_krj_bound() <= self.COARSE_KRJ_LIMIT:
+                if krj:
+                    self._synth_krj_unsupported = True
+                else:
+                    self._synth_unsupported = True
+                form, blocks = self._run_form(blocks, krj)
+        if form == "per sample":
             # the per-sample conversion fused into the writer (set_calibration first)
             self.sample()
             self.prepare()
             self.upsample_krj(out)
             return out
-        if blocks > 1 and not self.keep_pwv:
+        if form == "pipeline":
             return self._run_pipelined(out, blocks, writer_events=writer_events, krj=krj)
         with _range("Sampling turbulence + Computing atmospheric emission"):
-            self.sample()
+            self.sample()  # (leaves the record: the coarse loading stays whole and in pW, K_RJ goes to d_loading_krj)
         with _range("Upsampling atmospheric loading"):
             if krj:
                 self.coarse_to_krj()
             self.upsample_fused(out, krj=krj)
         return out
+
+    def _run_form(self, blocks, krj):
+        """(form, blocks) of a run(blocks=, krj=): "one launch" (synthesize), "per sample" (the K_RJ writer, where
+        coarse_krj_bound() refuses the coarse-grid form), "pipeline" (_run_pipelined on two streams) or "serial" (the
+        stages back to back); ``blocks``: the caller's, or default_blocks() where a two-call form is taken."""
+        coarse_ok = bool(krj) and self.coarse_krj_bound() <= self.COARSE_KRJ_LIMIT
+        if blocks is None and self.synthesize_applies() and (not krj or (coarse_ok and krj != "sample" and not self._synth_krj_unsupported)):
+            return "one launch", None
+        if blocks is None:
+            blocks = self.default_blocks()
+        if krj and not coarse_ok:
+            return "per sample", blocks
+        return ("pipeline" if blocks > 1 and not self.keep_pwv else "serial"), blocks
 
     def synthesize_applies(self):
         """Does run() take the one-launch form by default?  Wherever the library's form applies (every layer on a
@@ -758,9 +676,9 @@ class DevicePath:
         The two-call forms stay selectable (same bits, the stages back to back or pipelined on two streams): set
         ``path.one_launch = False``, or MARIA_AMD_ONE_LAUNCH=0 in the environment for every path of the process
         (``Simulation`` included) -- the fallback for a device on which the launch's hand-over raises MRX_FLAG_HANDOVER."""
-        if not getattr(self, "one_launch", True) or os.environ.get("MARIA_AMD_ONE_LAUNCH", "1") == "0":
+        if not self.one_launch or os.environ.get("MARIA_AMD_ONE_LAUNCH", "1") == "0":
             return False
-        return self.D >= 1024 and not getattr(self, "_synth_unsupported", False)
+        return self.D >= 1024 and not self._synth_unsupported
 
     def synthesize(self, out=None, block_rows=None, sampler_wgs_per_cu=None, chunk=None, writer_events=None, krj=False, sampler_wgs=0):
         """Atmosphere -> TOD in ONE launch (mrx_atm_synthesize): sampler work items and TOD tiles as two queues of
@@ -788,7 +706,7 @@ class DevicePath:
         if writer_events is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record(main)
-        if getattr(self, "_coarse_blocks", None) is None:
+        if self._coarse_blocks is None:
             self._coarse_blocks = torch.empty(self.Ta * ((self.D + 31) // 32 * 32), dtype=torch.float32, device=self.device)
         saved = (self.ctx.get_option(_lib.OPT_SAMPLE_WGS_PER_CU), self.ctx.get_option(_lib.OPT_SAMPLE_CHUNK))
         if sampler_wgs_per_cu is not None:
@@ -804,10 +722,10 @@ class DevicePath:
         if krj:
             c = self._cal
             if self._krj_split() < self.T:  # the samples past the last knot: per sample, from the last knots in pW
-                if getattr(self, "_synth_tail", None) is None:
+                if self._synth_tail is None:
                     self._synth_tail = torch.empty((self._krj_tail_knots(), self.D), dtype=torch.float32, device=self.device)
                 tail = self._synth_tail
-            args += [ptr(c["dx"]), ptr(c["dy"]), ptr(c["axis"]), ptr(c["values"]), c["n_el"], c["n_bands"],
+            args += [ptr(c["dx"]), ptr(c["dy"]), *self._cal_abi(),
                      ptr(tail), 0 if tail is None else tail.shape[0], 0 if tail is None else tail.stride(0)]
         # keep_pwv: the sampler's second output, block by block like the loading (coarse_pwv() puts the blocks together)
         args.append(ptr(self.d_pwv) if self.keep_pwv else None)
@@ -823,12 +741,10 @@ class DevicePath:
             ev[1].record(main)
             writer_events.append(ev)
         self._mark_sampled(main)  # (enable_lookahead: the screens' stream may refill this set once this launch is through)
-        self._synth_block_rows = self.synth_block_rows(int(block_rows))
-        self._synthesized = True
-        self._synthesized_krj = bool(krj)  # (the coarse blocks then hold K_RJ, not pW)
-        self._pipelined = False
-        self._pwv_stale = not self.keep_pwv
-        self._pwv_blocked = self.keep_pwv  # (d_pwv holds blocks of [Ta][rows], not one [Ta][D] array)
+        rows = self.synth_block_rows(int(block_rows))
+        # (krj: the coarse blocks then hold K_RJ, not pW; a kept pwv in more than one block: d_pwv holds blocks of
+        #  [Ta][rows], not one [Ta][D] array)
+        self._last = _LastRun("blocks", bool(krj), rows, ("blocks" if rows < self.D else "whole") if self.keep_pwv else "stale")
         return out
 
     def synth_block_rows(self, block_rows=0):
@@ -864,7 +780,6 @@ class DevicePath:
         and one new stream in four lands on the caller's -- the two then take turns and the pipelined step is as
         slow as the serial one (mrx_streams_concurrent)."""
         self.ctx.set_stream(main)
-        side = None
         for _ in range(6):
             side = torch.cuda.Stream(device=self.device)
             if self.ctx.streams_concurrent(side):
@@ -872,7 +787,7 @@ class DevicePath:
         return side
 
     def _pipeline_state(self, blocks, main=None):
-        st = getattr(self, "_pipe", None)
+        st = self._pipe
         main = main if main is not None else torch.cuda.current_stream(self.device)
         if st is not None and st["blocks"] == blocks:
             if st["main"] != main.cuda_stream:  # another caller's stream: the side stream must be checked against it
@@ -884,7 +799,7 @@ class DevicePath:
         # first block half as long as the others, whose writer then waits for the second sampler: 2.02-2.05 ms
         # against 2.07-2.12 at four blocks; scripts/exp_block_shares.py)
         units = -(-self.D // 256)
-        share = getattr(self, "block_shares", None) or [1] * blocks
+        share = self.block_shares or [1] * blocks
         cuts = np.floor(np.cumsum(share) / float(sum(share)) * units + 0.5).astype(int)
         edges = [0] + [min(int(c) * 256, self.D) for c in cuts]
         edges[-1] = self.D
@@ -915,7 +830,6 @@ class DevicePath:
             raise RuntimeError("no screens bound: call set_screens() or generate_screens() first")
         if resident_wgs_per_cu is None:
             resident_wgs_per_cu = self.default_resident_wgs()
-        resident_wgs_per_cu = int(os.environ.get("MRX_AB_RESIDENT_WGS", resident_wgs_per_cu))  # (A/B runs)
         main = torch.cuda.current_stream(self.device)
         st = self._pipeline_state(blocks, main)
         side, ctx2 = st["side"], st["ctx2"]
@@ -923,14 +837,11 @@ class DevicePath:
         # recorded on, whatever stream was current when this DevicePath was made
         self.ctx.set_stream(main)
         serial = serial_events is not None
-        la = getattr(self, "_la", None) if not (serial or krj) else None
-        if la is None:
-            self.wait_screens(main)
-        else:
-            side.wait_event(la["screens_done"][la["current"]])
+        la = self._la if not (serial or krj) else None
+        self.wait_screens(main if la is None else side)
         if serial:
             side, ctx2 = main, self.ctx
-        if not serial:
+        else:
             # the sampler runs through the side context: what the caller set on this path's context (the cell rule, the
             # pointing chain: MRX_OPT_AXIS_LITERAL, MRX_OPT_POINTING_CHAIN) applies there too
             for opt in (_lib.OPT_POINTING_CHAIN, _lib.OPT_AXIS_LITERAL):
@@ -978,10 +889,7 @@ class DevicePath:
             else:
                 st["ready"][i].record(side)
                 main.wait_event(st["ready"][i])
-            if self.d_rows is not None:
-                dst, rows = out, sl(self.d_rows, lo, hi)
-            else:
-                dst, rows = out[lo:hi], None
+            dst, rows = (out, sl(self.d_rows, lo, hi)) if self.d_rows is not None else (out[lo:hi], None)
             if writer_events is not None:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record(main)
@@ -1005,11 +913,9 @@ class DevicePath:
         ctx2.set_option(_lib.OPT_SAMPLE_WGS_PER_CU, saved[0])
         ctx2.set_option(_lib.OPT_SAMPLE_TIMES, saved[1])
         self.ctx.set_option(_lib.OPT_WRITER_PER_TILE, 0)
-        if la is not None:  # the screens' stream may refill this set once these samplers are through
-            la["samplers_done"][la["current"]].record(side)
-            la["sampled"][la["current"]] = True
-        else:  # (the serial and K_RJ forms sample on streams the caller's stream is ordered behind by now)
-            self._mark_sampled(main)
+        # the screens' stream may refill this set once these samplers are through (the serial and K_RJ forms sample on
+        # streams the caller's stream is ordered behind by now)
+        self._mark_sampled(main if la is None else side)
         if krj and krj != "sample" and self._krj_split() < self.T:
             if serial:
                 self._krj_tail(st["tail"], self.D, slice(0, self.D), out, ptr(self.d_rows), self.ctx)
@@ -1020,10 +926,7 @@ class DevicePath:
                     self._krj_tail(st["tail"], self.D, slice(0, self.D), out, ptr(self.d_rows), ctx2)
                 st["tail_done"].record(side)
                 main.wait_event(st["tail_done"])
-        self._pipelined = True
-        self._synthesized = False
-        self._pipelined_krj = bool(krj and krj != "sample")  # (the coarse buffers then hold K_RJ, not pW)
-        self._pwv_stale = True
+        self._last = _LastRun("pipe", krj=bool(krj and krj != "sample"))  # (krj: the coarse buffers then hold K_RJ, not pW)
         return out
 
     # -- TOD.to("K_RJ") fused into the upsample -----------------------------------------
@@ -1039,94 +942,28 @@ class DevicePath:
         K_RJ = pW / den.  ``bore_el``: full-rate boresight elevation [T]; ``coords_offsets``:
         the (rolled) offsets of observation.coords [D, 2] in the caller's detector order."""
         dev = self.device
-        k_B = 1.380649e-23
-        nb = len(cal_tables)
-        el_axis = np.asarray(cal_tables[0]["el"], float)
-        polarized = np.zeros(nb, bool) if polarized is None else np.asarray(polarized, bool)
-        dens = np.zeros((nb, len(el_axis)), np.float32)
-        for b, tab in enumerate(cal_tables):
-            assert np.array_equal(np.asarray(tab["el"], float), el_axis), "bands must share the elevation axis"
-            vals = np.asarray(tab["values"], np.float32).astype(np.float64)
-            wts = []
-            for axis, x in ((tab["T"], base_temperature), (tab["pwv"], zenith_pwv)):
-                g = np.asarray(axis, np.float32)
-                xf = np.float32(x)
-                i = int(np.searchsorted(g, xf, side="left")) - 1
-                i = min(max(i, 0), len(g) - 2)
-                w = np.float32((xf - g[i]) / (g[i + 1] - g[i]))
-                oob = bool(xf < g[0] or xf > g[-1])
-                wts.append((i, float(w), oob))
-            (it, wt, ot), (ip, wp, op) = wts
-            sl = vals[it : it + 2, ip : ip + 2]  # [2, 2, nel]
-            col = ((1 - wt) * (1 - wp)) * sl[0, 0] + ((1 - wt) * wp) * sl[0, 1] + (wt * (1 - wp)) * sl[1, 0] + (wt * wp) * sl[1, 1]
-            if ot or op:
-                col = np.full_like(col, np.nan)
-            dens[b] = ((0.5 if polarized[b] else 1.0) * k_B * 1e12 * col).astype(np.float32)
+        el_axis, dens = pipeline_host.collapse_calibration(cal_tables, base_temperature, zenith_pwv, polarized)
         off = np.asarray(coords_offsets, float)[self.det_slice][self.order]
         self._cal = dict(
-            axis=_dev(el_axis, torch.float32, dev), values=_dev(dens, torch.float32, dev), n_el=len(el_axis), n_bands=nb,
+            axis=_dev(el_axis, torch.float32, dev), values=_dev(dens, torch.float32, dev), n_el=len(el_axis), n_bands=len(dens),
             bore_el=_dev(bore_el, torch.float32, dev), dx=_dev(off[:, 0], torch.float32, dev), dy=_dev(off[:, 1], torch.float32, dev),
-            axis_np=el_axis.astype(np.float32).astype(np.float64), values_np=dens.astype(np.float64),
+            axis_np=el_axis, values_np=dens,
             # (of the WHOLE focal plane, not of this shard's rows: which form of the conversion a run takes must not
             # depend on how its detectors are sharded -- shards are bit-identical to the unsharded rows)
             radius=float(np.hypot(*np.asarray(coords_offsets, float).T).max()) if len(coords_offsets) else 0.0,
         )
 
-    # the coarse-grid form of the K_RJ conversion is taken when this estimate of its deviation from the
-    # per-sample form stays below 0.4 of the parity tolerance (1e-5): the float32 path itself takes 3e-6 of it
-    # at full size (DESIGN 4), which leaves a quarter of the tolerance unspent
-    COARSE_KRJ_LIMIT = 4.0e-6
-    SPLINE_KINK = 0.1708  # max |spline - f| / (slope jump x knot spacing) for a kink between uniform knots
+    def _cal_abi(self):
+        """The calibration as every libmrx call takes it: (elevation axis, denominators, n_el, n_bands)."""
+        c = self._cal
+        return ptr(c["axis"]), ptr(c["values"]), c["n_el"], c["n_bands"]
 
     def coarse_krj_bound(self):
-        """Estimate of max |S[y/g] - S[y]/g| / |S[y]/g| (S: the spline in time, g: the K_RJ
-        denominator at the detector's elevation), i.e. of what dividing the COARSE loading by g
-        (mrx_coarse_to_krj, then the pW writer) changes against dividing every full-rate sample
-        (mrx_spline_upsample_krj, the reference's order, tod/tod.py:106-142).  Both are the same
-        linear functional of y but for the spline's interpolation error on g(t) = den(el(t)):
-        (a) where a detector's elevation crosses a node of the table's axis between two knots g has
-        a kink, and the not-a-knot cubic spline through uniform knots misses a kink by at most 0.1708 x
-        (slope jump) x (knot spacing) -- the kink in the middle of a knot interval; 0.085 on a knot; a
-        linear interpolant: 0.25 -- (tests/test_host_geometry.py::test_spline_error_at_a_kink computes it);
-        measured on the daisy scan: 0.15;
-        (b) inside a cell g is linear in el, so the error is the spline's error on el(t),
-        (5/384) h^4 d4el/dt4 -- estimated from fourth differences of the coarse boresight.
-        inf when the form does not apply: a NaN in the collapsed table, a detector that may leave
-        the table's elevation axis, or one that comes within 7 deg of the zenith (its elevation
-        is not smooth in time there)."""
-        c = self._cal
-        ax, den = c["axis_np"], c["values_np"]
-        el = np.asarray(self.problem["el_a"], float)
-        if not np.isfinite(den).all() or len(el) < 5:
-            return float("inf")
-        lo, hi = el.min() - 1.05 * c["radius"], el.max() + 1.05 * c["radius"]
-        if lo < ax[0] or hi > ax[-1] or hi > np.radians(83.0):
-            return float("inf")
-        # only the part of the axis the detectors visit counts: the cells that overlap [lo, hi] and the
-        # nodes between them
-        i0 = max(int(np.searchsorted(ax, lo, side="right")) - 1, 0)
-        i1 = min(int(np.searchsorted(ax, hi, side="left")), len(ax) - 1)  # cells i0 .. i1 - 1
-        slope = np.diff(den, axis=1) / np.diff(ax)[None, :]
-        inner = slice(i0, i1 - 1)  # jumps between cells k and k + 1, k = i0 .. i1 - 2, sit at node k + 1
-        rel_jump = (np.abs(np.diff(slope, axis=1))[:, inner] / np.abs(den[:, 1:-1][:, inner])).max() if i1 - i0 > 1 else 0.0
-        cells = slice(i0, i1)
-        rel_slope = (np.abs(slope[:, cells]) / np.minimum(np.abs(den[:, 1:]), np.abs(den[:, :-1]))[:, cells]).max()
-        step = np.abs(np.diff(el)).max()
-        d4 = np.abs(np.diff(el, n=4)).max()
-        # Samples BEFORE the first knot (none in the reference, whose coarse grid starts at the first sample) would be
-        # EXTRAPOLATED by both forms, and the cubic's error on g at a distance
-        # delta h beyond the end is delta (delta+1) (delta+2) (delta+3) / 24 times h^4 d4g/dt4 -- 0.95 at delta = 1
-        # against the 5/384 of an interior interval -- and a kink there is missed by delta x (slope jump) x h.  (A
-        # randomised sweep found the form 9e-5 off in the last four samples of a tight, fast scan: a 0.13 deg daisy
-        # at 0.6 deg/s, 12 knots per turn.)
-        t, ta = np.asarray(self.problem["t"], float), np.asarray(self.problem["ta"], float)
-        h = (ta[-1] - ta[0]) / max(len(ta) - 1, 1)
-        delta = max(0.0, (ta[0] - t.min()) / h) if len(t) else 0.0  # (past the last knot the samples are divided one by one)
-        smooth = max(5.0 / 384.0, delta * (delta + 1) * (delta + 2) * (delta + 3) / 24.0)
-        kink = max(self.SPLINE_KINK, delta)
-        # + 4e-7: the two forms round differently in float32 (and the per-sample writer interpolates
-        # the reciprocal over 4 samples)
-        return float(1.1 * (kink * rel_jump * step + smooth * rel_slope * d4) + 4e-7)
+        """Estimate of what dividing the COARSE loading by the K_RJ denominator (mrx_coarse_to_krj, then the pW writer)
+        changes against dividing every full-rate sample (mrx_spline_upsample_krj, the reference's order); inf where the
+        coarse-grid form does not apply.  run() takes that form up to COARSE_KRJ_LIMIT (pipeline_host.coarse_krj_bound)."""
+        c, p = self._cal, self.problem
+        return pipeline_host.coarse_krj_bound(c["axis_np"], c["values_np"], c["radius"], p["el_a"], p["t"], p["ta"])
 
     def coarse_to_krj(self, loading=None, n=None, rows=slice(None), ctx=None, tail=None):
         """mrx_coarse_to_krj on the coarse loading (``loading``: a block's [Ta, n] buffer, in
@@ -1134,25 +971,21 @@ class DevicePath:
         ``tail``: a [k, n] view that receives the last k knots in pW as they are read (_krj_tail's input)."""
         c = self._cal
         if loading is None:
-            if getattr(self, "d_loading_krj", None) is None:
+            if self.d_loading_krj is None:
                 self.d_loading_krj = torch.empty_like(self.d_loading)
             src, dst, n = self.d_loading, self.d_loading_krj, self.D
         else:
             src = dst = loading
-        (ctx or self.ctx).call(
-            "mrx_coarse_to_krj_keep_tail", ptr(src), n, self.Ta, ptr(self.d_el), ptr(c["dx"][rows]), ptr(c["dy"][rows]), ptr(self.d_band[rows]),
-            ptr(c["axis"]), ptr(c["values"]), c["n_el"], c["n_bands"], ptr(dst),
-            ptr(tail), 0 if tail is None else tail.shape[0], 0 if tail is None else tail.stride(0),
-        )
+        (ctx or self.ctx).call("mrx_coarse_to_krj_keep_tail", ptr(src), n, self.Ta, ptr(self.d_el), ptr(c["dx"][rows]), ptr(c["dy"][rows]),
+                               ptr(self.d_band[rows]), *self._cal_abi(), ptr(dst),
+                               ptr(tail), 0 if tail is None else tail.shape[0], 0 if tail is None else tail.stride(0))
 
     def upsample_krj(self, out):
         """mrx_spline_upsample_krj: the TOD in K_RJ (set_calibration first)."""
         c = self._cal
-        self.ctx.call(
-            "mrx_spline_upsample_krj", ptr(self.d_ym), self.D, self.Ta, self.ta0, self.dta, ptr(self.d_t), self.T,
-            ptr(self.d_gain), ptr(self.d_rows), ptr(c["bore_el"]), ptr(c["dx"]), ptr(c["dy"]), ptr(self.d_band),
-            ptr(c["axis"]), ptr(c["values"]), c["n_el"], c["n_bands"], ptr(out), out.stride(0),
-        )
+        self.ctx.call("mrx_spline_upsample_krj", ptr(self.d_ym), self.D, self.Ta, self.ta0, self.dta, ptr(self.d_t), self.T,
+                      ptr(self.d_gain), ptr(self.d_rows), ptr(c["bore_el"]), ptr(c["dx"]), ptr(c["dy"]), ptr(self.d_band),
+                      *self._cal_abi(), ptr(out), out.stride(0))
 
     def krj_row_tables(self):
         """What mrx_noise_generate_krj takes besides the field: the calibration of set_calibration() with the per-detector
@@ -1166,22 +999,17 @@ class DevicePath:
     def to_krj(self, data):
         """mrx_tod_to_krj: convert a full-rate [D, T] pW field (caller's row order) to K_RJ in
         place with the calibration of ``set_calibration`` (tod/tod.py:106-142)."""
-        c = self._cal
-        assert tuple(data.shape) == (self.D, self.T) and data.stride(1) == 1
-        self.ctx.call(
-            "mrx_tod_to_krj", ptr(data), data.stride(0), self.D, self.T, None, ptr(self.d_rows), ptr(c["bore_el"]),
-            ptr(c["dx"]), ptr(c["dy"]), ptr(self.d_band), ptr(c["axis"]), ptr(c["values"]), c["n_el"], c["n_bands"],
-        )
-        return data
+        return self._tod_krj("mrx_tod_to_krj", data)
 
     def from_krj(self, data):
         """mrx_tod_from_krj: the way back, a [D, T] K_RJ field to pW in place."""
+        return self._tod_krj("mrx_tod_from_krj", data)
+
+    def _tod_krj(self, call, data):
         c = self._cal
         assert tuple(data.shape) == (self.D, self.T) and data.stride(1) == 1
-        self.ctx.call(
-            "mrx_tod_from_krj", ptr(data), data.stride(0), self.D, self.T, None, ptr(self.d_rows), ptr(c["bore_el"]),
-            ptr(c["dx"]), ptr(c["dy"]), ptr(self.d_band), ptr(c["axis"]), ptr(c["values"]), c["n_el"], c["n_bands"],
-        )
+        self.ctx.call(call, ptr(data), data.stride(0), self.D, self.T, None, ptr(self.d_rows), ptr(c["bore_el"]),
+                      ptr(c["dx"]), ptr(c["dy"]), ptr(self.d_band), *self._cal_abi())
         return data
 
     def check_flags(self):

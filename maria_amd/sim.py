@@ -357,7 +357,7 @@ class Simulation:
         path = atm._device_path()
         key = (metadata["base_temperature"], metadata["pwv"])
         # (the key lives on the path itself: a path rebuilt for another shard has none, whatever address it got)
-        if getattr(path, "_cal_key", None) == key and hasattr(path, "_cal"):  # same path, same scalars: the tables are on the device already
+        if path._cal_key == key and path._cal is not None:  # same path, same scalars: the tables are on the device already
             return
         path._cal_key = key
         sp = atm.spectrum
