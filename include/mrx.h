@@ -132,7 +132,11 @@ enum {
                                  once the chunks it needs are in, before it loads them -- the hand-over form that is valid
                                  whatever a CU holds; 0 (default) = write-through stores, drained waves and sc1 loads alone,
                                  measured valid and 2 % faster */
-  MRX_OPT_COUNT = 14
+  MRX_OPT_WRITER_GENERAL = 14, /* mrx_spline_upsample_fused / mrx_atm_synthesize: 1 = the writer's row loop reads a row's
+                                  coefficients once per SAMPLE everywhere; 0 (default) = once per thread and row in every
+                                  wave whose threads' four samples each lie in one knot interval.  Same bits either way:
+                                  the A/B switch and the tests' reference */
+  MRX_OPT_COUNT = 15
 };
 int mrx_set_option(mrx_ctx* ctx, int option, int value);
 const char* mrx_last_error(const mrx_ctx* ctx);

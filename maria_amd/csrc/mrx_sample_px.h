@@ -227,6 +227,42 @@ struct PxNoHooks {
   __device__ __forceinline__ void done(int) {}
 };
 
+// The band tables into LDS, by the whole workgroup: 16-byte loads, kFly of a thread in flight before the first is
+// waited for (one load, its wait, one LDS write at a time was nine dependent round trips for atlast_10k's 2 112 floats:
+// now one), the last table_floats mod 4 floats singly, in the same round.  Both ends are 16-byte aligned (the plan's
+// buffer is its own allocation; the callers' LDS layouts keep the tables behind whole float4s).  The caller's next
+// barrier publishes them.
+__device__ __forceinline__ void stage_tables(float* lds_tables, const float* __restrict__ table_data, int table_floats) {
+  constexpr int kFly = 4;
+  const int n4 = table_floats >> 2;
+  const float4* __restrict__ src = reinterpret_cast<const float4*>(table_data);
+  float4* dst = reinterpret_cast<float4*>(lds_tables);
+  if (table_floats <= 0) return;
+  const int rest = min((n4 << 2) + (int)(threadIdx.x & 3), table_floats - 1);  // (every lane: one of the last floats)
+  const float last = table_data[rest];
+  for (int i0 = threadIdx.x; i0 < n4; i0 += kPxBlock * kFly) {
+    // (a lane past the end copies the last float4 again -- the same value to the same place -- so that the body has
+    // no branch: behind a condition each load was sunk to its write, with a wait of its own)
+    float4 v[kFly];
+    int i[kFly];
+#pragma unroll
+    for (int u = 0; u < kFly; ++u) {
+      i[u] = min(i0 + u * kPxBlock, n4 - 1);
+      v[u] = src[i[u]];
+    }
+    // (the empty asm wants all of them in registers at once: left alone, the scheduler of a kernel at its register
+    // bound runs them through ONE quad of registers, load - wait - write four times over)
+    static_assert(kFly == 4, "the asm below names four float4s");
+    asm volatile("" : "+v"(v[0].x), "+v"(v[0].y), "+v"(v[0].z), "+v"(v[0].w), "+v"(v[1].x), "+v"(v[1].y), "+v"(v[1].z), "+v"(v[1].w),
+                      "+v"(v[2].x), "+v"(v[2].y), "+v"(v[2].z), "+v"(v[2].w), "+v"(v[3].x), "+v"(v[3].y), "+v"(v[3].z), "+v"(v[3].w));
+#pragma unroll
+    for (int u = 0; u < kFly; ++u) dst[i[u]] = v[u];
+  }
+  lds_tables[rest] = last;
+}
+
+// `tables_staged` (workgroup-uniform): the band tables of an earlier call are still in this workgroup's LDS -- the
+// one-launch synthesis calls once per work item and stages only after something else has used the LDS.
 template <bool kLdsTables, int kT, bool kPipe, bool kWriteThrough, typename Hooks>
 __device__ __forceinline__ void px_sample_items(
     const mrx_layer_fast* __restrict__ fast, const mrx_layer_px* __restrict__ lpx, int n_layers,
@@ -235,7 +271,8 @@ __device__ __forceinline__ void px_sample_items(
     const float* __restrict__ el, int Ta, const float* __restrict__ dxs_all, const float* __restrict__ dys_all,
     const int32_t* __restrict__ band_all, const float* __restrict__ mueller00_all, int D_all, double pwv0,
     double* __restrict__ pwv_out_all, float* __restrict__ loading_all, uint32_t* __restrict__ flags, int chunk,
-    int nby, int block_rows, int n_blocks, int blk_begin, int blk_end, int wg, int n_wgs, float4* lds_px, Hooks& hooks) {
+    int nby, int block_rows, int n_blocks, int blk_begin, int blk_end, int wg, int n_wgs, float4* lds_px, Hooks& hooks,
+    bool tables_staged = false) {
   // [chunk * n_layers anchors of 32 bytes: (fraction e, fraction c, middle e, middle c), byte offset of the anchor's
   //  cell, padding][band tables]
   __shared__ float4 bore[kMaxChunk];   // per step: cos/sin of (el - pi/2), cos/sin of az
@@ -245,8 +282,7 @@ __device__ __forceinline__ void px_sample_items(
   // kWriteThrough: [4 steps][64 lanes] floats per wave, behind the tables (16-byte aligned: table_floats rounded up)
   float* turn = lds_tables + (kLdsTables ? (table_floats + 3) / 4 * 4 : 0) + (threadIdx.x / 64) * 256;
   static_assert(!kWriteThrough || kT == 1 || kT == 2 || kT == 4, "the write-through form turns four steps: kT must divide 4");
-  if (kLdsTables)
-    for (int i = threadIdx.x; i < table_floats; i += kPxBlock) lds_tables[i] = table_data[i];
+  if (kLdsTables && !tables_staged) stage_tables(lds_tables, table_data, table_floats);
   const float* __restrict__ tdata = kLdsTables ? lds_tables : table_data;
   uint32_t myflags = 0u;
 
@@ -289,6 +325,21 @@ __device__ __forceinline__ void px_sample_items(
         __builtin_amdgcn_make_buffer_rsrc((void*)loading, 0, kWriteThrough ? Ta * pitch * 4 : 0, 0x00020000);
     const int t_first = by * chunk;
     uint32_t iflags = 0u;
+    // the synthesis role loads the detector's own inputs first: in flight while the boresight terms and the anchors are
+    // made (they were four loads and a dependent 48-byte gather between the anchors and the barrier that ends the prologue)
+    float dx, dy, m00;
+    int b;
+    mrx_table_dev tb;
+    auto load_detector = [&]() {
+      const int dd = min(bx * kPxBlock + (int)threadIdx.x, D - 1);  // (the lane's row, as below: a valid address past the end)
+      dx = dxs[dd];
+      dy = dys[dd];
+      b = band[dd];
+      m00 = mueller00[dd];
+      tb = tables[min(max(b, 0), n_tables - 1)];
+    };
+    // (the stand-alone kernel keeps them behind the anchors: its global-table instances spill a register more otherwise)
+    if (kWriteThrough) load_detector();
     __syncthreads();  // the previous item's readers of bore[] and anchor[] are done
     if ((int)threadIdx.x < chunk) {
       const int t = min(t_first + (int)threadIdx.x, Ta - 1);
@@ -320,17 +371,14 @@ __device__ __forceinline__ void px_sample_items(
     const bool live = d < D;
     const int dd = live ? d : D - 1;  // keep addresses valid; stores are masked
     hooks.item(blk, (int)row0 + dd);
+    if (!kWriteThrough) load_detector();
     // ---- per-detector constants (coords/transforms.py:14-23), float32 ------
-    const float dx = dxs[dd], dy = dys[dd];
     const float r = sqrtf(dx * dx + dy * dy);
     const float p = atan2f(-dx, -dy);
     const float sr = sinf(r), cr = cosf(r);
     const float A = sr * cosf(p);  // sin(r) cos(p): real part before the tilt
     const float Y = sr * sinf(p);  // sin(r) sin(p)
-    const int b = band[dd];
-    const float m00 = mueller00[dd];
     if (live && (b < 0 || b >= n_tables)) iflags |= MRX_FLAG_NAN;
-    const mrx_table_dev tb = tables[min(max(b, 0), n_tables - 1)];
     __syncthreads();  // anchors are in place
 
     for (int it = 0; it < chunk && t_first + it < Ta; it += kT) {

@@ -292,12 +292,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MRX_WRIT
     const float* __restrict__ y, int D, int n, double ta0, double inv_dta,
     const double* __restrict__ t, int T, const float* __restrict__ scale,
     const int32_t* __restrict__ rows, float* __restrict__ out, size_t ld,
-    int vec_ok, int batches, int nsx, int total, int* ctl) {
+    int vec_ok, int general, int batches, int nsx, int total, int* ctl) {
   // dynamic LDS (FusedLds<...>::kBytes): with a static size the compiler derives the occupancy
   // from it and ignores the register bound above
   extern __shared__ __align__(16) unsigned char fused_lds[];
   if (!kQueue) {  // one workgroup per tile, a two-dimensional grid (time tiles x row groups): MRX_OPT_WRITER_PER_TILE
-    fused_writer_tile<kHasScale, kMaxKnots, kG>(y, D, D, n, ta0, inv_dta, t, T, scale, rows, out, ld, vec_ok, batches,
+    fused_writer_tile<kHasScale, kMaxKnots, kG>(y, D, D, n, ta0, inv_dta, t, T, scale, rows, out, ld, vec_ok, general, batches,
                                                  (int)blockIdx.x, (int)blockIdx.y, fused_lds);
     return;
   }
@@ -308,7 +308,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MRX_WRIT
     const int tile = s_next;
     if (tile >= total) break;
     const int by = tile / nsx;
-    fused_writer_tile<kHasScale, kMaxKnots, kG>(y, D, D, n, ta0, inv_dta, t, T, scale, rows, out, ld, vec_ok, batches,
+    fused_writer_tile<kHasScale, kMaxKnots, kG>(y, D, D, n, ta0, inv_dta, t, T, scale, rows, out, ld, vec_ok, general, batches,
                                                  tile - by * nsx, by, fused_lds);
   }
   synth_leave(ctl, 0);
@@ -452,7 +452,7 @@ int mrx_spline_upsample_fused(mrx_ctx* ctx, const float* d_y, int D, int Ta,
 #define MRX_LAUNCH_UPF_Q(S, K, G, Q)                                                 \
   hipLaunchKernelGGL((spline_upsample_fused_kernel<S, K, G, Q>), Q ? grid_q : grid_t, dim3(kBlock), (FusedLds<K, G>::kBytes), \
                      ctx->stream, d_y, D, Ta, ta0, 1.0 / dta, d_t, T, d_scale,       \
-                     d_rows, d_out, ld_out, vec_ok, batches, (int)nsx, (int)n_tiles, ctl)
+                     d_rows, d_out, ld_out, vec_ok, ctx->options[MRX_OPT_WRITER_GENERAL] != 0 ? 1 : 0, batches, (int)nsx, (int)n_tiles, ctl)
 #define MRX_LAUNCH_UPF(S, K, G) do { if (per_tile) MRX_LAUNCH_UPF_Q(S, K, G, false); else MRX_LAUNCH_UPF_Q(S, K, G, true); } while (0)
   if (d_scale) {
     if (small) MRX_LAUNCH_UPF(true, kSmallKnots, 2); else MRX_LAUNCH_UPF(true, 256, 1);

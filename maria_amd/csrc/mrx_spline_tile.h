@@ -72,13 +72,13 @@ struct FusedLds {
 // One tile of the fused writer: time tile `sx` (kTileSamples samples), row group `by` (batches x kRows rows of the
 // D rows `y` holds).  The body of spline_upsample_fused_kernel (one tile per workgroup) and of the writer role of
 // atm_tod_kernel (a workgroup takes tiles from a queue); `fused_lds` is the dynamic LDS, FusedLds<...>::kBytes;
-// `ldy` the pitch of y's rows in floats (D in the stand-alone kernel).
+// `ldy` the pitch of y's rows in floats (D in the stand-alone kernel); `general`: MRX_OPT_WRITER_GENERAL (3., the row loop).
 template <bool kHasScale, int kMaxKnots, int kG, bool kHandedOver = false>
 __device__ __forceinline__ void fused_writer_tile(
     const float* __restrict__ y, int ldy, int D, int n, double ta0, double inv_dta,
     const double* __restrict__ t, int T, const float* __restrict__ scale,
     const int32_t* __restrict__ rows, float* __restrict__ out, size_t ld,
-    int vec_ok, int batches, int sx, int by, unsigned char* fused_lds) {
+    int vec_ok, int general, int batches, int sx, int by, unsigned char* fused_lds) {
   constexpr int kRows = kTileDet * kG;
   constexpr int kPitch = kMaxKnots + 1;
   constexpr int kWin = kMaxKnots + 2 * kFHalo + 6;  // raw knots: the image's + (halo + 3) either side
@@ -340,7 +340,24 @@ __device__ __forceinline__ void fused_writer_tile(
           r[q] = min(max(jq[q] - jmin, 0), K - 2);  // in range even if t is unsorted
           u[q] = (float)(x - (double)(jmin + r[q]));
         }
-        if (full) {
+        // A thread's four samples normally lie in ONE interval (an upsampling ratio of 40 with the knots on the sample
+        // grid: no quad of atlast_10k or atlast_50k straddles a knot): where that holds for every lane of the wave, a row
+        // costs the thread one coefficient read instead of four -- the same nest on the same operands, the same bits.
+        // The clamped r of all four is compared (t may be unsorted); `general` (MRX_OPT_WRITER_GENERAL) keeps the
+        // read per sample everywhere: the A/B switch, and the tests' reference.
+        const bool one = r[1] == r[0] && r[2] == r[0] && r[3] == r[0];
+        if (full && !general && __builtin_amdgcn_ballot_w64(!one) == 0) {
+#pragma unroll 4
+          for (int dl = 0; dl < nd; ++dl) {
+            const float4 cf = coef[dl * kCPitch + r[0]];
+            float o[kSamplesPerThread];
+#pragma unroll
+            for (int q = 0; q < kSamplesPerThread; ++q)
+              o[q] = fmaf(u[q], fmaf(u[q], fmaf(u[q], cf.w, cf.z), cf.y), cf.x);
+            const vfloat4 v = {o[0], o[1], o[2], o[3]};
+            __builtin_nontemporal_store(v, reinterpret_cast<vfloat4*>(out_sb + row_off[dl]));
+          }
+        } else if (full) {
 #pragma unroll 4
           for (int dl = 0; dl < nd; ++dl) {
             const float4* row = coef + dl * kCPitch;

@@ -170,7 +170,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MRX_SYNT
     uint32_t* __restrict__ flags, int chunk, int nby, int block_rows, int n_blocks, int n_dedicated,
     double ta0, double inv_dta, const double* __restrict__ t, int T,
     const float* __restrict__ scale, const int32_t* __restrict__ rows, float* __restrict__ out, size_t ld, int vec_ok,
-    int batches, int tile_order, int* ctl, int poll_limit, int acquire, SynthCal cal) {
+    int batches, int tile_order, int* ctl, int poll_limit, int acquire, int general, SynthCal cal) {
   extern __shared__ __align__(16) unsigned char synth_lds[];
   __shared__ int s_word[8];  // what the first wave found out for the workgroup: [0] tile / item, [1] watermark, [2] the tile's last unit, [3..5] its (block, time tile, row group)
   SynthHooks<kKrj> hooks;
@@ -219,6 +219,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MRX_SYNT
   };
   int have = 0;    // hand-over units 0 .. have - 1 are known to be sampled (blocks in order, chunks in order)
   int tries = 0;
+  // The band tables (and the K_RJ cell table) are the same for every item of the launch: they are staged by the first
+  // item after entry or after a tile -- the tile's images lie over them -- and stay for the items that follow it (a
+  // dedicated sampler stages once; staged per item they were nine dependent round trips at the head of each)
+  bool tables_in = false;
   for (;;) {
     __syncthreads();  // everybody is done with the previous turn's LDS: the images, the tables, s_word
     bool take_item = sampling;
@@ -315,8 +319,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MRX_SYNT
         const unsigned long long tt0 = MRX_TRACE_NOW();
         fused_writer_tile<kHasScale, kMaxKnots, kG, MRX_SYNTH_ACQUIRE == 0>(loading + (size_t)Ta * row0, (Db + 31) & ~31, Db, Ta, ta0, inv_dta, t, T,
                                                            kHasScale ? scale + row0 : nullptr, rows ? rows + row0 : nullptr,
-                                                           rows ? out : out + row0 * ld, ld, vec_ok, batches, sx, by, synth_lds);
+                                                           rows ? out : out + row0 * ld, ld, vec_ok, general, batches, sx, by, synth_lds);
         MRX_TRACE(1, tile, tt0);
+        tables_in = false;
         if (++tile == tile_end) tile = -1;
         tries = 0;
         continue;
@@ -340,13 +345,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MRX_SYNT
       const int by = rem / nbx, bx = rem - by * nbx;
       hooks.slot = blk * nby + by;
       const unsigned long long ti0 = MRX_TRACE_NOW();
-      if (kKrj) stage_cal_cells(cells, cal.axis, cal.values, cal.n_el, cal.n_bands);  // (the item starts with a barrier)
+      if (kKrj && !tables_in) stage_cal_cells(cells, cal.axis, cal.values, cal.n_el, cal.n_bands);  // (the item starts with a barrier)
       // px_sample_items walks the items of "workgroup w of W" in its own order -- XCD w mod 8 takes the chunks
       // w mod 8, + 8, ... -- and W = 2^30 makes that walk exactly ONE item long: the one numbered (by, bx)
       mrx_px::px_sample_items<kLdsTables, MRX_SYNTH_KT, MRX_SYNTH_PIPE != 0, true>(
           fast, lpx, n_layers, offpx, tables, n_tables, table_data, table_floats, az, el, Ta, dxs, dys, band, mueller00,
           D, pwv0, pwv_out, loading, flags, chunk, nby, block_rows, n_blocks, blk, blk + 1, ((by >> 3) * nbx + bx) * 8 + (by & 7),
-          1 << 30, reinterpret_cast<float4*>(synth_lds), hooks);
+          1 << 30, reinterpret_cast<float4*>(synth_lds), hooks, tables_in);
+      tables_in = true;
       MRX_TRACE(2, item, ti0);
     }
   }
@@ -487,7 +493,8 @@ static int atm_synthesize(mrx_ctx* ctx, const mrx_atm_plan* plan, const float* d
                        plan->d_table_data, plan->table_floats, d_az, d_el, Ta, d_dx, d_dy, d_band, d_mueller00,   \
                        D, pwv0, d_pwv, d_coarse, d_flags, chunk, nby, block_rows, n_blocks, (int)dedicated, ta0, 1.0 / dta, \
                        d_t, T, d_scale, d_rows, d_out, ld_out, vec_ok, batches, ctx->options[MRX_OPT_SYNTH_TILE_ORDER], ctl, poll_limit,       \
-                       ctx->options[MRX_OPT_SYNTH_ACQUIRE] != 0 ? 1 : 0, cal);                                    \
+                       ctx->options[MRX_OPT_SYNTH_ACQUIRE] != 0 ? 1 : 0,                                          \
+                       ctx->options[MRX_OPT_WRITER_GENERAL] != 0 ? 1 : 0, cal);                                   \
   } while (0)
 #define MRX_LAUNCH_SYNTH_J(L, S, K, G) do { if (krj) MRX_LAUNCH_SYNTH(L, S, K, G, true); else MRX_LAUNCH_SYNTH(L, S, K, G, false); } while (0)
 #define MRX_LAUNCH_SYNTH_S(L, S) do { if (small) MRX_LAUNCH_SYNTH_J(L, S, kSmallKnots, 2); else MRX_LAUNCH_SYNTH_J(L, S, 256, 1); } while (0)
