@@ -872,6 +872,25 @@ int mrx_tod_noise_filter_modes(mrx_ctx* ctx, const float* d_x, size_t ld_x, floa
  * null pointers, D < 1, T < 1, m outside 1 .. 16 or ld_x < T -> MRX_ERR_INVALID with d_a untouched */
 int mrx_tod_mode_project(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, const double* d_U, int m, double* d_a);
 
+/* ---- anti-aliased downsampling of a TOD (maria_amd/downsample.py) ------------------------------------ */
+
+/* y[d][j] = ( sum_i h[H + i] x[d][j q + i] ) / ( sum_i h[H + i] ),   both sums over -H <= i <= H with 0 <= j q + i < T,
+ * H = (n_taps - 1) / 2,  j = 0 .. T_out - 1,  T_out = (T + q - 1) / q.
+ * Products and sums in float64 (x float32, taps float64), the quotient in float64, rounded ONCE to float32.
+ * Output sample j belongs to input time t[j q] (zero phase for symmetric taps); T_out = len(range(0, T, q)).
+ * Orientation: a CORRELATION, h's index grows along the sample index (d_taps[0] meets x[j q - H], d_taps[n_taps - 1]
+ * meets x[j q + H]).  For symmetric taps this is scipy.signal.resample_poly(x, 1, q, window=h) divided by the same call
+ * on a row of ones; for general taps pass window=h[::-1].
+ * Edges: taps that fall outside [0, T) are dropped and the rest renormalised (the denominator above), so a constant row
+ * maps onto itself; where the denominator is 0 the result is whatever the division gives.
+ *  d_x     [D][ld_x] float32, read only
+ *  d_taps  [n_taps] float64
+ *  d_y     [D][ld_y] float32; nothing is written past T_out in a row
+ * No alignment beyond 4 bytes is asked of the pointers or pitches.  q outside 2 .. 32, n_taps even or outside 1 .. 1025,
+ * D < 1, T < 1, ld_x < T, ld_y < T_out, d_y == d_x or a null pointer -> MRX_ERR_INVALID with d_y untouched */
+int mrx_tod_decimate(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, int q,
+                     const double* d_taps, int n_taps, float* d_y, size_t ld_y);
+
 /* ---- TOD pre-processing for the mappers (tod/processing.py:91-204) --------------------- */
 
 /* remove_slope (D -= linspace(D[:, 0], D[:, -1], T), processing.py:99-105) and / or window

@@ -197,6 +197,45 @@ class TOD:
         f, p = self.psd(nperseg=nperseg, field=field, ctx=ctx, device=device)
         return fit_noise(f, p, f_min=f_min, f_max=f_max, n_bins=n_bins)
 
+    def downsample(self, q, taps=None, ctx=None, device="cuda:0"):
+        """A new TOD at 1 / q of the sample rate (q = 2 .. 32): every field low-passed and decimated on the device by
+        maria_amd.downsample.decimate (``taps`` None: scipy.signal.decimate's FIR for q), one field at a time, into
+        float32 device tensors; the boresight picked at every q-th sample (it is smooth, and picking keeps azimuth wraps
+        out of the filter), output sample j at time t[j q].  ``dets``, ``units`` and ``metadata`` are carried over and
+        ``metadata["downsample"]`` records the factor, the tap count and the new sample rate.  The pW <-> K_RJ
+        calibrator is NOT carried over (it closes over full-rate tables): ``to()`` on the result raises
+        NotImplementedError, so convert units first.  This TOD is left as it is."""
+        import torch
+
+        from ._lib import Context
+        from .downsample import MAX_FACTOR, MIN_FACTOR, decimate, design_taps, upload_taps
+
+        if int(q) != q or not MIN_FACTOR <= int(q) <= MAX_FACTOR:
+            raise ValueError(f"q {q}: an integer in {MIN_FACTOR} .. {MAX_FACTOR}")
+        q = int(q)
+        h = design_taps(q) if taps is None else np.ascontiguousarray(
+            taps.detach().cpu().numpy() if isinstance(taps, torch.Tensor) else taps, np.float64)
+        data, d_taps = {}, {}  # the taps go to a device once, and one context serves every field
+        for name, v in self.data.items():
+            v = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
+            dev = v.device if v.is_cuda else torch.device(device)
+            x = v.to(dev, torch.float32)
+            if x.dim() == 2 and x.shape[1] > 1 and x.stride(1) != 1:
+                x = x.contiguous()
+            if ctx is None:
+                ctx = Context(dev.index or 0)
+                ctx.set_stream(torch.cuda.current_stream(dev))
+            if dev not in d_taps:
+                d_taps[dev] = upload_taps(h, dev)
+            data[name] = decimate(x, q, taps=h, ctx=ctx, device_taps=d_taps[dev])
+        c = self.coords
+        t = np.asarray(c.t, float)
+        coords = Coordinates(t[::q], c._baz[::q], c._bel[::q], offsets=c.offsets)
+        metadata = dict(self.metadata)
+        rate = (t.size - 1) / (t[-1] - t[0]) / q if t.size > 1 else float("nan")
+        metadata["downsample"] = {"factor": q, "n_taps": int(h.size), "sample_rate": float(rate)}
+        return TOD(data=data, dets=self.dets, coords=coords, units=self.units, metadata=metadata)
+
     def to(self, units):
         """tod/tod.py:106-142 between "pW" and "K_RJ" (``mrx_tod_to_krj`` / ``mrx_tod_from_krj`` on
         every field), for a TOD that came out of ``Simulation.run``; other units stay with maria's
