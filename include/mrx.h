@@ -891,6 +891,46 @@ int mrx_tod_mode_project(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int
 int mrx_tod_decimate(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, int q,
                      const double* d_taps, int n_taps, float* d_y, size_t ld_y);
 
+/* ---- glitch flags and gap filling of a TOD (maria_amd/flagging.py) ----------------------------------- */
+
+/* r[d][t] = x[d][t] - med[d][t], one float32 subtraction, where med[d][t] is the median of the 2 h + 1 values
+ * x[d][clamp(t + i, 0, T - 1)], -h <= i <= h, h = half_window: scipy.ndimage.median_filter(x, size=(1, 2 h + 1),
+ * mode="nearest").  The median is a selection, so r is reproducible bit for bit.  Inputs must be finite: the result on
+ * NaN or inf is unspecified.
+ *  d_x  [D][ld_x] float32, read only
+ *  d_r  [D][ld_r] float32; nothing is written past T in a row
+ * No alignment beyond 4 bytes is asked of the pointers or pitches.  half_window outside 1 .. 15, D < 1, T < 1, a pitch < T,
+ * d_r == d_x or a null pointer -> MRX_ERR_INVALID with d_r untouched */
+int mrx_tod_median_residual(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, int half_window,
+                            float* d_r, size_t ld_r);
+
+/* Glitch flags of a TOD from the residual above.  Sample s of row d is a DETECTION if |r[d][s]| > d_thresh[d] (strict;
+ * a NaN threshold detects nothing, a negative one every sample).  flags[d][t] = 1 where t is a detection, else 2 where
+ * some detection s has t - grow_after <= s <= t + grow_before (a detection flags grow_before samples before itself and
+ * grow_after samples after itself, clipped to the row), else 0.  Every byte of [0, T) of every row is written.
+ *  d_thresh  [D] float32
+ *  d_flags   [D][ld_f] uint8; no alignment is asked (4-byte stores where pointer and pitch allow them, bytes otherwise)
+ *  d_count   [D] uint32 number of nonzero flags of each row, OVERWRITTEN (one integer atomic a tile), or NULL
+ * mrx_tod_median_residual's refusals on x, ld_f < T, a grow_* outside 0 .. 64 or a null d_thresh or d_flags ->
+ * MRX_ERR_INVALID with d_flags and d_count untouched */
+int mrx_tod_glitch_flag(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, int half_window,
+                        const float* d_thresh, int grow_before, int grow_after,
+                        uint8_t* d_flags, size_t ld_f, uint32_t* d_count);
+
+/* Fill the flagged samples of a TOD in place.  For every maximal run [a, b) of nonzero flags of a row: L = the unflagged
+ * indices of [max(0, a - n_fit), a), R = those of [b, min(T, b + n_fit)); (tL, yL), (tR, yR) the float64 means of the
+ * indices and samples of L and R;  x[d][t] = yL + (yR - yL) (t - tL) / (tR - tL) for a <= t < b, in float64, rounded ONCE
+ * to float32.  A run that starts at 0 gets yR, one that ends at T gets yL, a row flagged from end to end is left as it
+ * is.  Only flagged samples are written and only unflagged ones are read.  No noise realisation is added.
+ * One thread fills a run: meant for sparse flags; correct, and bounded by T, for any run length.
+ *  d_x       [D][ld_x] float32, in place
+ *  d_flags   [D][ld_f] uint8, read only
+ *  d_filled  [D] uint32 number of samples written in each row, OVERWRITTEN, or NULL
+ * n_fit outside 1 .. 16, D < 1, T < 1, a pitch < T or a null d_x or d_flags -> MRX_ERR_INVALID with d_x and d_filled
+ * untouched */
+int mrx_tod_gap_fill(mrx_ctx* ctx, float* d_x, size_t ld_x, int D, int T, const uint8_t* d_flags, size_t ld_f,
+                     int n_fit, uint32_t* d_filled);
+
 /* ---- TOD pre-processing for the mappers (tod/processing.py:91-204) --------------------- */
 
 /* remove_slope (D -= linspace(D[:, 0], D[:, -1], T), processing.py:99-105) and / or window

@@ -125,6 +125,7 @@ class _GridMapper:
 
     def _tod_inputs(self, tod, ctx, unit_i_response=False, with_operator=False):
         """The ``TodInputs`` (signal, weight, az, el, transform, dx, dy, stokes_w, channel) of one TOD; weight None for ones.
+        The weight is the pre-processing's window times ``tod.flags == 0`` where the TOD has flags.
         ``unit_i_response``: the Stokes weights over the detector's I weight (its Mueller [0, 0]).  ``with_operator``:
         ``(TodInputs, op)``, op the pre-processing as a ``tod_processing.PreprocessOperator`` (no steps: the identity)."""
         from .sim import sky_transform_stack
@@ -151,6 +152,9 @@ class _GridMapper:
                 f = f.to(dev, torch.float32)
                 signal = f.clone() if signal is None else signal.add_(f)
             signal = signal.contiguous()
+        if getattr(tod, "flags", None) is not None:  # flagged samples get no weight (TOD.flag_glitches)
+            good = (torch.as_tensor(tod.flags).to(dev) == 0).to(torch.float32)
+            weight = good if weight is None else weight * good
         transform = None
         if self.frame == "ra/dec":
             transform = torch.as_tensor(sky_transform_stack(coords.t, tod.metadata["latitude"], tod.metadata["longitude"]).reshape(-1, 9)).to(dev)

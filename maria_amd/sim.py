@@ -154,11 +154,13 @@ class Observation:
 
 class TOD:
     """The slice of ``maria.tod.TOD`` this path fills: ``data`` (dict of [ndet, nt]
-    float32 arrays, numpy or device tensors), ``dets``, ``coords``, ``units``, ``metadata``."""
+    float32 arrays, numpy or device tensors), ``dets``, ``coords``, ``units``, ``metadata``.  ``flags``: None, or a
+    [ndet, nt] uint8 device tensor whose nonzero entries mark samples the mappers give no weight (``flag_glitches``)."""
 
-    def __init__(self, data, dets, coords, units="pW", metadata=None):
+    def __init__(self, data, dets, coords, units="pW", metadata=None, flags=None):
         self.data, self.dets, self.coords, self.units = data, dets, coords, units
         self.metadata = metadata or {}
+        self.flags = flags
 
     @property
     def fields(self):
@@ -204,7 +206,8 @@ class TOD:
         out of the filter), output sample j at time t[j q].  ``dets``, ``units`` and ``metadata`` are carried over and
         ``metadata["downsample"]`` records the factor, the tap count and the new sample rate.  The pW <-> K_RJ
         calibrator is NOT carried over (it closes over full-rate tables): ``to()`` on the result raises
-        NotImplementedError, so convert units first.  This TOD is left as it is."""
+        NotImplementedError, so convert units first.  ``flags`` become ``flagging.downsample_flags(flags, q)``: an output is
+        flagged if any input within q samples of it is.  This TOD is left as it is."""
         import torch
 
         from ._lib import Context
@@ -234,7 +237,53 @@ class TOD:
         metadata = dict(self.metadata)
         rate = (t.size - 1) / (t[-1] - t[0]) / q if t.size > 1 else float("nan")
         metadata["downsample"] = {"factor": q, "n_taps": int(h.size), "sample_rate": float(rate)}
-        return TOD(data=data, dets=self.dets, coords=coords, units=self.units, metadata=metadata)
+        flags = None
+        if self.flags is not None:
+            from .flagging import downsample_flags
+
+            flags = downsample_flags(self.flags, q)
+        return TOD(data=data, dets=self.dets, coords=coords, units=self.units, metadata=metadata, flags=flags)
+
+    def flag_glitches(self, n_sigma=6.0, half_window=5, grow=(2, 8), n_fit=4, fill=True, ctx=None, device="cuda:0"):
+        """A new TOD with glitches flagged and, with ``fill``, filled (maria_amd.flagging).  Glitches are
+        detected on the signal (the sum of the fields): samples further than ``n_sigma`` robust sigmas from the running
+        median of 2 * half_window + 1 samples, grown by ``grow = (before, after)`` samples, ORed into any ``flags`` this
+        TOD already has.  Every field of the result is a float32 device copy whose flagged samples are replaced by the
+        line between the means of the ``n_fit`` unflagged samples either side (no noise is added), so that the
+        pre-processing filters do not ring; ``flags`` is the [D, T] uint8 device tensor the mappers take as zero weight, and
+        ``metadata["glitches"]`` records the parameters, ``flagged_fraction`` and the per-row ``counts``.  ``dets``,
+        ``coords``, ``units`` and the pW <-> K_RJ calibrator are carried over.  This TOD is left as it is."""
+        import torch
+
+        from ._lib import Context
+        from .flagging import find_glitches, gap_fill
+
+        data, signal, dev = {}, None, None
+        for name, v in self.data.items():
+            v = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
+            if dev is None:  # the first field's device (a host field: ``device``) takes them all
+                dev = v.device if v.is_cuda else torch.device(device)
+            data[name] = v.to(dev, torch.float32, copy=True).contiguous()
+            signal = data[name].clone() if signal is None else signal.add_(data[name])
+        if ctx is None:
+            ctx = Context(dev.index or 0)
+            ctx.set_stream(torch.cuda.current_stream(dev))
+        flags, count = find_glitches(signal, n_sigma=n_sigma, half_window=half_window, grow=grow, ctx=ctx)
+        del signal
+        if self.flags is not None:
+            flags |= torch.as_tensor(self.flags).to(dev, torch.uint8)
+            count = (flags != 0).sum(dim=1)
+        if fill:
+            for x in data.values():
+                gap_fill(x, flags, n_fit=n_fit, ctx=ctx)
+        metadata = dict(self.metadata)
+        counts = count.cpu().numpy().astype(np.int64)
+        metadata["glitches"] = {"n_sigma": float(n_sigma), "half_window": int(half_window), "grow": (int(grow[0]), int(grow[1])),
+                                "n_fit": int(n_fit), "fill": bool(fill), "flagged_fraction": float(counts.sum() / flags.numel()),
+                                "counts": counts}
+        out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=flags)
+        out._calibrator = getattr(self, "_calibrator", None)
+        return out
 
     def to(self, units):
         """tod/tod.py:106-142 between "pW" and "K_RJ" (``mrx_tod_to_krj`` / ``mrx_tod_from_krj`` on
@@ -247,7 +296,7 @@ class TOD:
                 f"conversion {self.units} -> {units}: only pW <-> K_RJ of a TOD made by Simulation.run() is built"
             )
         out = TOD(data=self._calibrator(self.data, to_krj=(units == "K_RJ")), dets=self.dets, coords=self.coords, units=units,
-                  metadata=self.metadata)
+                  metadata=self.metadata, flags=self.flags)
         out._calibrator = self._calibrator
         return out
 
