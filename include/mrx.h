@@ -931,6 +931,47 @@ int mrx_tod_glitch_flag(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int 
 int mrx_tod_gap_fill(mrx_ctx* ctx, float* d_x, size_t ld_x, int D, int T, const uint8_t* d_flags, size_t ld_f,
                      int n_fit, uint32_t* d_filled);
 
+/* ---- templates synchronous with a per-sample key: ground pickup in azimuth bins (maria_amd/ground.py) - */
+
+/* For row d and bin k, with kept(d, k) = the indices t of bin k with 0 <= t < T and flags[d][t] == 0 (all of them when
+ * d_flags is NULL):
+ *   hits[d][k]     = |kept(d, k)|
+ *   sum[d][k]      = sum over kept(d, k) of ((double)x[d][t] - (double)model[d][t])      (no model term when d_model is NULL)
+ *   template[d][k] = hits >= max(min_hits, 1) ? (float)(sum / (double)hits) : 0.0f       (float64 quotient, rounded ONCE)
+ * The bins are lists shared by every row: bin k owns the sample indices d_order[d_start[k] .. d_start[k + 1]); a sample
+ * in no bin is absent from d_order.  The sums are float64 and REPRODUCIBLE: the order of the additions is a function of
+ * the bin's list alone (no atomics), so the same inputs give the same bits on every call, and a row's result does not
+ * depend on which other rows share the call.
+ *  d_x         [D][ld_x] float32, read only
+ *  d_model     [D][ld_m] float32, read only, or NULL
+ *  d_flags     [D][ld_f] uint8, read only, or NULL; a nonzero flag keeps the sample out
+ *  d_order     [n_order] int32 sample indices, bin after bin
+ *  d_start     [K + 1] int32, non-decreasing from 0 to n_order
+ *  d_sum       [D][K] float64, OVERWRITTEN, or NULL
+ *  d_hits      [D][K] uint32, OVERWRITTEN, or NULL
+ *  d_template  [D][K] float32, OVERWRITTEN, or NULL
+ * An entry of d_order outside [0, T) is skipped (an unsigned comparison; nothing is read through it), and the bounds
+ * read from d_start are clamped into [0, n_order]: bad lists give wrong sums, never an access outside the arrays.  No
+ * alignment beyond the element size is asked of the pointers or pitches.  D < 1, T < 1, K outside 1 .. 4096, n_order
+ * outside 0 .. T, min_hits < 0, a pitch (of an array that is given) < T, a null d_x, d_order or d_start, or all three
+ * outputs null -> MRX_ERR_INVALID with the outputs untouched */
+int mrx_tod_bin_reduce(mrx_ctx* ctx, const float* d_x, size_t ld_x, const float* d_model, size_t ld_m,
+                       const uint8_t* d_flags, size_t ld_f, int D, int T,
+                       const int32_t* d_order, int n_order, const int32_t* d_start, int K, int min_hits,
+                       double* d_sum, uint32_t* d_hits, float* d_template);
+
+/* y[d][t] = x[d][t] + sign * template[d][d_bin[t]], sign = -1 or +1: one float32 subtraction or addition.  Where d_bin[t]
+ * is outside 0 .. K - 1 (by convention -1) y[d][t] = x[d][t]: an unsigned comparison, and no template entry is read.
+ *  d_x         [D][ld_x] float32
+ *  d_bin       [T] int32, shared by every row
+ *  d_template  [D][K] float32
+ *  d_y         [D][ld_y] float32; d_y == d_x (with ld_y == ld_x) works in place; nothing is written past T in a row
+ * 16-byte accesses where d_x, d_y, d_bin and both pitches allow them, 4-byte ones otherwise: no alignment beyond 4 bytes
+ * is asked.  D < 1, T < 1, K outside 1 .. 4096, sign not -1 or +1, ld_x < T, ld_y < T or a null pointer ->
+ * MRX_ERR_INVALID with d_y untouched */
+int mrx_tod_bin_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, const int32_t* d_bin,
+                      const float* d_template, int K, int sign, float* d_y, size_t ld_y);
+
 /* ---- TOD pre-processing for the mappers (tod/processing.py:91-204) --------------------- */
 
 /* remove_slope (D -= linspace(D[:, 0], D[:, -1], T), processing.py:99-105) and / or window

@@ -285,6 +285,71 @@ class TOD:
         out._calibrator = getattr(self, "_calibrator", None)
         return out
 
+    def remove_ground(self, n_bins=64, bins=None, model=None, shared=False, min_hits=8, into=None, ctx=None, device="cuda:0"):
+        """A new TOD with the scan-synchronous ground pickup removed (maria_amd.ground): per detector, the mean
+        of the signal (the sum of the fields) in each of ``n_bins`` uniform bins of the boresight azimuth
+        (``ground.azimuth_bins``), subtracted from every sample of the bin.  ``model``: a [D, T] array or tensor of the
+        expected sky signal (a previous map sampled back through ``Simulation(map=...)``, or a field of this TOD), taken
+        off the signal before the means are formed, so that the subtraction does not eat the sky; without it the template
+        holds the sky's own mean in every bin.  Samples with nonzero ``flags`` take no part in the means, and are
+        subtracted from like the rest.  ``bins``: any int32 [T] key in -1 .. n_bins - 1 in place of the azimuth bins
+        (-1: the sample is left as it is).  ``shared``: one template for all detectors (``ground.shared_template``).
+        A (detector, bin) pair with fewer than ``min_hits`` samples gets no template and its samples stay as they are.
+        Every field of the result is a float32 device copy; the template is subtracted from the field ``into`` (default:
+        the first), the mappers bin the sum.  ``flags``, ``dets``, ``coords``, ``units`` and the pW <-> K_RJ calibrator
+        are carried over; ``metadata["ground"]`` records ``n_bins``, ``lo``, ``hi`` (None with ``bins``), ``min_hits``,
+        ``shared``, ``empty_bins`` (the (detector, bin) pairs without a template) and the [D, n_bins] float32
+        ``template``.  This TOD is left as it is."""
+        import torch
+
+        from . import ground
+        from ._lib import Context
+
+        n_bins = ground._check_n_bins(n_bins)
+        T = int(np.asarray(self.coords.t).size)
+        lo = hi = None
+        if bins is None:
+            bins, lo, hi = ground.azimuth_bins(self.coords._baz, n_bins)
+        bins = ground._check_bins(bins, n_bins, T)
+        if int(min_hits) != min_hits or int(min_hits) < 0:
+            raise ValueError(f"min_hits {min_hits}: an integer >= 0")
+        into = self.fields[0] if into is None else into
+        if into not in self.data:
+            raise ValueError(f"into {into!r}: one of the fields {self.fields}")
+        data, signal, dev = {}, None, None
+        for name, v in self.data.items():
+            v = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
+            if dev is None:  # the first field's device (a host field: ``device``) takes them all
+                dev = v.device if v.is_cuda else torch.device(device)
+            data[name] = v.to(dev, torch.float32, copy=True).contiguous()
+            signal = data[name].clone() if signal is None else signal.add_(data[name])
+        if tuple(signal.shape) != (signal.shape[0], T):
+            raise ValueError(f"fields of shape {tuple(signal.shape)}: the coordinates have {T} samples")
+        if model is not None:
+            model = model if isinstance(model, torch.Tensor) else torch.as_tensor(np.asarray(model))
+            if tuple(model.shape) != tuple(signal.shape):
+                raise ValueError(f"model of shape {tuple(model.shape)}: the fields' {tuple(signal.shape)}")
+            model = model.to(dev, torch.float32).contiguous()
+        flags = None if self.flags is None else torch.as_tensor(self.flags).to(dev, torch.uint8).contiguous()
+        if ctx is None:
+            ctx = Context(dev.index or 0)
+            ctx.set_stream(torch.cuda.current_stream(dev))
+        template, hits, sums = ground.bin_template(signal, bins, n_bins, flags=flags, model=model, min_hits=min_hits, ctx=ctx)
+        del signal
+        floor = max(int(min_hits), 1)
+        if shared:
+            template = ground.shared_template(sums, hits, min_hits)
+            empty = int((hits.sum(dim=0) < floor).sum()) * int(hits.shape[0])
+        else:
+            empty = int((hits < floor).sum())
+        ground.apply_template(data[into], bins, template, sign=-1, out=data[into], ctx=ctx)
+        metadata = dict(self.metadata)
+        metadata["ground"] = {"n_bins": n_bins, "lo": lo, "hi": hi, "min_hits": int(min_hits), "shared": bool(shared),
+                              "empty_bins": empty, "template": template.cpu().numpy()}
+        out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=self.flags)
+        out._calibrator = getattr(self, "_calibrator", None)
+        return out
+
     def to(self, units):
         """tod/tod.py:106-142 between "pW" and "K_RJ" (``mrx_tod_to_krj`` / ``mrx_tod_from_krj`` on
         every field), for a TOD that came out of ``Simulation.run``; other units stay with maria's
