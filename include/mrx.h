@@ -972,6 +972,63 @@ int mrx_tod_bin_reduce(mrx_ctx* ctx, const float* d_x, size_t ld_x, const float*
 int mrx_tod_bin_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, const int32_t* d_bin,
                       const float* d_template, int K, int sign, float* d_y, size_t ld_y);
 
+/* ---- the common mode and other shared time templates: a flag-aware regression (maria_amd/regress.py) -- */
+
+/* Common to the three entries below.  G groups, 1 <= G <= 16.  d_group [D] int32 names each row's group, NULL: every row
+ * in group 0; a row whose entry is outside 0 .. G - 1 (by convention -1; an unsigned comparison) takes part in nothing.
+ * d_flags [D][ld_f] uint8 or NULL: a nonzero flag keeps the sample out of SUMS, never out of the subtraction.
+ * d_model [D][ld_m] float32 or NULL.  term(d, t) = (double)x[d][t] - (double)model[d][t], one rounding, plain
+ * (double)x[d][t] when d_model is NULL.  Every operation written below is one float64 rounding (no fused
+ * multiply-add).  The sums are REPRODUCIBLE, without atomics: a sum over rows is added in the ascending row order of the
+ * group, a sum over time in an order that is a function of T alone (not of K, D, the flags, the pointers' alignment or
+ * the other rows of the call), so the same inputs give the same bits on every call.  Inputs are never modified.  No
+ * alignment beyond the element size is asked of any pointer or pitch: a thread's four consecutive samples are one
+ * 16-byte access (flags: 4-byte) where the pointer and the pitch allow it, four accesses otherwise.  Nothing is written
+ * past T in a row. */
+
+/* The weighted mean across the rows of each group, sample by sample.  For group g and sample t, over the rows d of group
+ * g with flags[d][t] == 0, in ascending d:
+ *   S[g][t]    = sum of u[d] * (term(d, t) - off[d])
+ *   W[g][t]    = sum of v[d]
+ *   mean[g][t] = W > 0 ? (float)(S / W) : 0.0f                      (float64 quotient, rounded ONCE)
+ * Rows of other groups (or of none) do not enter the order: adding such rows to a call leaves a group's bits as they are.
+ *  d_x     [D][ld_x] float32
+ *  d_u, d_v [D] float64;  d_off [D] float64 or NULL (zeros)
+ *  d_S     [G][T] float64, OVERWRITTEN, or NULL
+ *  d_W     [G][T] float64, OVERWRITTEN, or NULL
+ *  d_mean  [G][ld_c] float32, OVERWRITTEN in [0, T) of each row, or NULL
+ * D < 1, T < 1, G outside 1 .. 16, a pitch (of an array that is given) < T, a null d_x, d_u or d_v, or all three outputs
+ * null -> MRX_ERR_INVALID with the outputs untouched */
+int mrx_tod_column_mean(mrx_ctx* ctx, const float* d_x, size_t ld_x, const float* d_model, size_t ld_m,
+                        const uint8_t* d_flags, size_t ld_f, int D, int T, const int32_t* d_group, int G,
+                        const double* d_u, const double* d_v, const double* d_off,
+                        double* d_S, double* d_W, float* d_mean, size_t ld_c);
+
+/* Each row's normal equations against its group's K templates d_B [G][K][ld_b] float32, 1 <= K <= 8.  For row d with
+ * g = group[d] and kept(d) = { t : flags[d][t] == 0 }:
+ *   N[d][i][j] = sum over kept(d) of (double)B[g][i][t] * (double)B[g][j][t]   (the product of two float32 is exact)
+ *   r[d][i]    = sum over kept(d) of (double)B[g][i][t] * term(d, t)           (the product one rounding)
+ *   hits[d]    = |kept(d)|
+ * N is the full symmetric K x K matrix.  A row outside every group gets zeros.  A row's sums do not depend on which
+ * rows share the call.
+ *  d_N     [D][K][K] float64, OVERWRITTEN
+ *  d_r     [D][K] float64, OVERWRITTEN
+ *  d_hits  [D] uint32, OVERWRITTEN, or NULL
+ * D < 1, T < 1, G outside 1 .. 16, K outside 1 .. 8, a pitch (of an array that is given) < T, or a null d_x, d_B, d_N or
+ * d_r -> MRX_ERR_INVALID with the outputs untouched */
+int mrx_tod_regress_normal(mrx_ctx* ctx, const float* d_x, size_t ld_x, const float* d_model, size_t ld_m,
+                           const uint8_t* d_flags, size_t ld_f, int D, int T, const int32_t* d_group, int G,
+                           const float* d_B, size_t ld_b, int K, double* d_N, double* d_r, uint32_t* d_hits);
+
+/* Subtract (sign -1) or add (sign +1) each row's fitted combination of its group's templates, d_a [D][K] float64:
+ *   s = 0.0; for i = 0 .. K - 1: s = s + a[d][i] * (double)B[g][i][t]          (two roundings a step, in this order)
+ *   y[d][t] = x[d][t] + sign * (float)s                                        (one float32 operation)
+ * A row outside every group is copied.  d_y == d_x with ld_y == ld_x works in place.
+ * D < 1, T < 1, G outside 1 .. 16, K outside 1 .. 8, sign not -1 or +1, ld_x, ld_y or ld_b < T, a null d_x, d_B, d_a or
+ * d_y, or d_y == d_x with ld_y != ld_x -> MRX_ERR_INVALID with d_y untouched */
+int mrx_tod_regress_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, const int32_t* d_group, int G,
+                          const float* d_B, size_t ld_b, int K, const double* d_a, int sign, float* d_y, size_t ld_y);
+
 /* ---- TOD pre-processing for the mappers (tod/processing.py:91-204) --------------------- */
 
 /* remove_slope (D -= linspace(D[:, 0], D[:, -1], T), processing.py:99-105) and / or window

@@ -300,10 +300,7 @@ class TOD:
         are carried over; ``metadata["ground"]`` records ``n_bins``, ``lo``, ``hi`` (None with ``bins``), ``min_hits``,
         ``shared``, ``empty_bins`` (the (detector, bin) pairs without a template) and the [D, n_bins] float32
         ``template``.  This TOD is left as it is."""
-        import torch
-
         from . import ground
-        from ._lib import Context
 
         n_bins = ground._check_n_bins(n_bins)
         T = int(np.asarray(self.coords.t).size)
@@ -313,6 +310,31 @@ class TOD:
         bins = ground._check_bins(bins, n_bins, T)
         if int(min_hits) != min_hits or int(min_hits) < 0:
             raise ValueError(f"min_hits {min_hits}: an integer >= 0")
+        data, signal, model, flags, into, ctx = self._device_fields(model, into, ctx, device)
+        template, hits, sums = ground.bin_template(signal, bins, n_bins, flags=flags, model=model, min_hits=min_hits, ctx=ctx)
+        del signal
+        floor = max(int(min_hits), 1)
+        if shared:
+            template = ground.shared_template(sums, hits, min_hits)
+            empty = int((hits.sum(dim=0) < floor).sum()) * int(hits.shape[0])
+        else:
+            empty = int((hits < floor).sum())
+        ground.apply_template(data[into], bins, template, sign=-1, out=data[into], ctx=ctx)
+        metadata = dict(self.metadata)
+        metadata["ground"] = {"n_bins": n_bins, "lo": lo, "hi": hi, "min_hits": int(min_hits), "shared": bool(shared),
+                              "empty_bins": empty, "template": template.cpu().numpy()}
+        out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=self.flags)
+        out._calibrator = getattr(self, "_calibrator", None)
+        return out
+
+    def _device_fields(self, model, into, ctx, device):
+        """(data, signal, model, flags, into, ctx) for ``remove_ground``, ``regress`` and ``remove_common_mode``: float32
+        device copies of the fields, their sum, the model and the flags on the same device."""
+        import torch
+
+        from ._lib import Context
+
+        T = int(np.asarray(self.coords.t).size)
         into = self.fields[0] if into is None else into
         if into not in self.data:
             raise ValueError(f"into {into!r}: one of the fields {self.fields}")
@@ -334,18 +356,88 @@ class TOD:
         if ctx is None:
             ctx = Context(dev.index or 0)
             ctx.set_stream(torch.cuda.current_stream(dev))
-        template, hits, sums = ground.bin_template(signal, bins, n_bins, flags=flags, model=model, min_hits=min_hits, ctx=ctx)
+        return data, signal, model, flags, into, ctx
+
+    def regress(self, templates, model=None, into=None, min_hits=8, rcond=1e-10, ctx=None, device="cuda:0"):
+        """A new TOD with the [K, T] time ``templates`` (K <= 8; float32, shared by all detectors: ``regress.
+        legendre_templates``, ``regress.airmass_template``, anything else) fitted to the signal (the sum of the fields,
+        less ``model``) of every detector by least squares and subtracted from the field ``into`` (default: the first; the
+        mappers bin the sum) (maria_amd.regress).  Samples with nonzero ``flags`` take no part in the fit,
+        and are subtracted from like the rest.  A detector with fewer than max(min_hits, K) samples left, or whose
+        templates are degenerate on them (``regress.solve``), is left as it is.  Every field of the result is a float32
+        device copy; ``flags``, ``dets``, ``coords``, ``units`` and the pW <-> K_RJ calibrator are carried over;
+        ``metadata["regress"]`` records ``n_templates``, ``min_hits``, ``rcond``, the [D, K] float64 ``coefficients`` and
+        ``failed_rows``.  This TOD is left as it is."""
+        import torch
+
+        from . import regress
+
+        min_hits = regress._check_min_hits(min_hits)
+        B = templates if isinstance(templates, torch.Tensor) else torch.as_tensor(np.asarray(templates))
+        T = int(np.asarray(self.coords.t).size)
+        if B.dim() != 2 or B.shape[1] != T or not 1 <= B.shape[0] <= regress.MAX_TEMPLATES:
+            raise ValueError(f"templates must be a [K, {T}] array with K in 1 .. {regress.MAX_TEMPLATES}")
+        data, signal, model, flags, into, ctx = self._device_fields(model, into, ctx, device)
+        B = B.to(signal.device, torch.float32).contiguous()[None]
+        N, r, hits = regress.normal_equations(signal, B, flags=flags, model=model, ctx=ctx)
         del signal
-        floor = max(int(min_hits), 1)
-        if shared:
-            template = ground.shared_template(sums, hits, min_hits)
-            empty = int((hits.sum(dim=0) < floor).sum()) * int(hits.shape[0])
-        else:
-            empty = int((hits < floor).sum())
-        ground.apply_template(data[into], bins, template, sign=-1, out=data[into], ctx=ctx)
+        a, ok = regress.solve(N, r, hits, min_hits=min_hits, rcond=rcond)
+        regress.apply(data[into], B, a, sign=-1, out=data[into], ctx=ctx)
         metadata = dict(self.metadata)
-        metadata["ground"] = {"n_bins": n_bins, "lo": lo, "hi": hi, "min_hits": int(min_hits), "shared": bool(shared),
-                              "empty_bins": empty, "template": template.cpu().numpy()}
+        metadata["regress"] = {"n_templates": int(B.shape[1]), "min_hits": min_hits, "rcond": float(rcond),
+                               "coefficients": a.cpu().numpy(), "failed_rows": np.flatnonzero(~ok.cpu().numpy())}
+        out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=self.flags)
+        out._calibrator = getattr(self, "_calibrator", None)
+        return out
+
+    def remove_common_mode(self, groups="band", n_iter=3, poly_order=0, airmass=False, model=None, into=None, min_hits=8, rcond=1e-10,
+                           ctx=None, device="cuda:0"):
+        """A new TOD with the common mode removed (maria_amd.regress.fit_common_mode): per group of
+        detectors the gain-weighted mean of the signal (the sum of the fields, less ``model``) sample by sample, every
+        detector fitted to [1, common mode, further templates] by least squares, the fit subtracted from the field
+        ``into`` (default: the first), the constant included.  ``groups``: "band" (``dets.band_index``), None (one group)
+        or an integer array, -1 leaving a detector out and as it is (at most 16 groups).  Further templates: the Legendre
+        polynomials P_1 .. P_poly_order of the time axis and, with ``airmass``, 1 / sin(elevation) less its mean.  Mean
+        and fit are iterated ``n_iter`` times, the gains of one fit weighting the next mean.  ``model``: the expected sky
+        signal, kept out of mean and fit.  Samples with nonzero ``flags`` take part in neither and are subtracted from
+        like the rest; a detector that cannot be fitted (``regress.solve``) is left as it is.  Every field of the result
+        is a float32 device copy; ``flags``, ``dets``, ``coords``, ``units`` and the pW <-> K_RJ calibrator are carried
+        over; ``metadata["common_mode"]`` records ``n_groups``, ``n_iter``, ``poly_order``, ``airmass``, ``min_hits``,
+        ``rcond``, the [D] ``gains`` and ``offsets``, the [D, K] ``coefficients``, the [G, T] float32 ``common_mode``
+        and ``failed_rows``.  This TOD is left as it is."""
+        from . import regress
+
+        min_hits = regress._check_min_hits(min_hits)
+        T = int(np.asarray(self.coords.t).size)
+        if isinstance(groups, str):
+            if groups != "band":
+                raise ValueError(f'groups {groups!r}: "band", None or an integer array')
+            groups = np.asarray(self.dets.band_index, np.int32)
+        elif groups is not None:
+            groups = np.asarray(groups)
+            if groups.ndim != 1 or groups.dtype.kind not in "iu" or (groups.size and groups.min() < -1):
+                raise ValueError("groups must be a one-dimensional integer array with entries >= -1")
+            groups = groups.astype(np.int32)
+        G = 1 if groups is None or not groups.size else max(int(groups.max()) + 1, 1)
+        regress._check_count(G, "the number of groups", regress.MAX_GROUPS)
+        if int(poly_order) != poly_order or int(poly_order) < 0 or 2 + int(poly_order) + bool(airmass) > regress.MAX_TEMPLATES:
+            raise ValueError(f"poly_order {poly_order}: an integer >= 0 with 2 + poly_order + airmass <= {regress.MAX_TEMPLATES}")
+        extra = [regress.legendre_templates(T, int(poly_order))[1:]]
+        if airmass:
+            extra.append(regress.airmass_template(self.coords._bel)[None])
+        extra = np.concatenate(extra)
+        data, signal, model, flags, into, ctx = self._device_fields(model, into, ctx, device)
+        c, a, gains, ok, B = regress.fit_common_mode(signal, groups=groups, n_groups=G, flags=flags, model=model,
+                                                     extra=extra if extra.shape[0] else None, n_iter=n_iter, min_hits=min_hits,
+                                                     rcond=rcond, ctx=ctx)
+        del signal
+        regress.apply(data[into], B, a, groups=groups, sign=-1, out=data[into], ctx=ctx)
+        metadata = dict(self.metadata)
+        a_host = a.cpu().numpy()
+        grouped = np.ones(a_host.shape[0], bool) if groups is None else groups >= 0  # a detector left out has not failed
+        metadata["common_mode"] = {"n_groups": G, "n_iter": int(n_iter), "poly_order": int(poly_order), "airmass": bool(airmass),
+                                   "min_hits": min_hits, "rcond": float(rcond), "gains": gains.cpu().numpy(), "offsets": a_host[:, 0].copy(),
+                                   "coefficients": a_host, "common_mode": c.cpu().numpy(), "failed_rows": np.flatnonzero(~ok.cpu().numpy() & grouped)}
         out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=self.flags)
         out._calibrator = getattr(self, "_calibrator", None)
         return out
