@@ -931,6 +931,75 @@ int mrx_tod_glitch_flag(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int 
 int mrx_tod_gap_fill(mrx_ctx* ctx, float* d_x, size_t ld_x, int D, int T, const uint8_t* d_flags, size_t ld_f,
                      int n_fit, uint32_t* d_filled);
 
+/* ---- jumps of a TOD: step statistic, peaks, heights, repair (maria_amd/jumps.py) ----------------------- */
+
+/* Common to the four entries below.  Rows are [D][ld] with unit stride along time; no alignment beyond the element size
+ * is asked of a pointer or pitch (16-byte accesses of float32 rows and 4-byte accesses of flags where pointer and pitch
+ * allow them, narrow ones otherwise), and nothing is written past T in a row.  d_flags [D][ld_f] uint8 or NULL: sample u
+ * of a row is VALID if 0 <= u < T and its flag is 0 (every sample of the row when d_flags is NULL).  Inputs must be
+ * finite: the result on NaN or inf is unspecified.  w = window, g = gap, m = min_count. */
+
+/* The step statistic: the mean after a sample less the mean before it.  For row d and t = 0 .. T - 1:
+ *   L(t) = the valid u of [t - g - w, t - g),   R(t) = the valid u of [t + g, t + g + w)
+ *   s[d][t] = |L| >= m and |R| >= m ? (float)(sum over R of x / |R| - sum over L of x / |L|) : 0.0f
+ * Sums, quotients and the difference are float64, the result is rounded ONCE.  The sums are differences of float64
+ * prefix sums over a tile of 1024 samples and its halo, formed in an order that is a function of T, w and g alone: the
+ * same inputs give the same bits on every call.
+ *  d_x  [D][ld_x] float32, read only
+ *  d_s  [D][ld_s] float32, OVERWRITTEN in [0, T) of each row
+ * window outside 2 .. 256, gap outside 0 .. 64, min_count outside 1 .. window, D < 1, T < 1, a pitch (of an array that
+ * is given) < T, d_s == d_x or a null d_x or d_s -> MRX_ERR_INVALID with d_s untouched */
+int mrx_tod_step_stat(mrx_ctx* ctx, const float* d_x, size_t ld_x, const uint8_t* d_flags, size_t ld_f, int D, int T,
+                      int window, int gap, int min_count, float* d_s, size_t ld_s);
+
+/* The peaks of |s|.  Sample t of row d is a PEAK if
+ *   |s[d][t]| > d_thresh[d]                                   (strict; a NaN threshold finds nothing)
+ *   |s[d][u]| <  |s[d][t]| for every u of [t - sep, t) inside the row
+ *   |s[d][u]| <= |s[d][t]| for every u of (t, t + sep] inside the row
+ * so the earliest sample of a plateau wins and two peaks are always more than sep apart.  flags[d][t] = 1 at a peak,
+ * else 2 where some peak p has t - grow_after <= p <= t + grow_before, else 0.  Every byte of [0, T) of every row is
+ * written.  Comparisons only: reproducible bit for bit.
+ *  d_s       [D][ld_s] float32, read only
+ *  d_thresh  [D] float32
+ *  d_flags   [D][ld_f] uint8
+ *  d_count   [D] uint32 number of PEAKS of each row, OVERWRITTEN (one integer atomic a tile), or NULL
+ * sep outside 1 .. 512, a grow_* outside 0 .. 64, D < 1, T < 1, a pitch < T or a null d_s, d_thresh or d_flags ->
+ * MRX_ERR_INVALID with d_flags and d_count untouched */
+int mrx_tod_jump_find(mrx_ctx* ctx, const float* d_s, size_t ld_s, int D, int T, const float* d_thresh, int sep,
+                      int grow_before, int grow_after, uint8_t* d_flags, size_t ld_f, uint32_t* d_count);
+
+/* The height of each listed jump.  The jumps are listed row after row: row d owns d_pos[d_row_start[d] ..
+ * d_row_start[d + 1]), ascending.  For jump j of row d at p = pos[j], with the row's neighbouring jumps p- = pos[j - 1]
+ * and p+ = pos[j + 1] where they exist:
+ *   lo = max(0, p - g - w, p- + g),   hi = min(T, p + g + w, p+ - g)
+ *   L = the valid u of [lo, p - g),   R = the valid u of [p + g, hi)
+ *   ok[j]     = |L| >= m and |R| >= m
+ *   height[j] = ok ? sum over R of x / |R| - sum over L of x / |L| : 0.0         (float64 throughout)
+ * The windows are clipped so that one jump's estimate never averages across another.  REPRODUCIBLE: the order of the
+ * additions is a function of the list and T alone (no atomics).
+ *  d_x          [D][ld_x] float32, read only
+ *  d_row_start  [D + 1] int32, non-decreasing from 0 to n
+ *  d_pos        [n] int32
+ *  d_height     [n] float64, d_ok [n] uint8: entry j OVERWRITTEN for every j some row owns
+ * An entry of d_pos is clamped into [0, T - 1] and a bound read from d_row_start into [0, n]: bad lists give wrong
+ * heights, never an access outside the arrays.  n = 0 is a valid call that does nothing (d_pos, d_height and d_ok may
+ * then be NULL).  mrx_tod_step_stat's refusals on window, gap, min_count, D, T and the pitches, n < 0, a null d_x or
+ * d_row_start, or with n > 0 a null d_pos, d_height or d_ok -> MRX_ERR_INVALID with the outputs untouched */
+int mrx_tod_jump_height(mrx_ctx* ctx, const float* d_x, size_t ld_x, const uint8_t* d_flags, size_t ld_f, int D, int T,
+                        const int32_t* d_row_start, const int32_t* d_pos, int n, int window, int gap, int min_count,
+                        double* d_height, uint8_t* d_ok);
+
+/* Take the listed jumps out.  With k(t) = the number of jumps of row d with pos <= t (lists as above):
+ *   y[d][t] = k(t) == 0 ? x[d][t] : (float)((double)x[d][t] - cum[row_start[d] + k(t) - 1])
+ * where d_cum [n] float64 is the caller's inclusive cumulative sum of the heights within each row.  One float64
+ * subtraction rounded once: reproducible bit for bit.
+ *  d_y  [D][ld_y] float32; d_y == d_x (with ld_y == ld_x) works in place
+ * The bounds read from d_row_start are clamped into [0, n]; n = 0 copies x (d_pos and d_cum may then be NULL).
+ * D < 1, T < 1, n < 0, ld_x < T, ld_y < T, a null d_x, d_y or d_row_start, with n > 0 a null d_pos or d_cum, or
+ * d_y == d_x with ld_y != ld_x -> MRX_ERR_INVALID with d_y untouched */
+int mrx_tod_jump_fix(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, const int32_t* d_row_start,
+                     const int32_t* d_pos, const double* d_cum, int n, float* d_y, size_t ld_y);
+
 /* ---- templates synchronous with a per-sample key: ground pickup in azimuth bins (maria_amd/ground.py) - */
 
 /* For row d and bin k, with kept(d, k) = the indices t of bin k with 0 <= t < T and flags[d][t] == 0 (all of them when

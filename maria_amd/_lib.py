@@ -229,6 +229,10 @@ SIGNATURES = {
     "mrx_tod_median_residual": (_i, [_vp, _vp, _sz, _i, _i, _i, _vp, _sz]),
     "mrx_tod_glitch_flag": (_i, [_vp, _vp, _sz, _i, _i, _i, _vp, _i, _i, _vp, _sz, _vp]),
     "mrx_tod_gap_fill": (_i, [_vp, _vp, _sz, _i, _i, _vp, _sz, _i, _vp]),
+    "mrx_tod_step_stat": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _i, _i, _i, _vp, _sz]),
+    "mrx_tod_jump_find": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "mrx_tod_jump_height": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "mrx_tod_jump_fix": (_i, [_vp, _vp, _sz, _i, _i, _vp, _vp, _vp, _i, _vp, _sz]),
     "mrx_tod_bin_reduce": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "mrx_tod_bin_apply": (_i, [_vp, _vp, _sz, _i, _i, _vp, _vp, _i, _i, _vp, _sz]),
     "mrx_tod_column_mean": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),

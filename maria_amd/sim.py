@@ -155,7 +155,8 @@ class Observation:
 class TOD:
     """The slice of ``maria.tod.TOD`` this path fills: ``data`` (dict of [ndet, nt]
     float32 arrays, numpy or device tensors), ``dets``, ``coords``, ``units``, ``metadata``.  ``flags``: None, or a
-    [ndet, nt] uint8 device tensor whose nonzero entries mark samples the mappers give no weight (``flag_glitches``)."""
+    [ndet, nt] uint8 device tensor whose nonzero entries mark samples the mappers give no weight (``flag_glitches``,
+    ``fix_jumps``)."""
 
     def __init__(self, data, dets, coords, units="pW", metadata=None, flags=None):
         self.data, self.dets, self.coords, self.units = data, dets, coords, units
@@ -282,6 +283,56 @@ class TOD:
                                 "n_fit": int(n_fit), "fill": bool(fill), "flagged_fraction": float(counts.sum() / flags.numel()),
                                 "counts": counts}
         out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=flags)
+        out._calibrator = getattr(self, "_calibrator", None)
+        return out
+
+    def fix_jumps(self, window=64, n_sigma=8.0, gap=4, sep=None, grow=(4, 4), min_count=None, model=None, into=None, n_fit=4, fill=True,
+                  ctx=None, device="cuda:0"):
+        """A new TOD with the jumps of every detector found, taken out and flagged (maria_amd.jumps).  Jumps
+        are the peaks of the step statistic of the signal (the sum of the fields, less ``model``): the mean of the
+        ``window`` samples after a sample less the mean of those before it, above ``n_sigma`` robust scales of the
+        statistic itself and more than ``sep`` (None: window) samples apart.  Samples with nonzero ``flags`` are kept
+        out of every mean, so run ``flag_glitches`` first: a 40 sigma spike shifts the statistic by 40 sigma / window
+        over window samples.  A jump's height is the same difference of means with the ``gap`` samples either side of
+        it left out and the windows clipped at the neighbouring jumps; the steps are subtracted from the field ``into``
+        (default: the first; the mappers bin the sum).  A jump with fewer than ``min_count`` (None: window // 2) valid
+        samples on a side has no height: it is flagged, counted in ``unfixed`` and left in the data.  The samples within
+        ``grow = (before, after)`` of a jump are ORed into the flags and, with ``fill``, every field is filled over the
+        new flags by ``flagging.gap_fill`` with ``n_fit``.  ``model``: the expected sky signal, or a drift to keep out of
+        the statistic.  Every field of the result is a float32 device copy; ``dets``, ``coords``, ``units`` and the
+        pW <-> K_RJ calibrator are carried over; ``metadata["jumps"]`` records the parameters, the per-row ``counts``,
+        ``positions`` and ``heights`` (a list of arrays, one a row; 0 for an unfixed jump), ``unfixed`` and
+        ``flagged_fraction``.  This TOD is left as it is."""
+        import torch
+
+        from . import jumps
+        from .flagging import MAX_FIT, _check_grow, gap_fill
+
+        w, g, m = jumps._check_window(window, gap, min_count)
+        sep = jumps._check_sep(sep, w)
+        grow = _check_grow(grow)
+        if int(n_fit) != n_fit or not 1 <= int(n_fit) <= MAX_FIT:
+            raise ValueError(f"n_fit {n_fit}: an integer in 1 .. {MAX_FIT}")
+        data, signal, model, flags, into, ctx = self._device_fields(model, into, ctx, device)
+        if model is not None:
+            signal.sub_(model)
+        row_start, pos, jump_flags, count = jumps.find_jumps(signal, window=w, n_sigma=n_sigma, sep=sep, grow=grow, flags=flags,
+                                                             min_count=m, ctx=ctx)
+        height, ok = jumps.jump_heights(signal, row_start, pos, w, g, flags=flags, min_count=m, ctx=ctx)
+        del signal
+        jumps.fix_jumps(data[into], row_start, pos, height, out=data[into], ctx=ctx)
+        if flags is not None:
+            jump_flags |= flags
+        if fill:
+            for x in data.values():
+                gap_fill(x, jump_flags, n_fit=int(n_fit), ctx=ctx)
+        rs, ps, hs = row_start.cpu().numpy(), pos.cpu().numpy().astype(np.int64), height.cpu().numpy()
+        metadata = dict(self.metadata)
+        metadata["jumps"] = {"window": w, "n_sigma": float(n_sigma), "gap": g, "sep": sep, "grow": grow, "min_count": m, "n_fit": int(n_fit),
+                             "fill": bool(fill), "into": into, "counts": count.cpu().numpy().astype(np.int64),
+                             "positions": [ps[a:b] for a, b in zip(rs[:-1], rs[1:])], "heights": [hs[a:b] for a, b in zip(rs[:-1], rs[1:])],
+                             "unfixed": int((~ok).sum()), "flagged_fraction": float((jump_flags != 0).sum()) / jump_flags.numel()}
+        out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=jump_flags)
         out._calibrator = getattr(self, "_calibrator", None)
         return out
 
