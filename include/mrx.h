@@ -1098,6 +1098,46 @@ int mrx_tod_regress_normal(mrx_ctx* ctx, const float* d_x, size_t ld_x, const fl
 int mrx_tod_regress_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, const int32_t* d_group, int G,
                           const float* d_B, size_t ld_b, int K, const double* d_a, int sign, float* d_y, size_t ld_y);
 
+/* ---- the subscan polynomial filter: a Legendre fit per (row, segment) (maria_amd/subscans.py) ---------- */
+
+/* Common to the two entries below.  d_flags, d_model, their pitches, term(d, t), the single float64 roundings (no fused
+ * multiply-add), the absence of atomics, the alignment (none beyond the element size), "nothing is written past T" and
+ * "inputs are never modified" are those of the block above mrx_tod_column_mean.
+ * Segments: d_bound [S + 1] int32 on the device, S >= 1.  Segment s is [lo, hi) with lo = clamp(bound[s], 0, T) and
+ * hi = clamp(bound[s + 1], 0, T); hi <= lo: the segment is empty.  Samples in no segment belong to nothing.  The kernels
+ * clamp, so that no content of d_bound makes them read or write out of range; ascending order is the caller's business
+ * (where segments overlap, mrx_tod_segment_apply gives a sample to one of them).
+ * The basis of a segment of L = hi - lo samples, 1 <= K <= 8:
+ *   u(t)    = L > 1 ? (double)(2 * (t - lo) - (L - 1)) / (double)(L - 1) : 0.0     (integer numerator, one division)
+ *   P_0 = 1.0;  P_1 = u
+ *   P_{n+1} = ((((double)(2n + 1) * u) * P_n) - ((double)n * P_{n-1})) * c_n,   c_n = 1.0 / (double)(n + 1), rounded once */
+
+/* The normal equations of every (row, segment).  For row d, segment s and kept = { t in the segment : flags[d][t] == 0 }:
+ *   N[d][s][i][j] = sum over kept of P_i * P_j                       (the product one rounding; the full symmetric matrix)
+ *   r[d][s][i]    = sum over kept of P_i * term(d, t)
+ *   hits[d][s]    = |kept|
+ * An empty segment gets zeros.  The sums of a (row, segment) are added in an order that is a function of lo and hi alone
+ * (not of K, D, S, the flags, the pitches, the pointers' alignment or what else is in the call): the same inputs give the
+ * same bits on every call, and for a row or a segment computed alone.
+ *  d_x     [D][ld_x] float32
+ *  d_N     [D][S][K][K] float64, OVERWRITTEN
+ *  d_r     [D][S][K] float64, OVERWRITTEN
+ *  d_hits  [D][S] uint32, OVERWRITTEN, or NULL
+ * D < 1, T < 1, S < 1, K outside 1 .. 8, a pitch (of an array that is given) < T, or a null d_x, d_bound, d_N or d_r ->
+ * MRX_ERR_INVALID with the outputs untouched */
+int mrx_tod_segment_normal(mrx_ctx* ctx, const float* d_x, size_t ld_x, const float* d_model, size_t ld_m,
+                           const uint8_t* d_flags, size_t ld_f, int D, int T, const int32_t* d_bound, int S, int K,
+                           double* d_N, double* d_r, uint32_t* d_hits);
+
+/* Subtract (sign -1) or add (sign +1) each segment's polynomial, d_a [D][S][K] float64:
+ *   s = 0.0; for i = 0 .. K - 1: s = s + a[d][seg][i] * P_i(u(t))               (two roundings a step, in this order)
+ *   y[d][t] = x[d][t] + sign * (float)s                                        (one float32 operation)
+ * Samples in no segment are copied.  d_y == d_x with ld_y == ld_x works in place.
+ * D < 1, T < 1, S < 1, K outside 1 .. 8, sign not -1 or +1, ld_x or ld_y < T, a null d_x, d_bound, d_a or d_y, or
+ * d_y == d_x with ld_y != ld_x -> MRX_ERR_INVALID with d_y untouched */
+int mrx_tod_segment_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, const int32_t* d_bound, int S, int K,
+                          const double* d_a, int sign, float* d_y, size_t ld_y);
+
 /* ---- TOD pre-processing for the mappers (tod/processing.py:91-204) --------------------- */
 
 /* remove_slope (D -= linspace(D[:, 0], D[:, -1], T), processing.py:99-105) and / or window

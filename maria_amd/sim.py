@@ -123,6 +123,17 @@ class Plan:
         az, el = daisy_scan(t, radius, speed, scan_center[0], scan_center[1])
         return cls(t, az, el)
 
+    @classmethod
+    def back_and_forth(cls, start_time=0.0, duration=60.0, sample_rate=50.0, scan_center=(45.0, 60.0), throw=2.0, speed=1.0, accel=2.0):
+        """A constant-elevation scan in az/el, degrees: the azimuth sweeps ``scan_center[0]`` -+ ``throw`` at ``speed``
+        (degrees of azimuth a second) and turns round beyond them at ``accel`` (``subscans.back_and_forth``); the elevation
+        stays at ``scan_center[1]``."""
+        from .subscans import back_and_forth
+
+        t = np.arange(start_time, start_time + duration, 1.0 / sample_rate)
+        az = np.radians(scan_center[0] + back_and_forth(t - start_time, throw, speed, accel))
+        return cls(t, az, np.full(t.shape, np.radians(scan_center[1])))
+
     @property
     def duration(self):
         return float(self.time[-1] - self.time[0])
@@ -379,7 +390,7 @@ class TOD:
         return out
 
     def _device_fields(self, model, into, ctx, device):
-        """(data, signal, model, flags, into, ctx) for ``remove_ground``, ``regress`` and ``remove_common_mode``: float32
+        """(data, signal, model, flags, into, ctx) for ``remove_ground``, ``regress``, ``remove_common_mode`` and the like: float32
         device copies of the fields, their sum, the model and the flags on the same device."""
         import torch
 
@@ -490,6 +501,69 @@ class TOD:
                                    "min_hits": min_hits, "rcond": float(rcond), "gains": gains.cpu().numpy(), "offsets": a_host[:, 0].copy(),
                                    "coefficients": a_host, "common_mode": c.cpu().numpy(), "failed_rows": np.flatnonzero(~ok.cpu().numpy() & grouped)}
         out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=self.flags)
+        out._calibrator = getattr(self, "_calibrator", None)
+        return out
+
+    def filter_subscans(self, order=3, bounds=None, turn_frac=0.9, flag_turnarounds=True, flag_failed=True, model=None, into=None,
+                        min_hits=8, rcond=1e-10, ctx=None, device="cuda:0"):
+        """A new TOD with a Legendre polynomial of degree ``order`` (0 .. 7) fitted to every detector's signal (the sum of
+        the fields, less ``model``) in every subscan and subtracted from the field ``into`` (default: the first; the
+        mappers bin the sum) (maria_amd.subscans).  The subscans are the stretches of the boresight azimuth
+        between two turnarounds (``subscans.find_subscans`` with ``turn_frac``), or the segments of ``bounds`` [S + 1],
+        ascending.  Samples with nonzero ``flags`` and the turnaround samples take no part in the fit, and are
+        subtracted from like the rest of their segment.  A (detector, segment) pair with fewer than max(min_hits,
+        order + 1) samples left, or whose polynomials are degenerate on them (``regress.solve``), is left bit for bit as
+        it was.  The result's flags are the old ones, ORed with the turnarounds (``flag_turnarounds``) and with every
+        sample of a segment that was not fitted (``flag_failed``).  Every field of the result is a float32 device copy;
+        ``dets``, ``coords``, ``units`` and the pW <-> K_RJ calibrator are carried over; ``metadata["subscans"]`` records
+        ``order``, ``bounds``, ``turn_frac``, ``min_hits``, ``rcond``, the [D, S, order + 1] float64 ``coefficients`` and
+        ``failed_segments``, the [n, 2] (detector, segment) pairs of the segments with samples that were not fitted.  This
+        TOD is left as it is."""
+        import torch
+
+        from . import regress, subscans
+
+        if int(order) != order or not 0 <= int(order) < subscans.MAX_ORDER:
+            raise ValueError(f"order {order}: an integer in 0 .. {subscans.MAX_ORDER - 1}")
+        K = int(order) + 1
+        min_hits = regress._check_min_hits(min_hits)
+        if not 0.0 <= float(rcond) < 1.0:
+            raise ValueError(f"rcond {rcond}: in [0, 1)")
+        T = int(np.asarray(self.coords.t).size)
+        found, turn = subscans.find_subscans(self.coords._baz, turn_frac)
+        if bounds is None:
+            bounds = found
+        else:
+            bounds = np.asarray(bounds)
+            if bounds.ndim != 1 or bounds.size < 2 or bounds.dtype.kind not in "iu" or np.any(np.diff(bounds.astype(np.int64)) < 0):
+                raise ValueError("bounds must be a one-dimensional array of S + 1 >= 2 ascending integers")
+            bounds = np.clip(bounds.astype(np.int64), 0, T).astype(np.int32)
+        if turn.size != T:
+            raise ValueError(f"the boresight has {turn.size} samples: the coordinates' time axis {T}")
+        data, signal, model, flags, into, ctx = self._device_fields(model, into, ctx, device)
+        dev = signal.device
+        d_turn = torch.as_tensor(turn).to(dev)
+        used = d_turn[None, :].expand(signal.shape[0], T).contiguous() if flags is None else flags | d_turn[None, :]
+        d_bounds = torch.as_tensor(bounds).to(dev)
+        a, ok = subscans.fit(signal, d_bounds, K, flags=used, model=model, min_hits=min_hits, rcond=rcond, ctx=ctx)
+        del signal
+        subscans.apply(data[into], d_bounds, a, sign=-1, out=data[into], ctx=ctx)
+        segment = np.full(T, -1, np.int64)  # every sample's segment
+        for s, (lo, hi) in enumerate(zip(bounds[:-1], bounds[1:])):
+            segment[lo:hi] = s
+        covered = torch.as_tensor(segment >= 0).to(dev)
+        failed = ~ok[:, torch.as_tensor(np.maximum(segment, 0)).to(dev)] & covered[None, :]  # [D, T]
+        new_flags = flags
+        if flag_turnarounds:
+            new_flags = used
+        if flag_failed:
+            new_flags = failed.to(torch.uint8) if new_flags is None else new_flags | failed.to(torch.uint8)
+        nonempty = np.diff(bounds.astype(np.int64)) > 0
+        metadata = dict(self.metadata)
+        metadata["subscans"] = {"order": int(order), "bounds": np.array(bounds, np.int32), "turn_frac": float(turn_frac), "min_hits": min_hits,
+                                "rcond": float(rcond), "coefficients": a.cpu().numpy(),
+                                "failed_segments": np.argwhere(~ok.cpu().numpy() & nonempty[None, :])}
+        out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=new_flags)
         out._calibrator = getattr(self, "_calibrator", None)
         return out
 
