@@ -1138,6 +1138,42 @@ int mrx_tod_segment_normal(mrx_ctx* ctx, const float* d_x, size_t ld_x, const fl
 int mrx_tod_segment_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, const int32_t* d_bound, int S, int K,
                           const double* d_a, int sign, float* d_y, size_t ld_y);
 
+/* ---- detector time constants: the one-pole lag and its exact inverse (maria_amd/time_constants.py) ------ */
+
+/* Common to the two entries below.  A detector answers optical power through a one-pole low-pass of time constant tau;
+ * at the sample rate fs its pole is a = exp(-1 / (fs tau)).
+ *  d_x, d_y  [D][ld] float32, pitches in elements; no alignment beyond the element size (16-byte accesses where
+ *            pointer and pitch allow it)
+ *  d_a       [D] float64 on the device: the pole of every row.  a = 0: no lag.  A row whose a is not in [0, 1), NaN
+ *            included, is copied, and so is a row with a = 0, bit for bit: no content of d_a makes a kernel read or
+ *            write out of range, and none makes the lag turn finite samples into Inf or NaN (its results are convex
+ *            combinations of samples).  The inverse has the gain (1 + a) / (1 - a) of its definition
+ *  init      0: zero state before the first sample (scipy.signal.lfilter without zi); 1: steady state, the detector has
+ *            seen x[0] for ever
+ * Every operation written below is one float64 rounding (no fused multiply-add).  No atomics, and no workgroup waits for
+ * another: every bit of a row's result is a function of that row's samples, its a, T and init alone, not of D, the
+ * pitches, the pointers' alignment or what else is in the call.  The output with the same pitch as the input and
+ * d_y == d_x works in place.  Nothing is written past T in a row; inputs are otherwise never modified.
+ * D < 1, T < 1, a pitch < T, init not 0 or 1, a null d_x, d_a or d_y, or d_y == d_x with ld_y != ld_x ->
+ * MRX_ERR_INVALID with the output untouched */
+
+/* The lag.  With g = 1.0 - a the result is the float32 rounding of the serial float64 recurrence
+ *   y64[0] = init ? (double)x[0] : g * (double)x[0]
+ *   y64[t] = a * y64[t - 1] + g * (double)x[t]
+ *   y[t]   = (float)y64[t]
+ * evaluated time-parallel (a scan of the affine maps s -> a^k s + B over tiles of 1024 samples, powers of a and the
+ * carry from tile to tile in float64; one workgroup a row): |y - y64| <= 2^-24 |y64| + 64 * 2^-53 * max|x| / (1 - a). */
+int mrx_tod_onepole(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, const double* d_a, int init, float* d_y,
+                    size_t ld_y);
+
+/* The exact inverse, a two-tap FIR.  With r = 1.0 / (1.0 - a), in this order:
+ *   x[0] = init ? y[0] : (float)((double)y[0] * r)
+ *   x[t] = (float)(((double)y[t] - a * (double)y[t - 1]) * r)
+ * the same bits as these lines on the host.  Of a float32 TOD that mrx_tod_onepole made it returns the input to
+ *   |x' - x| <= 2^-24 |x| + (1 + a) / (1 - a) * 2^-23 * max|y|. */
+int mrx_tod_onepole_inverse(mrx_ctx* ctx, const float* d_y, size_t ld_y, int D, int T, const double* d_a, int init,
+                            float* d_x, size_t ld_x);
+
 /* ---- TOD pre-processing for the mappers (tod/processing.py:91-204) --------------------- */
 
 /* remove_slope (D -= linspace(D[:, 0], D[:, -1], T), processing.py:99-105) and / or window

@@ -36,7 +36,7 @@ class Band:
     """band/band.py:89-160 (constructor) and :317-323 (``passband``)."""
 
     def __init__(self, center=None, width=None, nu=None, tau=None, name=None, shape="gaussian", efficiency=0.5, gain_error=0.0,
-                 NEP=1e-17, NEP_per_loading=0.0, knee=1.0):
+                 NEP=1e-17, NEP_per_loading=0.0, knee=1.0, time_constant=0.0):
         auto = center is not None and width is not None
         manual = nu is not None and tau is not None
         if not auto ^ manual:
@@ -53,6 +53,9 @@ class Band:
         self.efficiency = efficiency
         self.gain_error = gain_error
         self.NEP, self.NEP_per_loading, self.knee = NEP, NEP_per_loading, knee  # W sqrt(s), -, Hz (band.py:103-108)
+        self.time_constant = float(time_constant)  # s: the one-pole lag of the band's detectors (band.py: time_constant)
+        if not (np.isfinite(self.time_constant) and self.time_constant >= 0):
+            raise ValueError(f"time_constant {time_constant}: a finite number of seconds >= 0")
         self.shape = shape
         self.center = float(np.trapezoid(self.nu * self.tau, self.nu) / np.trapezoid(self.tau, self.nu)) if center is None else float(center)
         self.name = name or f"f{10 ** (np.log10(self.center) % 3):>03.0f}"
@@ -84,7 +87,7 @@ def compute_angular_fwhm(fwhm_0, z=np.inf, n=1.0, nu=None):
 class Detectors:
     """The detector table (``instrument.dets``): offsets, band membership, beams."""
 
-    def __init__(self, offsets, bands, band_index=None, primary_size=10.0, gamma=None):
+    def __init__(self, offsets, bands, band_index=None, primary_size=10.0, gamma=None, time_constant=None):
         self.offsets = np.atleast_2d(np.asarray(offsets, float))
         self.bands = list(bands)
         self.n = len(self.offsets)
@@ -93,16 +96,22 @@ class Detectors:
         self.gamma = np.full(self.n, np.nan) if gamma is None else np.asarray(gamma, float)
         if self.band_index.shape != (self.n,) or (self.n and (self.band_index.min() < 0 or self.band_index.max() >= len(self.bands))):
             raise ValueError("band_index must map every detector to one of the bands")
+        # [n] seconds: each detector's band value, or a scalar or an array in its place
+        if time_constant is None:
+            time_constant = np.array([getattr(b, "time_constant", 0.0) for b in self.bands], float)[self.band_index]
+        self.time_constant = np.broadcast_to(np.asarray(time_constant, float), (self.n,)).copy()
+        if not np.all(np.isfinite(self.time_constant) & (self.time_constant >= 0)):
+            raise ValueError("time_constant: finite numbers of seconds >= 0")
 
     @classmethod
-    def hexagon(cls, n, field_of_view_deg, bands, primary_size=10.0):
+    def hexagon(cls, n, field_of_view_deg, bands, primary_size=10.0, time_constant=None):
         """``n`` positions x ``len(bands)`` bands, each band its own block of rows
         (array/array.py:496-502)."""
         from .synthetic import hex_pack
 
         pos = hex_pack(n, np.radians(field_of_view_deg))
         nb = len(bands)
-        return cls(np.tile(pos, (nb, 1)), bands, np.repeat(np.arange(nb), n), primary_size)
+        return cls(np.tile(pos, (nb, 1)), bands, np.repeat(np.arange(nb), n), primary_size, time_constant=time_constant)
 
     @property
     def band_name(self):
@@ -151,7 +160,8 @@ class Detectors:
         return self.subset(np.sort(first))
 
     def subset(self, idx):
-        return Detectors(self.offsets[idx], self.bands, self.band_index[idx], self.primary_size[idx], self.gamma[idx])
+        return Detectors(self.offsets[idx], self.bands, self.band_index[idx], self.primary_size[idx], self.gamma[idx],
+                         time_constant=self.time_constant[idx])
 
     def mask(self, band_name):
         return self.band_name == band_name

@@ -567,6 +567,52 @@ class TOD:
         out._calibrator = getattr(self, "_calibrator", None)
         return out
 
+    def deconvolve_time_constants(self, tau=None, init="steady", into=None, ctx=None, device="cuda:0"):
+        """A new TOD with the detectors' one-pole lag taken out of every field by its exact inverse, the two-tap FIR
+        x[t] = (y[t] - a y[t - 1]) / (1 - a) with a = exp(-1 / (fs tau)) (maria_amd.time_constants).  It is
+        the first step of time-domain cleaning, before anything is flagged or fitted: deconvolve_time_constants ->
+        downsample -> flag_glitches -> fix_jumps -> remove_ground -> remove_common_mode -> filter_subscans.  A pipeline
+        sees only the sum of the fields and the operation is linear, so every field is deconvolved, the noise with
+        them (the FIR raises white noise towards the Nyquist frequency by up to (1 + a) / (1 - a); ``downsample`` is the
+        next step and low-passes).  ``tau``: seconds, a scalar or one per detector (None: ``dets.time_constant``); an
+        explicit value lets one study a mis-estimated time constant.  ``init``: "steady" (the detector had seen the first
+        sample for ever, what ``Simulation`` applies) or "zero".  ``into``: accepted like the other steps' (a field's
+        name); every field is treated alike.  fs is (n - 1) / (t[-1] - t[0]) as in ``psd``.  Flags: sample t of the
+        result is flagged if t or t - 1 was, for its value depends on both.  On a TOD that was downsampled it raises
+        NotImplementedError: at the reduced rate the lag is no longer one pole, so deconvolve first.  Every field of the
+        result is a float32 device copy; ``dets``, ``coords``, ``units`` and the pW <-> K_RJ calibrator are carried over
+        (the conversion scales a row by a factor that changes over many time constants; exact where the run was made in
+        pW); ``metadata["time_constants"]`` gains ``deconvolved`` True, ``deconvolved_tau`` and ``deconvolved_init``.  This TOD
+        is left as it is."""
+        import torch
+
+        from . import time_constants
+
+        if "downsample" in self.metadata:
+            raise NotImplementedError("deconvolve_time_constants on a downsampled TOD: at the reduced rate the lag is no longer one "
+                                      "pole; deconvolve first, then downsample")
+        time_constants._check_init(init)
+        n = int(self.dets.n)
+        tau = np.asarray(self.dets.time_constant if tau is None else tau, float)
+        if tau.ndim > 1 or (tau.ndim == 1 and tau.shape[0] != n):
+            raise ValueError(f"tau must be a scalar or one time constant for each of the {n} detectors")
+        a = time_constants.poles(np.broadcast_to(tau, (n,)), time_constants.sample_rate_of(self.coords.t))
+        data, signal, _, flags, into, ctx = self._device_fields(None, into, ctx, device)
+        d_a = torch.as_tensor(a).to(signal.device)
+        del signal
+        for x in data.values():
+            time_constants.deconvolve(x, d_a, init=init, out=x, ctx=ctx)
+        if flags is not None:
+            grown = flags.clone()
+            grown[:, 1:] |= flags[:, :-1]
+            flags = grown
+        metadata = dict(self.metadata)
+        metadata["time_constants"] = dict(metadata.get("time_constants") or {}, deconvolved=True, deconvolved_tau=np.broadcast_to(tau, (n,)).copy(),
+                                          deconvolved_init=init)
+        out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=flags)
+        out._calibrator = getattr(self, "_calibrator", None)
+        return out
+
     def to(self, units):
         """tod/tod.py:106-142 between "pW" and "K_RJ" (``mrx_tod_to_krj`` / ``mrx_tod_from_krj`` on
         every field), for a TOD that came out of ``Simulation.run``; other units stay with maria's
@@ -914,6 +960,14 @@ class Simulation:
                     "shard": None if rows is None else {"rank": self.shard[0], "world": self.shard[1], "rows": [lo, hi]}}
         has_atm = hasattr(obs, "atmosphere")
         device = torch.device(obs.atmosphere.device) if has_atm else torch.device(self.device)
+        # Detector time constants: the detector lags optical power and calibration follows, so with any of
+        # this process's rows lagged the run is made in pW, the optical fields go through mrx_tod_onepole on the device,
+        # and the finished TOD through TOD.to(units).  Where every tau is 0 nothing below changes.
+        tau = self._time_constants(dets)
+        lagged = tau is not None
+        units_out = units
+        if lagged:
+            units = "pW"
         if hi <= lo:
             # a rank past the last block of rows (dist.shard_bounds cuts blocks of 16: 144 detectors on 4 ranks are
             # 48 + 48 + 48 + 0): fields of no rows, and the random streams kept in step with the other ranks
@@ -987,13 +1041,47 @@ class Simulation:
             for field in (map_loading, noise):
                 if field is not None:
                     field /= den
+        if lagged:  # the noise is the law of the readout's output and stays as drawn
+            optical = [n for n, f in (("atmosphere", loading), ("map", map_loading)) if f is not None]
+            self._apply_time_constants(obs, [f for f in (loading, map_loading) if f is not None], tau)
+            metadata["time_constants"] = {"applied": True, "fields": optical, "init": "steady"}
         for name, field in (("atmosphere", loading), ("map", map_loading), ("noise", noise)):
             if field is not None:
                 obs.loading[name] = field if self.device_output else field.cpu().numpy()
         coords = obs.coords if rows is None else obs.boresight.broadcast(obs.coords.offsets[lo:hi])
         tod = TOD(data=obs.loading, dets=dets, coords=coords, units=units, metadata=metadata)
         tod._calibrator = self._make_calibrator(obs, metadata, (lo, hi))
+        if units_out != units:
+            tod = tod.to(units_out)
+            obs.loading = tod.data
         return tod
+
+    @staticmethod
+    def _time_constants(dets):
+        """[D] seconds, the time constants of ``dets``, or None where every one is 0: no launch, no metadata key and the
+        bits of a run without them."""
+        tau = np.asarray(dets.time_constant, float)
+        return tau if np.any(tau > 0) else None
+
+    def _apply_time_constants(self, obs, fields, tau):
+        """``mrx_tod_onepole`` from the steady state over each of ``fields`` ([D, T] float32 pW on the device), in place:
+        every row through its detector's one-pole lag ``tau`` [D] (seconds) at the rate of the observation's samples."""
+        import torch
+
+        from . import time_constants
+        from ._lib import Context
+
+        if hasattr(obs, "atmosphere"):
+            path = obs.atmosphere._device_path()
+            ctx, device = path.ctx, path.device
+        else:
+            device = torch.device(self.device)
+            self._noise_ctx = self._noise_ctx or Context(device.index or 0)
+            ctx = self._noise_ctx
+        ctx.set_stream(torch.cuda.current_stream(device))
+        a = torch.as_tensor(time_constants.poles(tau, time_constants.sample_rate_of(obs.coords.t))).to(device)
+        for field in fields:
+            time_constants.apply(field, a, init="steady", out=field, ctx=ctx)
 
     @staticmethod
     def _band_denominators(dets):
