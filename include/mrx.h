@@ -447,7 +447,15 @@ int mrx_linear_upsample(mrx_ctx* ctx, const double* d_pwv, int D, int Ta,
  * per-layer screen smoothing (atmosphere/atmosphere.py:341-344) and
  * ProjectionMap.smooth (map/projection.py:485-504).  A sigma <= 1e-15 skips
  * that axis as scipy does.  d_tmp is ny*nx floats of scratch; in == out is
- * allowed. */
+ * allowed.
+ * Non-finite input spreads as in scipy and no further: a NaN makes the pixels
+ * whose window holds it NaN (+-radius per filtered axis, folded back at a
+ * reflecting edge), an Inf makes them Inf of its sign (NaN where +Inf and -Inf,
+ * or a pass's Inf and NaN, meet in one window); every other pixel is the finite
+ * value scipy gives, to the bound of MRX_OPT_GAUSS_ACCUM.  A radius whose tile
+ * does not fit the LDS (3574 along x or along a y that runs transposed, 238
+ * along a directly filtered y) returns MRX_ERR_UNSUPPORTED before d_out is
+ * written. */
 int mrx_gauss_smooth2d(mrx_ctx* ctx, const float* d_in, float* d_out,
                        float* d_tmp, int ny, int nx, double sigma_y,
                        double sigma_x, double truncate);
@@ -464,7 +472,12 @@ int mrx_resample_columns(mrx_ctx* ctx, const float* d_in, int n_e, int n_in, siz
 
 /* ProjectionMap.smooth (map/projection.py:485-504): numer = G(data*weight),
  * denom = G(weight), out = denom > 0 ? numer/denom : 0; d_weight may be NULL
- * (weight == 1).  d_denom_out may be NULL.  d_tmp: 2*ny*nx floats. */
+ * (weight == 1).  d_denom_out may be NULL.  d_tmp: 2*ny*nx floats.
+ * A binned map's unhit pixels (NaN data, weight 0) behave as in the reference:
+ * data*weight is NaN there, so out is NaN over that pixel's window and nowhere
+ * else (mrx_gauss_smooth2d's non-finite rule, on numer and denom alike); an
+ * infinite weight gives Inf / Inf = NaN over its window.  Give unhit pixels a
+ * finite value (0) to have them ignored instead. */
 int mrx_map_smooth(mrx_ctx* ctx, const float* d_data, const float* d_weight,
                    float* d_out, float* d_denom_out, float* d_tmp, int ny,
                    int nx, double sigma_y, double sigma_x);

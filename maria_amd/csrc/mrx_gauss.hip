@@ -12,6 +12,7 @@
 // there; lanes run along x in both passes so LDS reads are conflict-free and
 // global traffic is coalesced.
 #include <cmath>
+#include <utility>
 #include <vector>
 
 #include "mrx_internal.h"
@@ -74,6 +75,106 @@ __host__ __device__ inline int gauss_tap_slots(int ntap) { return (4 + ntap + 7 
 // workgroups of it at 8192^2, and waited more than it computed.
 constexpr int kXRows = 4;
 
+// A value meets an accumulator only INSIDE that output's window.  The sliding window gives every staged value to all of a
+// thread's outputs; where the value lies outside an output's window the tap register holds a zero -- the first steps
+// (taps "before" the row), the last ones (the zero padding behind the taps) -- and 0 * NaN, 0 * Inf are NaN: a
+// non-finite pixel would spread past scipy's +-radius.  Output j takes window step s only if 0 <= s - j < ntap.  The
+// window is walked four steps at a time, and what a group of four has to ask depends on where it is (kKind):
+//   kInside: every step inside every output's window -- nothing asked: the steady loops, as they were;
+//   kHead:   the first steps, s a literal once the group is unrolled: s >= j is folded by the compiler;
+//   kTail:   the groups that reach past tap ntap - 1.  rem = ntap - s0 (s0 the group's first step) is the same in every
+//            lane and odd, so ONE scalar switch picks the group's form (gauss_tail4<rem>) and the multiply-adds in it
+//            carry no condition.  (A comparison per output and step is turned into a select per multiply-add by the
+//            compiler, and a load behind a branch is waited for on its own: both cost a third of the time at
+//            radius 8.  Values and taps are therefore fetched before the switch.)
+//   kBoth:   a window shorter than the first group, where head and tail overlap (radius 0 and 1; small radii in the
+//            blocked mode when it is forced on them): both comparisons per output.
+// For finite input a dropped + 0 * v changes nothing: an accumulator that starts at +0 never becomes -0.
+enum { kInside = 0, kHead = 1, kTail = 2, kBoth = 3 };
+
+__device__ __forceinline__ void gauss_mad(double t, double v, double& acc) { acc += t * v; }
+__device__ __forceinline__ void gauss_mad(float t, float v, float& acc) { acc = fmaf(t, v, acc); }
+
+// four steps with kRem taps left for output 0 at the first of them: step i reaches output j only if j > i - kRem.
+// t[j]: the tap of step s - j; v, w: the values and taps of a group of kN steps, these four from kOff on
+template <int kRem, int kOut, int kOff, int kN, typename T>
+__device__ __forceinline__ void gauss_tail4(const float (&v)[kN], const T (&w)[kN], T (&t)[kOut], T (&acc)[kOut]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+#pragma unroll
+    for (int j = kOut - 1; j > 0; --j) t[j] = t[j - 1];
+    t[0] = w[kOff + i];
+#pragma unroll
+    for (int j = 0; j < kOut; ++j)
+      if (j > i - kRem) gauss_mad(t[j], (T)v[kOff + i], acc[j]);
+  }
+}
+
+template <int kKind, int kOut, int kOff, int kN, typename T>
+__device__ __forceinline__ void gauss_steps4(const float (&v)[kN], const T (&w)[kN], int s0, int ntap, T (&t)[kOut], T (&acc)[kOut]) {
+  static_assert(kOut == 4 || kOut == 8, "the switch below lists the forms of 4 and 8 outputs");
+  if constexpr (kKind == kTail) {
+    const int rem = ntap - s0;
+    if (rem >= 4) {
+      gauss_tail4<4, kOut, kOff, kN, T>(v, w, t, acc);
+    } else {
+      switch (rem) {
+        case 3: gauss_tail4<3, kOut, kOff, kN, T>(v, w, t, acc); break;
+        case 1: gauss_tail4<1, kOut, kOff, kN, T>(v, w, t, acc); break;
+        case -1: gauss_tail4<-1, kOut, kOff, kN, T>(v, w, t, acc); break;
+        case -3: if constexpr (kOut == 8) gauss_tail4<-3, kOut, kOff, kN, T>(v, w, t, acc); break;
+        case -5: if constexpr (kOut == 8) gauss_tail4<-5, kOut, kOff, kN, T>(v, w, t, acc); break;
+        default: break;  // past every output's window (and so is every later step)
+      }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int j = kOut - 1; j > 0; --j) t[j] = t[j - 1];
+      t[0] = w[kOff + i];
+      const int s = s0 + i;
+#pragma unroll
+      for (int j = 0; j < kOut; ++j)
+        if (kKind == kInside || (kKind == kHead && s >= j) || (kKind == kBoth && s >= j && s - j < ntap))
+          gauss_mad(t[j], (T)v[kOff + i], acc[j]);
+    }
+  }
+}
+
+// four window steps of the x pass: one 16-byte LDS read, the four taps w of those steps
+template <int kKind, typename T>
+__device__ __forceinline__ void gauss_x_group(const float4 q, const T (&w)[4], int k, int ntap, T (&t)[4], T (&acc)[4]) {
+  const float v[4] = {q.x, q.y, q.z, q.w};
+  gauss_steps4<kKind, 4, 0, 4, T>(v, w, k, ntap, t, acc);
+}
+
+template <int kKind>
+__device__ __forceinline__ void gauss_x_group_exact(const float4* c4, const double* __restrict__ tapsd, int k, int ntap, double (&t)[4], double (&acc)[4]) {
+  const float4 q = c4[k >> 2];
+  const double w[4] = {tapsd[4 + k], tapsd[5 + k], tapsd[6 + k], tapsd[7 + k]};  // (uniform: scalar loads)
+  gauss_x_group<kKind, double>(q, w, k, ntap, t, acc);
+}
+
+// kAccBlock window steps of the x pass in the blocked mode: float32 sums, added to the float64 accumulators
+template <int kFirst, int kRest>
+__device__ __forceinline__ void gauss_x_block(const float4* c4, const float* __restrict__ tapsf, int k, int ntap, float (&t)[4], double (&acc)[4]) {
+  float4 q[kAccBlock / 4];
+  float w[kAccBlock / 4][4];
+#pragma unroll
+  for (int g = 0; g < kAccBlock / 4; ++g) q[g] = c4[(k >> 2) + g];
+#pragma unroll
+  for (int g = 0; g < kAccBlock / 4; ++g)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[g][i] = tapsf[4 + k + 4 * g + i];  // (uniform: scalar loads)
+  float p[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  gauss_x_group<kFirst, float>(q[0], w[0], k, ntap, t, p);
+#pragma unroll
+  for (int g = 1; g < kAccBlock / 4; ++g) gauss_x_group<kRest, float>(q[g], w[g], k + 4 * g, ntap, t, p);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] += (double)p[j];
+}
+
 template <bool kBlocked>
 __global__ __launch_bounds__(kBlock) void gauss_x_kernel(
     const float* __restrict__ in, float* __restrict__ out, int ny, int nx,
@@ -104,61 +205,38 @@ __global__ __launch_bounds__(kBlock) void gauss_x_kernel(
   __syncthreads();
   const int x = x0 + threadIdx.x * kXPerThread;
   if (x >= nx) return;
-  const int steps = ntap + 3;  // (the steps past the window meet zero taps and the image's zero padding)
+  const int steps = ntap + 3;  // (the steps past an output's window are not given to it: gauss_steps4)
   for (int r = 0; r < kXRows && y_first + r < ny; ++r) {
   const int y = y_first + r;
   // outputs x .. x + 3 read img[4 tid .. 4 tid + 2 radius + 3]; window step k: value img[4 tid + k], tap of output j: step k - j
   const float4* c4 = reinterpret_cast<const float4*>(img_all + r * pitch + threadIdx.x * kXPerThread);
-  double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
   if constexpr (kBlocked) {
-    float t1 = 0.0f, t2 = 0.0f, t3 = 0.0f;
-    for (int k = 0; k < steps; k += kAccBlock) {
-      float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f, p3 = 0.0f;
-#pragma unroll
-      for (int kk = 0; kk < kAccBlock; kk += 4) {
-        const float4 q = c4[(k + kk) >> 2];
-        const float v[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float t0 = tapsf[4 + k + kk + i];  // (uniform: a scalar load)
-          p0 = fmaf(t0, v[i], p0);
-          p1 = fmaf(t1, v[i], p1);
-          p2 = fmaf(t2, v[i], p2);
-          p3 = fmaf(t3, v[i], p3);
-          t3 = t2;
-          t2 = t1;
-          t1 = t0;
-        }
-      }
-      acc0 += (double)p0;
-      acc1 += (double)p1;
-      acc2 += (double)p2;
-      acc3 += (double)p3;
+    float t[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (ntap >= kAccBlock) {
+      gauss_x_block<kHead, kInside>(c4, tapsf, 0, ntap, t, acc);
+      int k = kAccBlock;
+      for (; k + kAccBlock <= ntap; k += kAccBlock) gauss_x_block<kInside, kInside>(c4, tapsf, k, ntap, t, acc);
+      for (; k < steps; k += kAccBlock) gauss_x_block<kTail, kTail>(c4, tapsf, k, ntap, t, acc);
+    } else {
+      for (int k = 0; k < steps; k += kAccBlock) gauss_x_block<kBoth, kBoth>(c4, tapsf, k, ntap, t, acc);
     }
   } else {
-    double t1 = 0.0, t2 = 0.0, t3 = 0.0;  // the taps of the three steps before
-    for (int k = 0; k < steps; k += 4) {
-      const float4 q = c4[k >> 2];
-      const float v[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const double t0 = tapsd[4 + k + i];
-        const double vv = (double)v[i];
-        acc0 += t0 * vv;
-        acc1 += t1 * vv;
-        acc2 += t2 * vv;
-        acc3 += t3 * vv;
-        t3 = t2;
-        t2 = t1;
-        t1 = t0;
-      }
+    double t[4] = {0.0, 0.0, 0.0, 0.0};
+    if (ntap >= 4) {
+      gauss_x_group_exact<kHead>(c4, tapsd, 0, ntap, t, acc);
+      int k = 4;
+      for (; k + 4 <= ntap; k += 4) gauss_x_group_exact<kInside>(c4, tapsd, k, ntap, t, acc);
+      for (; k < steps; k += 4) gauss_x_group_exact<kTail>(c4, tapsd, k, ntap, t, acc);
+    } else {
+      for (int k = 0; k < steps; k += 4) gauss_x_group_exact<kBoth>(c4, tapsd, k, ntap, t, acc);
     }
   }
+  const double acc0 = acc[0], acc1 = acc[1], acc2 = acc[2], acc3 = acc[3];
   float* dst = out + (size_t)y * nx + x;
   if (x + 3 < nx && (nx & 3) == 0) {
     *reinterpret_cast<float4*>(dst) = make_float4((float)acc0, (float)acc1, (float)acc2, (float)acc3);
   } else {
-    const double acc[4] = {acc0, acc1, acc2, acc3};
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (x + j < nx) dst[j] = (float)acc[j];
@@ -172,6 +250,36 @@ __global__ __launch_bounds__(kBlock) void gauss_x_kernel(
 // read takes the LDS two cycles, its four multiply-adds the SIMD eight, and four SIMDs share the LDS.  kRows = 4 stays for
 // the tiles of 16 rows that the largest radii need.
 constexpr int kYCols = 64;
+
+// kSteps window steps of the y pass from step k on (kinds as in the x pass: gauss_steps4), one 4-byte LDS read a step;
+// values and taps first
+template <int kKind, int kRows, int kSteps, typename T, int... kGroup>
+__device__ __forceinline__ void gauss_y_groups(const float (&v)[kSteps], const T (&w)[kSteps], int k, int ntap, T (&t)[kRows], T (&acc)[kRows],
+                                               std::integer_sequence<int, kGroup...>) {
+  (gauss_steps4<kKind, kRows, 4 * kGroup, kSteps, T>(v, w, k + 4 * kGroup, ntap, t, acc), ...);
+}
+
+template <int kKind, int kSteps, int kRows, typename T>
+__device__ __forceinline__ void gauss_y_steps(const float* c, const T* __restrict__ taps, int k, int ntap, T (&t)[kRows], T (&acc)[kRows]) {
+  float v[kSteps];
+  T w[kSteps];
+#pragma unroll
+  for (int kk = 0; kk < kSteps; ++kk) v[kk] = c[(k + kk) * kYCols];
+#pragma unroll
+  for (int kk = 0; kk < kSteps; ++kk) w[kk] = taps[4 + k + kk];  // (uniform: scalar loads)
+  gauss_y_groups<kKind, kRows, kSteps, T>(v, w, k, ntap, t, acc, std::make_integer_sequence<int, kSteps / 4>());
+}
+
+// kAccBlock steps in the blocked mode: float32 sums, added to the float64 accumulators
+template <int kKind, int kRows>
+__device__ __forceinline__ void gauss_y_block(const float* c, const float* __restrict__ tapsf, int k, int ntap, float (&t)[kRows], double (&acc)[kRows]) {
+  float p[kRows];
+#pragma unroll
+  for (int j = 0; j < kRows; ++j) p[j] = 0.0f;
+  gauss_y_steps<kKind, kAccBlock, kRows, float>(c, tapsf, k, ntap, t, p);
+#pragma unroll
+  for (int j = 0; j < kRows; ++j) acc[j] += (double)p[j];
+}
 
 template <bool kBlocked, int kRows>
 __global__ __launch_bounds__(kBlock) void gauss_y_kernel(
@@ -219,36 +327,25 @@ __global__ __launch_bounds__(kBlock) void gauss_y_kernel(
       float t[kRows];  // t[j]: the tap of step k - j
 #pragma unroll
       for (int j = 0; j < kRows; ++j) t[j] = 0.0f;
-      for (int k = 0; k < steps; k += kAccBlock) {
-        float p[kRows];
-#pragma unroll
-        for (int j = 0; j < kRows; ++j) p[j] = 0.0f;
-#pragma unroll
-        for (int kk = 0; kk < kAccBlock; ++kk) {
-          const float v = c[(k + kk) * kYCols];
-#pragma unroll
-          for (int j = kRows - 1; j > 0; --j) t[j] = t[j - 1];
-          t[0] = tapsf[4 + k + kk];  // (uniform: a scalar load)
-#pragma unroll
-          for (int j = 0; j < kRows; ++j) p[j] = fmaf(t[j], v, p[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < kRows; ++j) acc[j] += (double)p[j];
+      if (ntap >= kAccBlock) {
+        gauss_y_block<kHead, kRows>(c, tapsf, 0, ntap, t, acc);
+        int k = kAccBlock;
+        for (; k + kAccBlock <= ntap; k += kAccBlock) gauss_y_block<kInside, kRows>(c, tapsf, k, ntap, t, acc);
+        for (; k < steps; k += kAccBlock) gauss_y_block<kTail, kRows>(c, tapsf, k, ntap, t, acc);
+      } else {
+        for (int k = 0; k < steps; k += kAccBlock) gauss_y_block<kBoth, kRows>(c, tapsf, k, ntap, t, acc);
       }
     } else {
       double t[kRows];
 #pragma unroll
       for (int j = 0; j < kRows; ++j) t[j] = 0.0;
-      for (int k = 0; k < steps; k += kRows) {
-#pragma unroll
-        for (int kk = 0; kk < kRows; ++kk) {
-          const double v = (double)c[(k + kk) * kYCols];
-#pragma unroll
-          for (int j = kRows - 1; j > 0; --j) t[j] = t[j - 1];
-          t[0] = tapsd[4 + k + kk];
-#pragma unroll
-          for (int j = 0; j < kRows; ++j) acc[j] += t[j] * v;
-        }
+      if (ntap >= kRows) {
+        gauss_y_steps<kHead, kRows, kRows, double>(c, tapsd, 0, ntap, t, acc);
+        int k = kRows;
+        for (; k + kRows <= ntap; k += kRows) gauss_y_steps<kInside, kRows, kRows, double>(c, tapsd, k, ntap, t, acc);
+        for (; k < steps; k += kRows) gauss_y_steps<kTail, kRows, kRows, double>(c, tapsd, k, ntap, t, acc);
+      } else {
+        for (int k = 0; k < steps; k += kRows) gauss_y_steps<kBoth, kRows, kRows, double>(c, tapsd, k, ntap, t, acc);
       }
     }
 #pragma unroll

@@ -67,6 +67,81 @@ def test_pointing_round_trip_like_the_reference_test(gpu_ctx):
     assert worst < 1e-9  # what float32 actually delivers for centres at least ~1 deg from a pole
 
 
+def _pointing_f64(dx, dy, cphi, ctheta):
+    """coords/transforms.py:10-29 in float64 (on the float32 inputs the kernel gets)."""
+    dx, dy, cphi, ctheta = (np.asarray(v, np.float32).astype(np.float64) for v in (dx, dy, cphi, ctheta))
+    z = np.exp(1j * np.arctan2(-dx, -dy))
+    r = np.sqrt(dx * dx + dy * dy)
+    a = (np.sin(r) * z.real + 1j * np.cos(r)) * np.exp(1j * (ctheta - np.pi / 2))
+    return np.arctan2(np.sin(r) * z.imag, a.real) + cphi, np.arcsin(a.imag)
+
+
+def _angle(az1, el1, az2, el2):
+    """The angle between two directions, from the chord of their unit vectors (float64)."""
+    def unit(az, el):
+        az, el = np.asarray(az, np.float64), np.asarray(el, np.float64)
+        return np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)])
+
+    return 2.0 * np.arcsin(np.minimum(1.0, 0.5 * np.linalg.norm(unit(az1, el1) - unit(az2, el2), axis=0)))
+
+
+def test_full_rate_pointing_over_the_sphere_and_both_store_paths(gpu_ctx):
+    """mrx_pointing_broadcast with boresights over the whole sphere (az around the wrap, |el| up to 1.55) and offsets up
+    to 0.5 deg, the detector at (0, 0) among them, against the transform in float64; as the angle between the two
+    directions, so that az near a pole does not dominate.  The float32 oracle (hotpath.broadcast) is held to the same
+    float64 result: both are float32 chains of about eight library calls and two libraries differ by a few ulp a call, so
+    per bin of |el| the kernel's worst angle may be at most 4 x the oracle's.  Every shape through the 16-byte stores
+    (aligned rows) and the scalar ones (base pointer 4 bytes off a 16-byte boundary, ld % 4 == 0): same bits, and the
+    sentinels beyond T survive."""
+    import torch
+
+    from maria_amd._lib import ptr
+    from oracle import hotpath
+
+    rng = np.random.default_rng(31)
+    dev = "cuda:0"
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float32)).to(dev)  # noqa: E731
+    edges = [(0.0, 1.2), (1.2, 1.5), (1.5, 2.0)]
+    worst_k, worst_o = [0.0] * 3, [0.0] * 3
+    for D in (1, 16, 77):
+        off = np.radians(rng.uniform(-0.5, 0.5, (D, 2)))
+        off[0] = 0.0  # r = 0: atan2(-0, -0)
+        if D > 2:
+            off[1], off[2] = np.radians([0.5, -0.5]), np.radians([-0.5, 0.0])
+        for T in (1, 3, 1024, 4099):
+            az, el = rng.uniform(0, 2 * np.pi, T), rng.uniform(-1.55, 1.55, T)
+            if T >= 3:
+                az[:3] = [1e-4, 2 * np.pi - 1e-4, 2 * np.pi - 9e-4]
+                el[:3] = [1.55, -1.55, 1.55]
+            az, el = az.astype(np.float32), el.astype(np.float32)
+            d_az, d_el, d_dx, d_dy = t(az), t(el), t(off[:, 0]), t(off[:, 1])
+            ld = (T + 3) // 4 * 4 + 4
+            res = []
+            for shift in (0, 1):  # floats off the (256-byte aligned) allocation: 0 -> 16-byte stores, 1 -> scalar stores
+                bufs = [torch.full((D * ld + 4,), -9.0, dtype=torch.float32, device=dev) for _ in range(2)]
+                va, ve = (b[shift:shift + D * ld].view(D, ld) for b in bufs)
+                assert va.data_ptr() % 16 == 4 * shift and ve.data_ptr() % 16 == 4 * shift
+                gpu_ctx.call("mrx_pointing_broadcast", ptr(d_az), ptr(d_el), T, ptr(d_dx), ptr(d_dy), D, ptr(va), ptr(ve), ld)
+                full = [b.cpu().numpy() for b in bufs]
+                ga, ge = (f[shift:shift + D * ld].reshape(D, ld) for f in full)
+                assert (ga[:, T:] == -9).all() and (ge[:, T:] == -9).all()
+                assert all((f[:shift] == -9).all() and (f[shift + D * ld:] == -9).all() for f in full)
+                res.append((ga[:, :T].copy(), ge[:, :T].copy()))
+            assert np.array_equal(res[0][0].view(np.uint32), res[1][0].view(np.uint32))
+            assert np.array_equal(res[0][1].view(np.uint32), res[1][1].view(np.uint32))
+            ref_az, ref_el = _pointing_f64(off[:, 0][:, None], off[:, 1][:, None], az[None, :], el[None, :])
+            o_az, o_el = hotpath.broadcast(off, az, el)
+            ang_k, ang_o = _angle(res[0][0], res[0][1], ref_az, ref_el), _angle(o_az, o_el, ref_az, ref_el)
+            for b, (lo, hi) in enumerate(edges):
+                sel = (np.abs(ref_el) >= lo) & (np.abs(ref_el) < hi)
+                if sel.any():
+                    worst_k[b], worst_o[b] = max(worst_k[b], float(ang_k[sel].max())), max(worst_o[b], float(ang_o[sel].max()))
+    for (lo, hi), k, o in zip(edges, worst_k, worst_o):
+        print(f"pointing, {lo} <= |el| < {hi}: worst angle to float64, kernel {k:.3e} rad, float32 oracle {o:.3e} rad")
+    for k, o in zip(worst_k, worst_o):
+        assert o > 0 and k <= 4.0 * o, (worst_k, worst_o)
+
+
 def _cal_tables(n_bands):
     """Synthetic transmission-integral tables on a (T, pwv, el) grid (band.py:248-252 shape)."""
     T = np.array([250.0, 270.0, 290.0])

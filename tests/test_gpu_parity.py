@@ -293,6 +293,88 @@ def test_linear_upsample(gpu_ctx):
     assert rel_err(d_out.cpu().numpy(), ref) <= 2e-7
 
 
+_LINEAR_GRIDS = [(0.0, 0.1), (1.7e9, 0.1), (1.7e9 + 0.3, 0.04), (1.7e9, 1.0 / 3.0)]
+
+
+def _linear_times(rng, ta, dta, T):
+    """T unsorted times: the two extremes (3 dta outside the knots), every knot exactly, uniform draws between the
+    extremes -- as many of them, in that order of preference, as T holds."""
+    lo, hi = ta[0] - 3.0 * dta, ta[-1] + 3.0 * dta
+    must = np.concatenate([[lo, hi], ta])[:T]
+    t = np.concatenate([must, rng.uniform(lo, hi, T - len(must))])
+    return t[rng.permutation(T)]
+
+
+def _linear_bound(ta0, dta, pwv, t, ref):
+    """Per sample: 2^-24 |ref| + 8 2^-53 |ref| + 4 2^-53 (max|t| / dta) max_j |y_j+1 - y_j| max(1, |u|)."""
+    Ta = pwv.shape[1]
+    step = np.abs(np.diff(pwv, axis=1)).max(axis=1)[:, None]
+    jj = np.clip(np.floor((t - ta0) / dta), 0, Ta - 2)
+    u = np.abs((t - (ta0 + jj * dta)) / dta)[None, :]
+    return (2.0 ** -24 + 8 * 2.0 ** -53) * np.abs(ref) + 4 * 2.0 ** -53 * (np.abs(t).max() / dta) * step * np.maximum(1.0, u)
+
+
+@pytest.mark.parametrize("ta0,dta", _LINEAR_GRIDS)
+def test_linear_upsample_layouts_and_epoch_times(gpu_ctx, ta0, dta):
+    """mrx_linear_upsample against float64 interp1d with extrapolation (oracle.hotpath.upsample_linear): detector and
+    sample counts around the tile (16 rows) and the block (256 samples), two and ninety knots, times at the epoch,
+    unsorted, on the knots and up to 3 steps outside them; ld_out = T + 3 with a sentinel.  Per sample
+        |out - ref| <= 2^-24 |ref| + 8 2^-53 |ref| + 4 2^-53 (max|t| / dta) max_j |y_j+1 - y_j| max(1, |u|):
+    the float32 store, and the float64 roundings of t - ta0, * (1 / dta) and ta0 + j dta, which an epoch-sized t
+    amplifies by |t| / dta."""
+    import torch
+
+    from maria_amd._lib import ptr
+    from oracle import hotpath
+
+    rng = np.random.default_rng(17)
+    dev = "cuda:0"
+    worst = 0.0
+    for Ta in (2, 90):
+        ta = ta0 + np.arange(Ta) * dta
+        for D in (1, 16, 17, 33):
+            pwv = 1 + 0.01 * rng.standard_normal((D, Ta))
+            d_p = torch.as_tensor(np.ascontiguousarray(pwv.T)).to(dev)
+            for T in (1, 255, 256, 257, 1000):
+                t = _linear_times(rng, ta, dta, T)
+                ref = hotpath.upsample_linear(ta, pwv, t)
+                ld = T + 3
+                d_t = torch.as_tensor(t).to(dev)
+                d_out = torch.full((D, ld), -9.0, dtype=torch.float32, device=dev)
+                gpu_ctx.call("mrx_linear_upsample", ptr(d_p), D, Ta, float(ta0), float(dta), ptr(d_t), T, ptr(d_out), ld)
+                got = d_out.cpu().numpy()
+                assert (got[:, T:] == -9.0).all()
+                bound = _linear_bound(ta0, dta, pwv, t, ref)
+                ratio = float((np.abs(got[:, :T].astype(np.float64) - ref) / bound).max())
+                worst = max(worst, ratio)
+                assert ratio <= 1.0, (Ta, D, T, ratio)
+    print(f"linear upsample, ta0 = {ta0!r}, dta = {dta!r}: worst |out - ref| / bound = {worst:.3f}")
+
+
+def test_linear_upsample_nan_time_stays_in_its_sample(gpu_ctx):
+    import torch
+
+    from maria_amd._lib import ptr
+    from oracle import hotpath
+
+    rng = np.random.default_rng(18)
+    D, Ta, T = 17, 90, 257
+    ta = 1.7e9 + np.arange(Ta) * 0.1
+    pwv = 1 + 0.01 * rng.standard_normal((D, Ta))
+    t = _linear_times(rng, ta, 0.1, T)
+    t[100] = np.nan
+    d_p, d_t = torch.as_tensor(np.ascontiguousarray(pwv.T)).to("cuda:0"), torch.as_tensor(t).to("cuda:0")
+    d_out = torch.full((D, T), -9.0, dtype=torch.float32, device="cuda:0")
+    gpu_ctx.call("mrx_linear_upsample", ptr(d_p), D, Ta, 1.7e9, 0.1, ptr(d_t), T, ptr(d_out), T)
+    got = d_out.cpu().numpy()
+    bad = np.zeros((D, T), bool)
+    bad[:, 100] = True
+    assert np.array_equal(np.isnan(got), bad) and np.isfinite(got[~bad]).all()
+    ok = np.arange(T) != 100
+    ref = hotpath.upsample_linear(ta, pwv, t[ok])
+    assert (np.abs(got[:, ok].astype(np.float64) - ref) <= _linear_bound(1.7e9, 0.1, pwv, t[ok], ref)).all()
+
+
 def test_out_of_screen_raises_like_reference(gpu_ctx):
     """atmosphere/atmosphere.py:368-369: a sample outside a layer's grid is NaN and
     the reference raises RuntimeError; the kernel flags it and the host raises."""
