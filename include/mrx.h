@@ -1151,6 +1151,49 @@ int mrx_tod_segment_normal(mrx_ctx* ctx, const float* d_x, size_t ld_x, const fl
 int mrx_tod_segment_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, const int32_t* d_bound, int S, int K,
                           const double* d_a, int sign, float* d_y, size_t ld_y);
 
+/* ---- statistics per (row, segment) and the flagging of whole segments (maria_amd/cuts.py) ------------- */
+
+/* Common to the two entries below.  d_flags, d_model, their pitches, term(d, t), the single float64 roundings (no fused
+ * multiply-add), the absence of atomics, the alignment (none beyond the element size), "nothing is written past T" and
+ * "inputs are never modified" are those of the block above mrx_tod_column_mean; d_bound [S + 1], its clamping to 0 .. T
+ * in the kernels and the empty segment are those of the block above mrx_tod_segment_normal. */
+
+/* The moments of every (row, segment).  For row d, segment s = [lo, hi), kept = { t in [lo, hi) : flags[d][t] == 0 } and
+ * n = |kept|:
+ *   count[d][s][0] = n
+ *   count[d][s][1] = p, the number of t with t and t + 1 both in [lo, hi) and both kept
+ *   stat[d][s][0]  = mu = (sum over kept of term(d, t)) / (double)n                     (one sum, one division)
+ *   stat[d][s][1]  = M2 = sum over kept of e * e,        e = term(d, t) - mu            (mu: the rounded value stored)
+ *   stat[d][s][2]  = M3 = sum over kept of (e * e) * e
+ *   stat[d][s][3]  = M4 = sum over kept of (e * e) * (e * e)
+ *   stat[d][s][4]  = min, stat[d][s][5] = max of term(d, t) over kept                   (exact)
+ *   stat[d][s][6]  = D2 = sum over the p pairs of (term(d, t + 1) - term(d, t))^2
+ *   stat[d][s][7]  = 0.0, reserved
+ * n == 0: all eight values are 0.0; p == 0: D2 = 0.0.  A flagged sample is selected away, never multiplied: the results
+ * do not depend on what flagged samples hold (1e30 and NaN included).  An unflagged NaN makes stat[d][s][0 .. 6] of its own
+ * (row, segment) NaN and nothing else.  Every sum of a (row, segment) is added in an order that is a function of lo and hi
+ * alone (not of D, S, the flags, the model, the pitches, the pointers' alignment or what else is in the call): the same
+ * inputs give the same bits on every call, and for a row or a segment computed alone.  A sum of L terms is within
+ * L 2^-53 sum|terms| of the exact sum of its rounded terms, to first order.
+ *  d_x      [D][ld_x] float32
+ *  d_stat   [D][S][8] float64, OVERWRITTEN
+ *  d_count  [D][S][2] uint32, OVERWRITTEN
+ * D < 1, T < 1, S < 1, a pitch (of an array that is given) < T, or a null d_x, d_bound, d_stat or d_count ->
+ * MRX_ERR_INVALID with the outputs untouched */
+int mrx_tod_segment_moments(mrx_ctx* ctx, const float* d_x, size_t ld_x, const float* d_model, size_t ld_m,
+                            const uint8_t* d_flags, size_t ld_f, int D, int T, const int32_t* d_bound, int S,
+                            double* d_stat, uint32_t* d_count);
+
+/* Flag whole segments IN PLACE: flags[d][t] |= value for every t of a segment s with d_mask[d][s] != 0.  Samples in no
+ * segment, the segments whose mask is 0 and the bytes past T of a row are untouched.  Where segments overlap a sample
+ * belongs to one of them, as in mrx_tod_segment_apply.
+ *  d_flags  [D][ld_f] uint8
+ *  d_mask   [D][S] uint8
+ * D < 1, T < 1, S < 1, value outside 1 .. 255, ld_f < T, or a null d_flags, d_bound or d_mask -> MRX_ERR_INVALID with
+ * the flags untouched */
+int mrx_tod_segment_flag(mrx_ctx* ctx, uint8_t* d_flags, size_t ld_f, int D, int T, const int32_t* d_bound, int S,
+                         const uint8_t* d_mask, int value);
+
 /* ---- detector time constants: the one-pole lag and its exact inverse (maria_amd/time_constants.py) ------ */
 
 /* Common to the two entries below.  A detector answers optical power through a one-pole low-pass of time constant tau;

@@ -240,6 +240,8 @@ SIGNATURES = {
     "mrx_tod_regress_apply": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _vp, _sz, _i, _vp, _i, _vp, _sz]),
     "mrx_tod_segment_normal": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "mrx_tod_segment_apply": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _i, _vp, _i, _vp, _sz]),
+    "mrx_tod_segment_moments": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp, _i, _vp, _vp]),
+    "mrx_tod_segment_flag": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _vp, _i]),
     "mrx_tod_onepole": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _vp, _sz]),
     "mrx_tod_onepole_inverse": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _vp, _sz]),
     "mrx_tod_detrend_window": (_i, [_vp, _vp, _sz, _i, _i, _i, _vp, _vp]),

@@ -167,7 +167,7 @@ class TOD:
     """The slice of ``maria.tod.TOD`` this path fills: ``data`` (dict of [ndet, nt]
     float32 arrays, numpy or device tensors), ``dets``, ``coords``, ``units``, ``metadata``.  ``flags``: None, or a
     [ndet, nt] uint8 device tensor whose nonzero entries mark samples the mappers give no weight (``flag_glitches``,
-    ``fix_jumps``)."""
+    ``fix_jumps``, ``filter_subscans``, ``cut``)."""
 
     def __init__(self, data, dets, coords, units="pW", metadata=None, flags=None):
         self.data, self.dets, self.coords, self.units = data, dets, coords, units
@@ -571,7 +571,7 @@ class TOD:
         """A new TOD with the detectors' one-pole lag taken out of every field by its exact inverse, the two-tap FIR
         x[t] = (y[t] - a y[t - 1]) / (1 - a) with a = exp(-1 / (fs tau)) (maria_amd.time_constants).  It is
         the first step of time-domain cleaning, before anything is flagged or fitted: deconvolve_time_constants ->
-        downsample -> flag_glitches -> fix_jumps -> remove_ground -> remove_common_mode -> filter_subscans.  A pipeline
+        downsample -> flag_glitches -> fix_jumps -> remove_ground -> remove_common_mode -> filter_subscans -> cut.  A pipeline
         sees only the sum of the fields and the operation is linear, so every field is deconvolved, the noise with
         them (the FIR raises white noise towards the Nyquist frequency by up to (1 + a) / (1 - a); ``downsample`` is the
         next step and low-passes).  ``tau``: seconds, a scalar or one per detector (None: ``dets.time_constant``); an
@@ -610,6 +610,110 @@ class TOD:
         metadata["time_constants"] = dict(metadata.get("time_constants") or {}, deconvolved=True, deconvolved_tau=np.broadcast_to(tau, (n,)).copy(),
                                           deconvolved_init=init)
         out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=flags)
+        out._calibrator = getattr(self, "_calibrator", None)
+        return out
+
+    def _segment_bounds(self, bounds):
+        """[S + 1] int32 bounds for ``stats`` and ``cut``, clamped to 0 .. T: None (the whole row), "subscans"
+        (``subscans.find_subscans`` of the boresight azimuth), an int (chunks of that many samples) or an ascending
+        integer array."""
+        from . import cuts, subscans
+
+        T = int(np.asarray(self.coords.t).size)
+        if bounds is None:
+            return np.array([0, T], np.int32)
+        if isinstance(bounds, str):
+            if bounds != "subscans":
+                raise ValueError(f'bounds {bounds!r}: None, "subscans", a chunk length or an integer array')
+            found, _ = subscans.find_subscans(self.coords._baz)
+            if found[-1] != T:
+                raise ValueError(f"the boresight has {found[-1]} samples: the coordinates' time axis {T}")
+            return found
+        if isinstance(bounds, (int, np.integer)) and not isinstance(bounds, bool):
+            return cuts.chunk_bounds(T, bounds)
+        bounds = np.asarray(bounds)
+        if bounds.ndim != 1 or bounds.size < 2 or bounds.dtype.kind not in "iu" or np.any(np.diff(bounds.astype(np.int64)) < 0):
+            raise ValueError("bounds must be a one-dimensional array of S + 1 >= 2 ascending integers")
+        return np.clip(bounds.astype(np.int64), 0, T).astype(np.int32)
+
+    def stats(self, bounds=None, model=None, ctx=None, device="cuda:0"):
+        """The statistics of the signal (the sum of the fields, less ``model``) over the samples whose ``flags`` are 0
+        (maria_amd.cuts): a dict of ``bounds`` (the [S + 1] int32 segments used), ``segments`` (the
+        summary of ``cuts.summarize`` per (detector, segment): [D, S] float64 device tensors ``mean``, ``var``, ``std``,
+        ``skew``, ``kurtosis``, ``min``, ``max``, ``ptp``, ``sigma_diff``, ``flagged_fraction``, and int64 ``hits`` and
+        ``pairs``) and ``detectors`` (the same per detector, [D], from a second pass with the row as one segment).
+        ``bounds``: None (the whole row), "subscans" (``subscans.find_subscans``), an int (chunks of that many
+        samples) or an ascending integer array.  This TOD is left as it is."""
+        bounds = self._segment_bounds(bounds)
+        _, signal, model, flags, _, ctx = self._device_fields(model, None, ctx, device)
+        from . import cuts
+
+        seg = cuts.summarize(cuts.moments(signal, bounds, flags=flags, model=model, ctx=ctx), np.diff(bounds.astype(np.int64)))
+        det = seg if len(bounds) == 2 else cuts.summarize(cuts.moments(signal, None, flags=flags, model=model, ctx=ctx), [signal.shape[1]])
+        return {"bounds": bounds, "segments": seg, "detectors": {k: v[:, 0] for k, v in det.items()}}
+
+    def cut(self, bounds="subscans", groups="band", n_sigma=5.0, n_sigma_segment=5.0, max_flagged=0.5, max_bad_segments=0.5, min_hits=8,
+            criteria=("white", "rms", "skew", "kurtosis", "flagged"), value=1, model=None, ctx=None, device="cuda:0"):
+        """A new TOD whose flags also cover the detectors and the segments that are not worth mapping (maria_amd.cuts,
+        DESIGN 3.26); the last step of time-domain cleaning, after ``filter_subscans``.  The statistics of :meth:`stats`
+        are taken on the signal (the sum of the fields, less ``model``) over the samples whose flags are 0, per detector
+        and per segment of ``bounds`` (as in :meth:`stats`).  A detector is cut whole if, within its group (``groups``:
+        "band", None for one group, or an integer array, -1 leaving a detector out), it lies more than ``n_sigma``
+        robust scales (1.4826 times the median absolute deviation) from the median in log ``sigma_diff`` ("white"),
+        log ``std`` ("rms"), ``skew`` or ``kurtosis``, if more than ``max_flagged`` of its samples are flagged
+        ("flagged"), or if it is unusable: fewer than max(min_hits, 1) samples kept, or one of those values not finite
+        (a constant row).  A segment is bad if its ``sigma_diff`` lies more than ``n_sigma_segment`` robust scales
+        above the median over that detector's own segments (``cuts.bad_segments``; None: segments are not judged); a
+        detector with more than ``max_bad_segments`` of its non-empty segments bad is cut whole.  The segments are
+        judged first and the detectors on what is left, the bad segments flagged: one noisy subscan does not cost the
+        detector.  ``criteria`` picks among the five names.
+        ``value`` (1 .. 255) is ORed into the flags of every sample of a cut detector and of a bad segment
+        (``cuts.flag_segments``); the mappers give flagged samples no weight.  Every field of the result is a float32
+        device copy, unchanged; ``dets``, ``coords``, ``units`` and the pW <-> K_RJ calibrator are carried over;
+        ``metadata["cuts"]`` records the parameters, ``bounds``, the per-criterion [D] bool ``masks`` (with "unusable"
+        and "segments"), ``cut_detectors`` (indices), ``cut_segments`` (the [n, 2] (detector, segment) pairs flagged in
+        detectors that were not cut whole) and ``flagged_fraction_before`` / ``flagged_fraction_after``.  This TOD is
+        left as it is."""
+        import torch
+
+        from . import cuts
+
+        bounds = self._segment_bounds(bounds)
+        if isinstance(value, bool) or int(value) != value or not 1 <= int(value) <= 255:
+            raise ValueError(f"value {value}: an integer in 1 .. 255")
+        if isinstance(groups, str):
+            if groups != "band":
+                raise ValueError(f'groups {groups!r}: "band", None or an integer array')
+            groups = np.asarray(self.dets.band_index, np.int64)
+        elif groups is not None:
+            groups = np.asarray(groups)
+            if groups.ndim != 1 or groups.dtype.kind not in "iu" or (groups.size and groups.min() < -1):
+                raise ValueError("groups must be a one-dimensional integer array with entries >= -1")
+            groups = groups.astype(np.int64)
+        cuts._check_rules(n_sigma, n_sigma_segment, max_flagged, max_bad_segments, min_hits, criteria)
+        data, signal, model, flags, _, ctx = self._device_fields(model, None, ctx, device)
+        D, T = signal.shape
+        if groups is not None and groups.shape[0] != D:
+            raise ValueError(f"groups must have one entry for each of the {D} detectors")
+        seg = cuts.summarize(cuts.moments(signal, bounds, flags=flags, model=model, ctx=ctx), np.diff(bounds.astype(np.int64)))
+        bad = cuts.bad_segments(seg, groups, n_sigma_segment, min_hits)
+        new_flags = torch.zeros((D, T), dtype=torch.uint8, device=signal.device) if flags is None else flags.clone()
+        before = float((new_flags != 0).sum()) / new_flags.numel()
+        if bool(bad.any()):
+            cuts.flag_segments(new_flags, bounds, bad, value=int(value), ctx=ctx)
+        det = cuts.summarize(cuts.moments(signal, None, flags=new_flags, model=model, ctx=ctx), [T])  # without the bad segments
+        del signal
+        masks, cut = cuts.decide(det, seg, bad, groups, n_sigma, max_flagged, max_bad_segments, min_hits, criteria)
+        if bool(cut.any()):
+            cuts.flag_segments(new_flags, np.array([0, T], np.int32), cut[:, None], value=int(value), ctx=ctx)
+        metadata = dict(self.metadata)
+        metadata["cuts"] = {"bounds": np.array(bounds, np.int32), "n_sigma": float(n_sigma),
+                            "n_sigma_segment": None if n_sigma_segment is None else float(n_sigma_segment), "max_flagged": float(max_flagged),
+                            "max_bad_segments": float(max_bad_segments), "min_hits": int(min_hits), "criteria": tuple(criteria), "value": int(value),
+                            "groups": None if groups is None else groups.copy(), "masks": {k: v.cpu().numpy() for k, v in masks.items()},
+                            "cut_detectors": np.flatnonzero(cut.cpu().numpy()), "cut_segments": np.argwhere((bad & ~cut[:, None]).cpu().numpy()),
+                            "flagged_fraction_before": before, "flagged_fraction_after": float((new_flags != 0).sum()) / new_flags.numel()}
+        out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=new_flags)
         out._calibrator = getattr(self, "_calibrator", None)
         return out
 
