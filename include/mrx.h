@@ -1230,6 +1230,40 @@ int mrx_tod_onepole(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, c
 int mrx_tod_onepole_inverse(mrx_ctx* ctx, const float* d_y, size_t ld_y, int D, int T, const double* d_a, int init,
                             float* d_x, size_t ld_x);
 
+/* ---- a rotating half-wave plate (maria_amd/hwp.py) ---------------------------------------------------- */
+
+/* The lock-in decimator.  With the carrier c[t] = (cos 4 chi(t), sin 4 chi(t)), H = (n_taps - 1) / 2 and
+ * T_out = (T + q - 1) / q, for j = 0 .. T_out - 1 and every sum over -H <= i <= H with 0 <= j q + i < T:
+ *   y_t[d][j] =     sum_i hT[H + i]               x[d][j q + i] / sum_i hT[H + i]
+ *   y_q[d][j] = 2 * sum_i hP[H + i] c[j q + i][0] x[d][j q + i] / sum_i hP[H + i]
+ *   y_u[d][j] = 2 * sum_i hP[H + i] c[j q + i][1] x[d][j q + i] / sum_i hP[H + i]
+ * The products c x are float64, one rounding; each sum runs over the tap index ascending as acc = fma(h, term, acc) in
+ * float64 from 0; the quotient is float64 and the result rounded ONCE to float32.  y_t is mrx_tod_decimate(x, q, hT)
+ * bit for bit.  Orientation, edges (taps outside the row dropped, the rest renormalised) and the time of output j
+ * (t[j q]) are mrx_tod_decimate's.  The kernel does no trigonometry: the carrier is taken as given.
+ *  d_x        [D][ld_x] float32, read only
+ *  d_carrier  [T][2] float64
+ *  d_taps_t   [n_taps] float64 (hT); may be NULL where d_t is
+ *  d_taps_p   [n_taps] float64 (hP)
+ *  d_t        [D][ld_y] float32, or NULL: polarisation only (d_q and d_u then hold the bits of the three-output call)
+ *  d_q, d_u   [D][ld_y] float32; nothing is written past T_out in a row
+ * No alignment beyond the element size is asked of the pointers or pitches.  q outside 2 .. 32, n_taps even or outside
+ * 1 .. 1025, D < 1, T < 1, ld_x < T, ld_y < T_out, an output equal to d_x or to another output, or a null pointer other
+ * than d_t (with it, d_taps_t) -> MRX_ERR_INVALID with the outputs untouched */
+int mrx_tod_demodulate(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, int q, const double* d_carrier,
+                       const double* d_taps_t, const double* d_taps_p, int n_taps, float* d_t, float* d_q, float* d_u,
+                       size_t ld_y);
+
+/* The simulation's combine: out[d][t] = (float) fma(s[d][t], c[t][1], fma(c_[d][t], c[t][0], i[d][t])) in float64 on the
+ * float32 fields i, c_ (= d_c) and s, one rounding: i + c_ cos 4 chi + s sin 4 chi.
+ *  d_i, d_c, d_s  [D][ld_in] float32
+ *  d_carrier      [T][2] float64
+ *  d_out          [D][ld_out] float32; d_out == d_i with ld_out == ld_in works in place; nothing is written past T in a row
+ * No alignment beyond the element size (16-byte accesses where pointer and pitch allow it).  D < 1, T < 1, a pitch < T,
+ * d_out equal to d_c or d_s, d_out == d_i with ld_out != ld_in, or a null pointer -> MRX_ERR_INVALID with d_out untouched */
+int mrx_tod_hwp_modulate(mrx_ctx* ctx, const float* d_i, const float* d_c, const float* d_s, size_t ld_in, int D, int T,
+                         const double* d_carrier, float* d_out, size_t ld_out);
+
 /* ---- TOD pre-processing for the mappers (tod/processing.py:91-204) --------------------- */
 
 /* remove_slope (D -= linspace(D[:, 0], D[:, -1], T), processing.py:99-105) and / or window

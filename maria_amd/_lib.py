@@ -244,6 +244,8 @@ SIGNATURES = {
     "mrx_tod_segment_flag": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _vp, _i]),
     "mrx_tod_onepole": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _vp, _sz]),
     "mrx_tod_onepole_inverse": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _vp, _sz]),
+    "mrx_tod_demodulate": (_i, [_vp, _vp, _sz, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz]),
+    "mrx_tod_hwp_modulate": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _vp, _vp, _sz]),
     "mrx_tod_detrend_window": (_i, [_vp, _vp, _sz, _i, _i, _i, _vp, _vp]),
     "mrx_sosfilt_chunk": (_i, []),
     "mrx_sosfilt_work_doubles": (_i, [_i, _i, _i, C.POINTER(_sz)]),

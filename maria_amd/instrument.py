@@ -87,7 +87,7 @@ def compute_angular_fwhm(fwhm_0, z=np.inf, n=1.0, nu=None):
 class Detectors:
     """The detector table (``instrument.dets``): offsets, band membership, beams."""
 
-    def __init__(self, offsets, bands, band_index=None, primary_size=10.0, gamma=None, time_constant=None):
+    def __init__(self, offsets, bands, band_index=None, primary_size=10.0, gamma=None, time_constant=None, stokes=None):
         self.offsets = np.atleast_2d(np.asarray(offsets, float))
         self.bands = list(bands)
         self.n = len(self.offsets)
@@ -102,6 +102,11 @@ class Detectors:
         self.time_constant = np.broadcast_to(np.asarray(time_constant, float), (self.n,)).copy()
         if not np.all(np.isfinite(self.time_constant) & (self.time_constant >= 0)):
             raise ValueError("time_constant: finite numbers of seconds >= 0")
+        # [n, 4] (I, Q, U, V) weights in place of ``mueller_row(gamma)``, or None: the rows of a demodulated TOD
+        # (maria_amd.hwp.demodulated_detectors), whose Q and U series see no I
+        self.stokes = None if stokes is None else np.array(stokes, float)
+        if self.stokes is not None and (self.stokes.shape != (self.n, 4) or not np.all(np.isfinite(self.stokes))):
+            raise ValueError(f"stokes must be [{self.n}, 4] finite numbers")
 
     @classmethod
     def hexagon(cls, n, field_of_view_deg, bands, primary_size=10.0, time_constant=None):
@@ -146,6 +151,13 @@ class Detectors:
         m0 = np.where(np.isnan(self.gamma), np.sqrt(2), 1.0)
         return 0.5 * m0 * m0
 
+    def stokes_rows(self):
+        """[n, 4]: every detector's weights of (I, Q, U, V), the override where the table has one, else
+        ``map.mueller_row(gamma)``."""
+        from .map import mueller_row
+
+        return mueller_row(self.gamma) if self.stokes is None else self.stokes.copy()
+
     def outer(self):
         """array/array.py:156-162: the convex-hull detectors."""
         try:
@@ -161,7 +173,7 @@ class Detectors:
 
     def subset(self, idx):
         return Detectors(self.offsets[idx], self.bands, self.band_index[idx], self.primary_size[idx], self.gamma[idx],
-                         time_constant=self.time_constant[idx])
+                         time_constant=self.time_constant[idx], stokes=None if self.stokes is None else self.stokes[idx])
 
     def mask(self, band_name):
         return self.band_name == band_name

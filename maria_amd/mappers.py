@@ -21,7 +21,7 @@ import torch
 
 from . import destripe_prior, noise_estimate, noise_filter, noise_modes
 from ._lib import Context, MrxSkyMap, ptr
-from .map import ProjectionMap, mueller_row
+from .map import ProjectionMap
 
 logger = logging.getLogger("maria")
 
@@ -158,9 +158,12 @@ class _GridMapper:
         transform = None
         if self.frame == "ra/dec":
             transform = torch.as_tensor(sky_transform_stack(coords.t, tod.metadata["latitude"], tod.metadata["longitude"]).reshape(-1, 9)).to(dev)
-        row = mueller_row(dets.gamma)
+        # (without an override stokes_rows() is mueller_row(dets.gamma), and its column 0 and mueller00() are both
+        # 0.5 * m0 * m0: the bits of every plain detector table are what they were.  A demodulated TOD's Q and U rows
+        # have no I weight of their own and divide by their detector's)
+        row = dets.stokes_rows()
         if unit_i_response:
-            row = row / row[:, :1]
+            row = row / dets.mueller00()[:, None]
         stokes_w = torch.as_tensor(np.ascontiguousarray(row[:, ["IQUV".index(s) for s in self.stokes]], np.float64)).to(dev)
         # the nu plane whose frequency is the detector's band centre, else plane 0 (projection.py:152-155)
         chan = np.zeros(dets.n, np.int32)

@@ -256,6 +256,111 @@ class TOD:
             flags = downsample_flags(self.flags, q)
         return TOD(data=data, dets=self.dets, coords=coords, units=self.units, metadata=metadata, flags=flags)
 
+    def demodulate(self, hwp=None, q=None, taps_t=None, taps_p=None, ctx=None, device="cuda:0"):
+        """A new TOD at 1 / q of the sample rate whose rows are the T, Q and U series of every detector behind a rotating
+        half-wave plate (maria_amd.hwp.demodulate): every field locked in against the carrier
+        (cos 4 chi, sin 4 chi) and low-passed on the device, one field at a time, into float32 device tensors of
+        D + 2 D_pol rows -- the T rows of all D detectors, then the Q rows and then the U rows of the D_pol polarised
+        ones (an unpolarised detector carries no polarisation signal).  ``hwp``: the maria_amd.hwp.HWP (None:
+        ``metadata["hwp"]``, which the simulation wrote); ``q`` (2 .. 32; None: min(32, hwp.max_factor(...)));
+        ``taps_t``, ``taps_p``: the low-passes of T and of Q / U (one of them given serves for both; neither:
+        ``hwp.design_taps(sample rate, f_hwp)``).  The
+        boresight and the times are picked at every q-th sample, output sample j at time t[j q].  ``dets`` is
+        ``hwp.demodulated_detectors(self.dets)``, whose ``stokes_rows()`` the mappers take: a Q row is a detector of angle
+        -gamma without I weight, a U row one of angle pi / 4 - gamma; ``coords.offsets`` are repeated to match.  ``units``
+        and ``metadata`` are carried over and ``metadata["demodulate"]`` records ``f_hwp``, ``factor``, ``n_taps``,
+        ``sample_rate`` and the row ranges ``rows`` of T, Q and U.  The pW <-> K_RJ calibrator is NOT carried over: ``to()``
+        on the result raises NotImplementedError, so convert units first.  ``flags`` become
+        ``flagging.downsample_flags(flags, q)``, repeated for the Q / U rows.  This TOD is left as it is.  Its place in
+        the chain is downsample's, after deconvolve_time_constants and instead of downsample: a detector lag attenuates and
+        delays the 4 f carrier, which rotates Q into U."""
+        import torch
+
+        from . import hwp as mhwp
+        from ._lib import Context
+        from .downsample import MAX_FACTOR, MIN_FACTOR
+
+        if "demodulate" in self.metadata or "downsample" in self.metadata:
+            raise ValueError("demodulate takes the TOD at the rate the half-wave plate modulated it: this one is already reduced")
+        if hwp is None:
+            if "hwp" not in self.metadata:
+                raise ValueError('no hwp given and no metadata["hwp"]: this TOD was not simulated behind a half-wave plate')
+            hwp = mhwp.HWP.from_metadata(self.metadata["hwp"])
+        t = np.asarray(self.coords.t, float)
+        if t.size < 2:
+            raise ValueError("demodulate needs at least two samples to know the sample rate")
+        fs = (t.size - 1) / (t[-1] - t[0])
+        if q is None:
+            q = min(MAX_FACTOR, mhwp.max_factor(fs, hwp.frequency))
+        if int(q) != q or not MIN_FACTOR <= int(q) <= MAX_FACTOR:
+            raise ValueError(f"q {q}: an integer in {MIN_FACTOR} .. {MAX_FACTOR}")
+        q = int(q)
+        host = lambda h: np.ascontiguousarray(h.detach().cpu().numpy() if isinstance(h, torch.Tensor) else h, np.float64)  # noqa: E731
+        if taps_t is None and taps_p is None:
+            ht = hp = mhwp.design_taps(fs, hwp.frequency)
+        else:  # one of them given serves for both
+            hp = host(taps_t if taps_p is None else taps_p)
+            ht = hp if taps_t is None else host(taps_t)
+        c = mhwp.carrier(hwp.angle(t))
+        D = self.dets.n
+        pol = mhwp.polarized_rows(self.dets)
+        Dp = int(pol.size)
+        T_out = (t.size + q - 1) // q
+        data, d_carrier = {}, {}  # the carrier goes to a device once, and one context serves every field
+        for name, v in self.data.items():
+            v = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
+            dev = v.device if v.is_cuda else torch.device(device)
+            x = v.to(dev, torch.float32)
+            if x.dim() == 2 and x.shape[1] > 1 and x.stride(1) != 1:
+                x = x.contiguous()
+            if ctx is None:
+                ctx = Context(dev.index or 0)
+                ctx.set_stream(torch.cuda.current_stream(dev))
+            if dev not in d_carrier:
+                d_carrier[dev] = torch.as_tensor(c).to(dev)
+            y = torch.empty((D + 2 * Dp, T_out), dtype=torch.float32, device=dev)
+            if Dp == D:  # every detector has Q and U rows: the three outputs are the three blocks of the field
+                mhwp.demodulate(x, d_carrier[dev], q, ht, hp, ctx=ctx, out=(y[:D], y[D:2 * D], y[2 * D:]))
+            else:
+                _, yq, yu = mhwp.demodulate(x, d_carrier[dev], q, ht, hp, ctx=ctx, out=(y[:D], *torch.empty((2, D, T_out), dtype=torch.float32, device=dev)))
+                rows = torch.as_tensor(pol).to(dev)
+                y[D:D + Dp] = yq.index_select(0, rows)
+                y[D + Dp:] = yu.index_select(0, rows)
+            data[name] = y
+        idx = np.concatenate([np.arange(D), pol, pol])
+        cd = self.coords
+        coords = Coordinates(t[::q], cd._baz[::q], cd._bel[::q], offsets=None if cd.offsets is None else cd.offsets[idx])
+        metadata = dict(self.metadata)
+        metadata["demodulate"] = {"f_hwp": hwp.frequency, "factor": q, "n_taps": int(hp.size), "sample_rate": float(fs / q),
+                                  "rows": {"T": (0, D), "Q": (D, D + Dp), "U": (D + Dp, D + 2 * Dp)}}
+        flags = None
+        if self.flags is not None:
+            from .flagging import downsample_flags
+
+            low = downsample_flags(torch.as_tensor(self.flags), q)
+            flags = low.index_select(0, torch.as_tensor(idx).to(low.device))
+        return TOD(data=data, dets=mhwp.demodulated_detectors(self.dets), coords=coords, units=self.units, metadata=metadata, flags=flags)
+
+    def remove_hwpss(self, harmonics=(1, 2), hwp=None, **regress_kw):
+        """A new TOD with the half-wave plate's synchronous signal fitted and removed: ``TOD.regress`` on the templates
+        cos k chi, sin k chi of the ``harmonics`` k (at most 4: regress takes 8 templates), ``hwp.harmonic_templates``.
+        ``hwp`` None: ``metadata["hwp"]``; ``regress_kw``: ``model``, ``into``, ``min_hits``, ``rcond``, ``ctx``,
+        ``device``.  It runs at the full rate, before ``demodulate``.  Removing harmonic 4 also removes any polarisation
+        that is constant in the instrument's frame -- and with it the part of the sky's that happens to be.
+        ``metadata["regress"]`` is regress's, and ``metadata["hwpss"]`` records the harmonics."""
+        from . import hwp as mhwp
+
+        ks = tuple(harmonics)
+        if not 1 <= len(ks) <= mhwp.MAX_HARMONICS:
+            raise ValueError(f"harmonics {harmonics}: 1 .. {mhwp.MAX_HARMONICS} of them")
+        if hwp is None:
+            if "hwp" not in self.metadata:
+                raise ValueError('no hwp given and no metadata["hwp"]: this TOD was not simulated behind a half-wave plate')
+            hwp = mhwp.HWP.from_metadata(self.metadata["hwp"])
+        out = self.regress(mhwp.harmonic_templates(hwp.angle(self.coords.t), ks), **regress_kw)
+        out.metadata["hwpss"] = {"harmonics": tuple(int(k) for k in ks)}
+        return out
+
     def flag_glitches(self, n_sigma=6.0, half_window=5, grow=(2, 8), n_fit=4, fill=True, ctx=None, device="cuda:0"):
         """A new TOD with glitches flagged and, with ``fill``, filled (maria_amd.flagging).  Glitches are
         detected on the signal (the sum of the fields): samples further than ``n_sigma`` robust sigmas from the running
@@ -756,6 +861,7 @@ class Simulation:
         device_output: bool = False,
         shard=None,
         device: str = "cuda:0",
+        hwp=None,
     ):
         """sim/simulation.py:76-198.  ``device_output=True`` leaves the TOD on the GPU as
         a torch tensor (a 10 k x 240 k TOD is 9.6 GB; the PCIe copy dwarfs the synthesis).
@@ -763,7 +869,16 @@ class Simulation:
         detector rows (maria_amd.dist.shard_slice) of every observation, ``"auto"`` takes both
         from an initialised ``torch.distributed`` group, ``None`` simulates every row.  Every
         detector row is independent given the shared geometry (atmosphere.py:346-373 has no
-        cross-detector term), so a shard's TOD equals the same rows of the unsharded run."""
+        cross-detector term), so a shard's TOD equals the same rows of the unsharded run.
+        ``hwp``: a maria_amd.hwp.HWP, a continuously rotating ideal half-wave plate in front of the detectors: the
+        ``map`` field becomes S_I + S_c cos 4 chi + S_s sin 4 chi (atmosphere and noise are not modulated),
+        and ``TOD.demodulate`` takes it apart again.  None: no plate, and the bits of every run are what they were."""
+        if hwp is not None:
+            from .hwp import HWP
+
+            if not isinstance(hwp, HWP):
+                raise TypeError("'hwp' must be a maria_amd.hwp.HWP")
+        self.hwp = hwp
         if cmb is not None:
             raise NotImplementedError("the CMB mixin is a follow-on row (SURVEY 8(f))")
         if isinstance(map, str):
@@ -903,11 +1018,12 @@ class Simulation:
         path.check_flags()  # RuntimeError "introduced nans" like atmosphere.py:368-369
         return out
 
-    def _sample_maps(self, obs, rows=None, krj=None, gain=None):
+    def _sample_maps(self, obs, rows=None, krj=None, gain=None, stokes_rows=None):
         """sim/map.py:76-172 on the device: one ``mrx_map_sample`` per band, [D, T] pW
         (``rows = (lo, hi)``: only this shard's detector rows).  ``krj`` (``DevicePath.krj_row_tables()``): the field in
         K_RJ instead, ``gain`` [D] multiplied in, both on the sampler's own store (``mrx_map_sample_krj``: the bits of
-        the pW field times the gain, converted by ``DevicePath.to_krj``, without the two passes over the field)."""
+        the pW field times the gain, converted by ``DevicePath.to_krj``, without the two passes over the field).
+        ``stokes_rows``: [rows, 4] (I, Q, U, V) weights of this call in place of the detectors' cached Mueller rows."""
         import torch
 
         from . import map as mmap
@@ -948,7 +1064,7 @@ class Simulation:
                 cache["steps_per_tile"] = mmap.steps_per_tile(obs.coords.t, atm._device_path().dta)
             cache["transform"] = (f64(sky_transform_stack(obs.coords.t, obs.site.latitude, obs.site.longitude).reshape(T, 9))
                                   if self.map.frame == "ra/dec" else None)
-            stokes_rows = mmap.mueller_row(dets.gamma)[:, ["IQUV".index(s) for s in self.map.stokes]]
+            mueller_rows = mmap.mueller_row(dets.gamma)[:, ["IQUV".index(s) for s in self.map.stokes]]
             covered = np.zeros(dets.n, bool)
             for b, band in enumerate(dets.bands):
                 idx = np.nonzero(dets.band_index == b)[0]
@@ -978,7 +1094,7 @@ class Simulation:
                 sm = smoothed if isinstance(smoothed, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(smoothed, np.float32))
                 entry = dict(idx=idx, contiguous=bool((np.diff(idx) == 1).all()),
                              values=sm.to(device, torch.float32)[:, channels].transpose(0, 1).contiguous(),  # [C, S, eta, xi]
-                             offsets=f32(offsets[idx]), stokes=f64(stokes_rows[idx]), idx_dev=torch.as_tensor(idx, device=device))
+                             offsets=f32(offsets[idx]), stokes=f64(mueller_rows[idx]), idx_dev=torch.as_tensor(idx, device=device))
                 if atm is not None:
                     sp = atm.spectrum
                     entry.update(tab=f32(np.stack(tables)), ap=f32(sp.side_zenith_pwv), ae=f32(sp.side_elevation))
@@ -1007,8 +1123,12 @@ class Simulation:
                 kw.update(krj=dict(e["krj_rows"], bore_el=krj["bore_el"], axis=krj["axis"], values=krj["values"]),
                           scale=None if gain is None else gain.index_select(0, e["idx_dev"]))
             dst = out[int(idx[0]) : int(idx[-1]) + 1] if e["contiguous"] else torch.empty((len(idx), T), dtype=torch.float32, device=device)
+            stokes = e["stokes"]
+            if stokes_rows is not None:
+                picked = np.asarray(stokes_rows, np.float64)[idx][:, ["IQUV".index(s) for s in self.map.stokes]]
+                stokes = torch.as_tensor(np.ascontiguousarray(picked)).to(device)
             mmap.sample_map(ctx, e["values"], self.map.eta, self.map.xi, self.map.center, cache["az"], cache["el"],
-                            e["offsets"], e["stokes"], out=dst, transform=cache["transform"],
+                            e["offsets"], stokes, out=dst, transform=cache["transform"],
                             bilinear=bool(self.map_kwargs["bilinear_sampling"]), device=device, sync=False, **kw)
             if not e["contiguous"]:
                 out.index_copy_(0, e["idx_dev"], dst)
@@ -1062,6 +1182,8 @@ class Simulation:
         metadata = {"atmosphere": False, "altitude": float(obs.site.altitude), "region": obs.site.region,
                     "latitude": obs.site.latitude, "longitude": obs.site.longitude,
                     "shard": None if rows is None else {"rank": self.shard[0], "world": self.shard[1], "rows": [lo, hi]}}
+        if self.hwp is not None:
+            metadata["hwp"] = self.hwp.to_metadata()
         has_atm = hasattr(obs, "atmosphere")
         device = torch.device(obs.atmosphere.device) if has_atm else torch.device(self.device)
         # Detector time constants: the detector lags optical power and calibration follows, so with any of
@@ -1070,7 +1192,9 @@ class Simulation:
         tau = self._time_constants(dets)
         lagged = tau is not None
         units_out = units
-        if lagged:
+        # A half-wave plate modulates optical power too: the same precedent, the map field made in pW
+        modulated = self.hwp is not None and self.map is not None
+        if lagged or modulated:
             units = "pW"
         if hi <= lo:
             # a rank past the last block of rows (dist.shard_bounds cuts blocks of 16: 144 detectors on 4 ranks are
@@ -1109,6 +1233,8 @@ class Simulation:
                 d_gain_rows = torch.as_tensor(gain.astype(np.float32), device=device) if has_gain else None
                 map_loading = self._sample_maps(obs, rows, krj=obs.atmosphere._device_path().krj_row_tables(), gain=d_gain_rows)
                 map_done = True
+            elif modulated:
+                map_loading = self._sample_hwp(obs, rows, dets)  # pW
             else:
                 map_loading = self._sample_maps(obs, rows)  # pW
         noise = None
@@ -1159,6 +1285,36 @@ class Simulation:
             tod = tod.to(units_out)
             obs.loading = tod.data
         return tod
+
+    def _sample_hwp(self, obs, rows, dets):
+        """The map field behind the half-wave plate, [D, T] pW: S_I + S_c cos 4 chi + S_s sin 4 chi from three passes of
+        the sampler -- the detectors' I weights alone, the Q / U weights of angle -gamma, those of pi / 4 - gamma --
+        combined in place by ``mrx_tod_hwp_modulate``.  A map without Q and U has S_c = S_s = 0: one pass, no launch."""
+        import torch
+
+        from . import hwp as mhwp
+        from . import map as mmap
+        from ._lib import Context
+
+        rows_i = np.zeros((dets.n, 4))
+        rows_i[:, 0] = mmap.mueller_row(dets.gamma)[:, 0]
+        out = self._sample_maps(obs, rows, stokes_rows=rows_i)
+        if not set(self.map.stokes) & {"Q", "U"}:
+            return out
+        fields = []
+        for g in (-dets.gamma, np.pi / 4 - dets.gamma):
+            w = mmap.mueller_row(g)
+            w[:, 0] = w[:, 3] = 0.0
+            fields.append(self._sample_maps(obs, rows, stokes_rows=w))
+        if hasattr(obs, "atmosphere"):
+            path = obs.atmosphere._device_path()
+            ctx, device = path.ctx, path.device
+        else:
+            device = torch.device(self.device)
+            self._noise_ctx = self._noise_ctx or Context(device.index or 0)
+            ctx = self._noise_ctx
+        ctx.set_stream(torch.cuda.current_stream(device))
+        return mhwp.modulate(out, fields[0], fields[1], mhwp.carrier(self.hwp.angle(obs.coords.t)), out=out, ctx=ctx)
 
     @staticmethod
     def _time_constants(dets):
