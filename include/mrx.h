@@ -1194,6 +1194,72 @@ int mrx_tod_segment_moments(mrx_ctx* ctx, const float* d_x, size_t ld_x, const f
 int mrx_tod_segment_flag(mrx_ctx* ctx, uint8_t* d_flags, size_t ld_f, int D, int T, const int32_t* d_bound, int S,
                          const uint8_t* d_mask, int value);
 
+/* ---- beam, pointing offset and gain per detector from a source scan (maria_amd/beamfit.py) ------------- */
+
+/* Common to the two entries below.  The pointing arguments are mrx_bin_map's, in its order (d_az, d_el [T] float32,
+ * d_transform [T][9] float64 or NULL, d_dx, d_dy [D] float32), and the offsets (ox, oy) of detector d at sample t from the
+ * frame's centre (center_phi, center_theta, radians) are the float32 numbers the binning computes for a map of that
+ * centre: steps 1-3 of mrx_map.hip in the composed form, by the same code built with the same flags
+ * (mrx_map_pointing.h: sample_const, make_det_const, sample_offsets).  With MRX_OPT_POINTING_CHAIN set both return
+ * MRX_ERR_UNSUPPORTED and launch nothing.
+ *  d_src   [T][2] float32 or NULL: the source's offsets (src_x, src_y) from that centre at every sample (a planet that
+ *          moves); NULL: the source sits at the centre, (0, 0)
+ *  (u, v) = ((double)ox - (double)src_x(t), (double)oy - (double)src_y(t))
+ * d_flags [D][ld_f] uint8 of any pitch, no alignment beyond the element's.  No atomics: the same inputs give the same
+ * bits on every call. */
+
+/* The per-sample source mask:  flags[d][t] |= value  where u u + v v <= radius radius (inside = 1) or > radius radius
+ * (inside = 0), (ox, oy) from the detector's d_dx, d_dy; float64 products and one sum, compared with the float64 product
+ * radius radius.  One streaming pass in the TOD tile (16 rows x 1024 samples); a byte is written only where a bit is set,
+ * and nothing outside the D x T flags is touched.
+ * D < 1, T < 1, ld_f < T, value outside 1 .. 255, inside not 0 or 1, a radius that is negative or not finite, a centre
+ * that is not finite, or a null d_az, d_el, d_dx, d_dy or d_flags -> MRX_ERR_INVALID with the flags untouched */
+int mrx_tod_source_flag(mrx_ctx* ctx, const float* d_az, const float* d_el, int T, const double* d_transform,
+                        const float* d_dx, const float* d_dy, int D, double center_phi, double center_theta,
+                        const float* d_src, double radius, int inside, int value, uint8_t* d_flags, size_t ld_f);
+
+/* The Gauss-Newton sums of a Gaussian beam model per detector at the trial parameters d_param [D][K] float64:
+ *   K = 5: (A, dx, dy, w, c)          q = w (u u + v v)                       w = 1 / sigma^2
+ *   K = 7: (A, dx, dy, a, b, cc, c)   q = a (u u) + 2 b (u v) + cc (v v)      a quadratic form: no angle
+ *   term = (double)x[d][t] - (double)model[d][t]  (plain (double)x without a model)
+ *   g = exp(-q / 2);   m = A g + c;   r = term - m
+ * The row's trial (dx, dy) are rounded to float32 and go through make_det_const and sample_offsets IN PLACE of
+ * d_dx[d], d_dy[d] (which this entry does not read: they may be NULL): at the optimum the offsets the fit saw are the
+ * bits the binning will see.  u, v are taken to float64 from the float32 offsets; everything after is float64, one
+ * rounding an operation (no fused multiply-add).  J = dm/dparam:
+ *   J_A = g;  J_c = 1;  m_u = -(A g) (w u | a u + b v);  m_v = -(A g) (w v | b u + cc v)
+ *   J_w = -(A g) (u u + v v) / 2       |   J_a = -(A g) (u u) / 2,  J_b = -(A g) (u v),  J_cc = -(A g) (v v) / 2
+ *   J_dx = m_u d ox/d dx + m_v d oy/d dx,   J_dy likewise, with
+ *   d(ox, oy)/d(dx, dy) = -f (dc/d. @ G):  c = (-dy s, cos r, -dx s) the detector's unit vector, s = sin r / r,
+ *   h = (cos r - s) / r^2 (its series below r^2 = 0.09, make_det_const's threshold),
+ *   dc/ddx = (-dx dy h, -dx s, -s - dx^2 h),  dc/ddy = (-s - dy^2 h, -dy s, -dx dy h),
+ *   G the sample's composed rotation (dz = c @ G, float32 as sample_const stores it) and f the asin(r)/r factor of
+ *   sample_offsets, HELD CONSTANT in the derivative.  What that neglects is of relative order |dz|^2 (the squared
+ *   angle between the detector's direction and the frame's centre); the residual r itself is exact, so the fixed point
+ *   of the iteration is the least-squares one to that order.
+ * Per row over the samples whose flag is 0 (all of them without d_flags), with nv = 1 + K (K + 1) / 2 + K:
+ *   d_count[d] = hits
+ *   d_out[d][0] = chi2 = sum r r;   d_out[d][1 ..] = the upper triangle of JtJ row by row ((0,0), (0,1) .. (K-1,K-1));
+ *   d_out[d][1 + K (K + 1) / 2 ..] = Jtr = sum J_i r
+ * Order of the sums: a thread owns 4 consecutive samples of each tile of 1024, adds its kept samples ascending, the 64
+ * lanes of a wave meet in a butterfly (xor 32 .. 1), a wave adds tile after tile of its chunk of 16 tiles, the 4 waves of
+ * a chunk are added in wave order and a row's chunks in ascending order: a function of T alone.  A wave's worth of
+ * samples without a kept one is skipped (it would add +0.0), so a scan whose window is a few per cent of the samples
+ * costs about one read of the flags.  A flagged sample's value is never read: what it holds (NaN included) changes no
+ * bit.  A row with nothing kept gives zeros and hits = 0.  Inputs are never modified.
+ *  d_x, d_model  [D][ld] float32, the model or NULL;  d_out [D][nv] float64 and d_count [D] int32, OVERWRITTEN
+ *  d_work  8-byte aligned, at least mrx_tod_beam_normal_work_bytes(D, T, K): the sums per (row, chunk), the trial
+ *          offsets in float32 and the samples' rotations G [T][6] (sample_const once per call for all rows)
+ * D < 1, T < 1, K not 5 or 7, a pitch (of an array that is given) < T, a centre that is not finite, a work buffer
+ * too small or misaligned, or a null d_x, d_az, d_el, d_param, d_out, d_count or d_work -> MRX_ERR_INVALID with the
+ * outputs untouched */
+int mrx_tod_beam_normal_work_bytes(int D, int T, int K, size_t* bytes);
+int mrx_tod_beam_normal(mrx_ctx* ctx, const float* d_x, size_t ld_x, const float* d_model, size_t ld_m,
+                        const uint8_t* d_flags, size_t ld_f, const float* d_az, const float* d_el, int T,
+                        const double* d_transform, const float* d_dx, const float* d_dy, int D, double center_phi,
+                        double center_theta, const float* d_src, const double* d_param, int K, double* d_out,
+                        int32_t* d_count, void* d_work, size_t work_bytes);
+
 /* ---- detector time constants: the one-pole lag and its exact inverse (maria_amd/time_constants.py) ------ */
 
 /* Common to the two entries below.  A detector answers optical power through a one-pole low-pass of time constant tau;

@@ -242,6 +242,9 @@ SIGNATURES = {
     "mrx_tod_segment_apply": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _i, _vp, _i, _vp, _sz]),
     "mrx_tod_segment_moments": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp, _i, _vp, _vp]),
     "mrx_tod_segment_flag": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _vp, _i]),
+    "mrx_tod_source_flag": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _d, _d, _vp, _d, _i, _i, _vp, _sz]),
+    "mrx_tod_beam_normal_work_bytes": (_i, [_i, _i, _i, _vp]),
+    "mrx_tod_beam_normal": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, _i, _d, _d, _vp, _vp, _i, _vp, _vp, _vp, _sz]),
     "mrx_tod_onepole": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _vp, _sz]),
     "mrx_tod_onepole_inverse": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _vp, _sz]),
     "mrx_tod_demodulate": (_i, [_vp, _vp, _sz, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz]),

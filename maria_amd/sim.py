@@ -822,6 +822,128 @@ class TOD:
         out._calibrator = getattr(self, "_calibrator", None)
         return out
 
+    def with_offsets(self, offsets):
+        """A TOD that shares this one's data, flags and metadata and whose ``coords.offsets`` and ``dets.offsets`` are
+        ``offsets`` [D, 2] (radians): a fitted table (``BeamFit.offsets()``) on its way into any mapper, or the nominal
+        table in place of the true one."""
+        offsets = np.array(offsets, float)
+        if offsets.shape != (self.dets.n, 2) or not np.all(np.isfinite(offsets)):
+            raise ValueError(f"offsets must be [{self.dets.n}, 2] finite numbers (radians)")
+        import copy
+
+        dets = copy.copy(self.dets)
+        dets.offsets = offsets
+        out = TOD(data=self.data, dets=dets, coords=self.coords.broadcast(offsets), units=self.units, metadata=self.metadata, flags=self.flags)
+        out._calibrator = getattr(self, "_calibrator", None)
+        return out
+
+    def beam_fwhm(self):
+        """[D] radians: the detector table's own beam FWHM, the one the simulation smooths a map with
+        (``compute_angular_fwhm`` of the mean ``primary_size`` at the detector's band centre)."""
+        from .instrument import compute_angular_fwhm
+
+        return np.asarray(compute_angular_fwhm(fwhm_0=float(self.dets.primary_size.mean()), z=np.inf, nu=self.dets.band_center), float)
+
+    def _source_frame(self, source, frame, src_track, degrees, device):
+        """(pointing dict of device tensors, centre (phi, theta) in radians, src [T, 2] or None) for ``mask_source`` and
+        ``fit_beams``: the frame's transform, the boresight and the detector table as the mappers hand them to the binning.
+        ``source`` None: the scan centre, the mean direction of the boresight in the frame."""
+        import torch
+
+        if frame not in ("ra/dec", "az/el"):
+            raise NotImplementedError(f"frame '{frame}': only 'ra/dec' and 'az/el' are built")
+        unit = np.pi / 180 if degrees else 1.0
+        T = int(np.asarray(self.coords.t).size)
+        stack = sky_transform_stack(self.coords.t, self.metadata["latitude"], self.metadata["longitude"]) if frame == "ra/dec" else None
+        if source is None:
+            from .beamfit import scan_center
+
+            center = scan_center(self.coords._baz, self.coords._bel, stack)
+        else:
+            source = np.asarray(source, float)
+            if source.shape != (2,) or not np.all(np.isfinite(source)):
+                raise ValueError("source must be (phi, theta): two finite angles")
+            center = (float(unit * source[0]), float(unit * source[1]))
+        if src_track is not None:
+            src_track = unit * np.asarray(src_track, float)
+            if src_track.shape != (T, 2) or not np.all(np.isfinite(src_track)):
+                raise ValueError(f"src_track must be [{T}, 2] finite offsets from the source's nominal position")
+            src_track = torch.as_tensor(np.ascontiguousarray(src_track, np.float32)).to(device)
+        f32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float32)).to(device)  # noqa: E731
+        point = {"az": f32(self.coords._baz), "el": f32(self.coords._bel),
+                 "transform": None if stack is None else torch.as_tensor(stack.reshape(-1, 9)).to(device),
+                 "dx": f32(self.coords.offsets[:, 0]), "dy": f32(self.coords.offsets[:, 1])}
+        return point, center, src_track
+
+    def mask_source(self, source=None, radius=None, frame="ra/dec", src_track=None, value=1, degrees=True, ctx=None, device="cuda:0"):
+        """A TOD whose flags also cover the neighbourhood of a point source (maria_amd.beamfit.source_flags):
+        ``value`` (1 .. 255) is ORed into the flags of every sample at which the detector, at its table offset, points
+        within ``radius`` of the source; the flags are created if the TOD has none.  ``source``: (phi, theta) in
+        ``frame`` ("ra/dec" or "az/el"), None for the scan centre; ``radius``: None for 3 x the largest beam FWHM of the
+        detector table; ``src_track`` [T, 2]: the source's offsets from ``source`` at every sample (a planet that
+        moves); angles in degrees with ``degrees``, else radians.  ``remove_common_mode`` and ``filter_subscans`` leave
+        flagged samples out of their fits, so a bright source masked first does not bias them.  The data are shared with
+        this TOD, which is left as it is."""
+        import torch
+
+        from . import beamfit
+
+        if radius is None:
+            radius = 3.0 * float(self.beam_fwhm().max())
+        else:
+            radius = float(radius) * (np.pi / 180 if degrees else 1.0)
+        if not (np.isfinite(radius) and radius >= 0):
+            raise ValueError(f"radius {radius}: finite and >= 0")
+        dev = torch.device(device) if self.flags is None or not torch.as_tensor(self.flags).is_cuda else torch.as_tensor(self.flags).device
+        point, center, src = self._source_frame(source, frame, src_track, degrees, dev)
+        D, T = int(self.dets.n), int(np.asarray(self.coords.t).size)
+        flags = torch.zeros((D, T), dtype=torch.uint8, device=dev) if self.flags is None else torch.as_tensor(self.flags).to(dev, torch.uint8).clone()
+        beamfit.source_flags(point, center, radius, src=src, inside=True, value=value, flags=flags, ctx=ctx)
+        metadata = dict(self.metadata)
+        metadata["source_mask"] = {"center": center, "radius": radius, "frame": frame, "value": int(value)}
+        out = TOD(data=self.data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=flags)
+        out._calibrator = getattr(self, "_calibrator", None)
+        return out
+
+    def fit_beams(self, source=None, frame="ra/dec", radius=None, elliptical=False, field=None, model=None, src_track=None, n_iter=20,
+                  degrees=True, ctx=None, device="cuda:0"):
+        """``beamfit.BeamFit``: every detector's beam, pointing offset and gain from this scan over a point source
+        (maria_amd.beamfit).  The signal is the sum of the fields (or the one ``field``), less ``model``.
+        The window is ``radius`` (None: 3 x the detector's own beam FWHM of the table, per band the largest) around the
+        source at the NOMINAL offsets of the table, ANDed with ``flags == 0``; it is fixed once.  The starting point
+        comes from ``cuts.moments`` over the window: c0 = mean, A0 = max - mean, the width from the detector table, the
+        offsets the nominal ones.  ``source``, ``frame``, ``src_track``, ``degrees`` as in :meth:`mask_source`.  Run
+        it on a source scan after ``flag_glitches`` / ``fix_jumps`` and before anything that filters (or filter with
+        the source masked); ``with_offsets(fit.offsets())`` then goes into any mapper, and ``fit.relative_gain()`` is
+        the flat field.  This TOD is left as it is."""
+        import torch
+
+        from . import beamfit, cuts
+
+        if field is not None and field not in self.data:
+            raise ValueError(f"field {field!r}: one of the fields {self.fields}")
+        fwhm = self.beam_fwhm()
+        if radius is None:
+            radius = 3.0 * float(fwhm.max())
+        else:
+            radius = float(radius) * (np.pi / 180 if degrees else 1.0)
+        if not (np.isfinite(radius) and radius > 0):
+            raise ValueError(f"radius {radius}: finite and > 0")
+        _, signal, model, flags, _, ctx = self._device_fields(model, None, ctx, device)
+        if field is not None:
+            v = self.data[field]
+            signal = (v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))).to(signal.device, torch.float32).contiguous()
+        D, T = signal.shape
+        point, center, src = self._source_frame(source, frame, src_track, degrees, signal.device)
+        window = torch.zeros((D, T), dtype=torch.uint8, device=signal.device) if flags is None else (flags != 0).to(torch.uint8)
+        beamfit.source_flags(point, center, radius, src=src, inside=False, value=1, flags=window, ctx=ctx)
+        m = cuts.moments(signal, None, flags=window, model=model, ctx=ctx)
+        mean, peak = m.mean[:, 0], m.max[:, 0]
+        w0 = torch.as_tensor((beamfit.FWHM_PER_SIGMA / fwhm) ** 2).to(signal.device)
+        init = torch.stack([peak - mean, point["dx"].to(torch.float64), point["dy"].to(torch.float64), w0, mean], dim=1)
+        return beamfit.fit(signal, point, center, init, window, model=model, src=src, elliptical=elliptical, n_iter=n_iter,
+                           groups=np.asarray(self.dets.band_index, np.int64), ctx=ctx)
+
     def to(self, units):
         """tod/tod.py:106-142 between "pW" and "K_RJ" (``mrx_tod_to_krj`` / ``mrx_tod_from_krj`` on
         every field), for a TOD that came out of ``Simulation.run``; other units stay with maria's
