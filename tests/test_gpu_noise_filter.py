@@ -1,6 +1,7 @@
 """mrx_tod_noise_filter against a float64 convolution, its symmetry, isolation and refusals, and the correlated-noise GLS
 map of MaximumLikelihoodMapper(noise_model=...) against the white-noise map, a dense float64 solve and the destriper
-(maria_amd/noise_filter.py)."""
+(maria_amd/noise_filter.py).
+The filter at the seams of its pair loop (carry registers, route edge, row lengths on block edges): tests/test_gpu_noise_seams.py."""
 
 import ctypes as C
 

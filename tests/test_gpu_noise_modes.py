@@ -1,7 +1,8 @@
 """The mode-aware GLS map (maria_amd/noise_modes.py) on the device: mrx_tod_mode_project against float64
 numpy, mrx_tod_noise_filter_modes against a float64 convolution of x - U b (and bit for bit the plain filter at m = 0),
 the whole N^-1 against its dense Woodbury form, the map against the plain noise model, the input sky and a dense solve,
-the fitted modes against the simulated couplings, and what the modes pay on a focal plane with shared noise."""
+the fitted modes against the simulated couplings, and what the modes pay on a focal plane with shared noise.
+The subtraction's tile edges and row-group loop and every row tail of the projection: tests/test_gpu_noise_seams.py."""
 
 import ctypes as C
 
