@@ -291,3 +291,222 @@ def envelope(x, G, params, flags=None, model_tod=None, src=None, spacing=SPACING
         h = (hits + 8.0).reshape((-1,) + (1,) * (base.ndim - 1))
         out.append(e + h * 2.0**-52 * ab[k])
     return tuple(out)
+
+
+# ---- the cases of the edge tests (tests/test_gpu_beamfit_edges.py, tests/test_host_beamfit.py) -----------
+
+def _frame_of(frame, t, az, el):
+    """(transform, center) as ``make_case`` takes them: az/el about (45, 60) degrees, or ra/dec about the scan's mean."""
+    from maria_amd.sim import sky_transform_stack
+
+    if frame == "az/el":
+        return None, (np.radians(45.0), np.radians(60.0))
+    transform = sky_transform_stack(t, -23.0, -67.8)
+    xyz = np.stack([np.cos(az) * np.cos(el), np.sin(az) * np.cos(el), np.sin(el)], -1).astype(np.float64)
+    mean = np.einsum("tk,tkj->tj", xyz, transform).mean(axis=0)
+    mean /= np.linalg.norm(mean)
+    return transform, (float(np.arctan2(mean[1], mean[0]) % (2 * np.pi)), float(np.arcsin(mean[2])))
+
+
+def _truth_of(rng, offsets_true, K, minor=(0.8, 0.95)):
+    """True parameters [D, K] with ``make_case``'s distributions at the true offsets."""
+    D = offsets_true.shape[0]
+    A = rng.uniform(0.8, 1.2, D)
+    c = rng.uniform(-0.05, 0.05, D)
+    if K == 5:
+        return np.stack([A, offsets_true[:, 0], offsets_true[:, 1], np.full(D, 1.0 / SIGMA**2) * rng.uniform(0.9, 1.1, D), c], axis=1)
+    sM, sm, th = SIGMA * rng.uniform(1.05, 1.25, D), SIGMA * rng.uniform(*minor, D), rng.uniform(-1.5, 1.5, D)
+    lM, lm = 1.0 / sM**2, 1.0 / sm**2
+    return np.stack([A, offsets_true[:, 0], offsets_true[:, 1], lM * np.cos(th) ** 2 + lm * np.sin(th) ** 2, np.cos(th) * np.sin(th) * (lM - lm),
+                     lM * np.sin(th) ** 2 + lm * np.cos(th) ** 2, c], axis=1)
+
+
+def _finish_case(t, az, el, transform, center, nominal, truth, src, K):
+    from maria_amd import beamfit
+
+    D, T = nominal.shape[0], t.size
+    x = beamfit.inject_source(np.zeros((D, T), np.float32), az, el, transform, center, truth, src=src)
+    model_tod = (0.3 * np.sin(np.linspace(0.0, 5.0, T))[None, :] * np.linspace(0.5, 1.5, D)[:, None]).astype(np.float32)
+    G = rotations(az, el, transform, center)
+    ox, oy = offsets(G, nominal[:, 0].astype(np.float32), nominal[:, 1].astype(np.float32))
+    if src is not None:
+        ox, oy = ox - src[None, :, 0].astype(np.float64), oy - src[None, :, 1].astype(np.float64)
+    return dict(t=t, az=az, el=el, transform=transform, center=center, nominal=nominal, truth=truth, x=x, model=model_tod, src=src, G=G,
+                dist2=ox * ox + oy * oy, K=K, D=D, T=T)
+
+
+def make_offaxis_case(frame="az/el", K=5, common=(0.0, 0.0), center_shift=0.0, drift=False, seed=0, D=D_CASE, T=T_CASE):
+    """``make_case`` with the hex-packed array moved by ``common`` (radians) on the focal plane and the frame's centre moved
+    ``center_shift`` radians off the scan (in phi, divided by cos(theta)).  The source sits still where the array's mean
+    lands in the frame (a constant float32 ``src`` track, plus ``make_case``'s linear drift with ``drift``), so the
+    detectors still cross it.  The same keys as ``make_case``; no detector that never crosses the source."""
+    from maria_amd import synthetic
+
+    rng = np.random.default_rng(seed)
+    t = 1.7e9 + np.arange(T) / 50.0
+    az, el = synthetic.daisy_scan(t, radius_deg=0.35, speed_deg_s=0.6)
+    az, el = az.astype(np.float32), el.astype(np.float32)
+    transform, center = _frame_of(frame, t, az, el)
+    center = (center[0] + center_shift / np.cos(center[1]), center[1])
+    nominal = synthetic.hex_pack(D, np.radians(0.3)) + np.asarray(common, np.float64)[None, :]
+    true_off = nominal + rng.normal(0.0, 0.15 * SIGMA, nominal.shape)
+    truth = _truth_of(rng, true_off, K)
+    G = rotations(az, el, transform, center)
+    mean = nominal.mean(axis=0)
+    mx, my = offsets(G, np.float32(mean[:1]), np.float32(mean[1:]))
+    src = np.empty((T, 2), np.float64)
+    src[:] = (mx.mean(), my.mean())
+    if drift:
+        src += np.linspace(-1.0, 1.0, T)[:, None] * np.radians([0.02, -0.015])[None, :]
+    return _finish_case(t, az, el, transform, center, nominal, truth, src.astype(np.float32), K)
+
+
+def make_hover_case(frame="az/el", K=5, D=17, T=1025, seed=0):
+    """The boresight hovers over the source (the frame's centre: no ``src``): a Lissajous of 0.05 x 0.04 degrees about
+    it, half a FWHM, with the array collapsed to within 0.2 FWHM of the boresight (the true offsets within 0.25), so that
+    every sample of every row carries weight: exp(-q / 2) lies in [0.05, 1] at the truth and at ``start_of`` (asserted),
+    and T = 1 or D = 1 still give sums of unit size.  The minor axis of K = 7 is 0.9 .. 1.0 sigma (``make_case``: 0.8 ..
+    0.95), which keeps the far corner of the Lissajous above 0.05.  The same keys as ``make_case``."""
+    from maria_amd import synthetic
+
+    rng = np.random.default_rng(seed)
+    t = 1.7e9 + np.arange(T) / 50.0
+    ph = 2.0 * np.pi * np.arange(T) / 50.0
+    az0, el0 = np.full(T, np.radians(45.0)), np.full(T, np.radians(60.0))
+    if frame == "az/el":
+        transform, center = None, (az0[0], el0[0])
+    else:  # the source is fixed on the sky where (az0, el0) points at the first sample, and the boresight tracks it
+        from maria_amd.sim import sky_transform_stack
+
+        transform = sky_transform_stack(t, -23.0, -67.8)
+        v = np.array([np.cos(az0[0]) * np.cos(el0[0]), np.sin(az0[0]) * np.cos(el0[0]), np.sin(el0[0])]) @ transform[0]
+        center = (float(np.arctan2(v[1], v[0]) % (2 * np.pi)), float(np.arcsin(v[2])))
+        b = np.einsum("j,tkj->tk", v, transform)
+        az0, el0 = np.arctan2(b[:, 1], b[:, 0]), np.arcsin(b[:, 2])
+    az = (az0 + np.radians(0.05) / np.cos(el0) * np.sin(0.37 * ph)).astype(np.float32)
+    el = (el0 + np.radians(0.04) * np.sin(0.23 * ph + 0.5)).astype(np.float32)
+    nominal = synthetic.hex_pack(D, 2 * 0.2 * FWHM)
+    true_off = nominal + np.clip(rng.normal(0.0, 0.02 * FWHM, nominal.shape), -0.035 * FWHM, 0.035 * FWHM)
+    truth = _truth_of(rng, true_off, K, minor=(0.9, 1.0))
+    case = _finish_case(t, az, el, transform, center, nominal, truth, None, K)
+    for p in (truth, start_of(case)):
+        ox, oy = offsets(case["G"], *trial_offsets(p))
+        g = model(p, ox, oy)[1]
+        assert 0.05 <= g.min() and g.max() <= 1.0, (float(g.min()), float(g.max()))
+    return case
+
+
+def dz_radius(G, dx, dy):
+    """|dz| [D, T], the r of the asin(r) / r factor: the kernel switches from its series to asinf at r^2 = 0.01."""
+    dz = np.einsum("dk,tkj->dtj", det_vector(dx, dy), G)
+    return np.hypot(dz[..., 0], dz[..., 1])
+
+
+def mutant_JtJ(x, G, params, flags=None, src=None, f_one=False, h_zero=False):
+    """JtJ [D, K, K] of ``sums`` with the Jacobian's factor asin(r) / r replaced by 1 (``f_one``) or the curvature term h
+    of dc/d(dx, dy) by 0 (``h_zero``), the offsets themselves left alone: what a kernel wrong in that term alone would
+    give.  With neither it is ``sums``' own JtJ."""
+    x = np.asarray(x, np.float64)
+    keep = np.ones(x.shape, bool) if flags is None else np.asarray(flags) == 0
+    dx, dy = trial_offsets(params)
+    ox, oy = offsets(G, dx, dy)
+    r = dz_radius(G, dx, dy)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        f = np.ones_like(r) if f_one else np.where(r > 0, np.arcsin(np.minimum(r, 1.0)) / np.where(r > 0, r, 1.0), 1.0)
+    cx, cy = det_vector_jac(dx, dy)
+    if h_zero:
+        s = np.sinc(np.hypot(dx, dy) / np.pi)
+        zero = np.zeros_like(s)
+        cx, cy = np.stack([zero, -dx * s, -s], axis=-1), np.stack([-s, -dy * s, zero], axis=-1)
+    jx = -f[..., None] * np.einsum("dk,tkj->dtj", cx, G)
+    jy = -f[..., None] * np.einsum("dk,tkj->dtj", cy, G)
+    sx, sy = (0.0, 0.0) if src is None else (np.asarray(src, np.float64)[None, :, 0], np.asarray(src, np.float64)[None, :, 1])
+    J = jacobian(params, ox - sx, oy - sy, (jx[..., 0], jx[..., 1], jy[..., 0], jy[..., 1]))
+    J = np.where(keep[..., None], J, 0.0)
+    return np.einsum("dti,dtj->dij", J, J)
+
+
+# The off-axis cases of DESIGN 3.31 at D_CASE x T_CASE: the builder's arguments, then how the kernel test runs them (model,
+# layout) and which term of the Jacobian each makes visible (the mutants of ``mutant_JtJ`` that must move JtJ).
+# Case 3 sits at (0.06, 0.04) rad: at (0.03, 0.02) h = 0 moves JtJ by 3.0 .. 43 envelopes, under 8 in five of the 18 rows.
+OFFAXIS = {
+    1: dict(make=dict(frame="az/el", K=5, center_shift=0.122), with_model=False, layout="aligned", mutants=("f_one",)),
+    2: dict(make=dict(frame="ra/dec", K=7, center_shift=0.1002), with_model=True, layout="odd", mutants=("f_one",)),
+    3: dict(make=dict(frame="az/el", K=7, common=(0.06, 0.04), drift=True), with_model=False, layout="odd", mutants=("h_zero",)),
+    4: dict(make=dict(frame="ra/dec", K=5, common=(0.2, 0.25)), with_model=True, layout="aligned", mutants=("h_zero",)),
+    5: dict(make=dict(frame="az/el", K=5, common=(0.2, 0.224)), with_model=False, layout="odd", mutants=("h_zero",)),
+    6: dict(make=dict(frame="ra/dec", K=7, common=(0.2, 0.25), center_shift=0.122, drift=True), with_model=True, layout="aligned",
+            mutants=("f_one", "h_zero")),
+}
+_OFFAXIS_MADE = {}
+
+
+def offaxis_case(number):
+    """(case, flags, params) of an off-axis case, made once and never changed: the window at the nominal offsets with
+    row 3 flagged end to end and every seventh sample of row 5 flagged with another bit; the trial point ``start_of``."""
+    if number not in _OFFAXIS_MADE:
+        case = make_offaxis_case(**OFFAXIS[number]["make"])
+        flags = window_of(case)
+        flags[3] = 1
+        flags[5, ::7] = 4
+        _OFFAXIS_MADE[number] = (case, flags, start_of(case))
+    return _OFFAXIS_MADE[number]
+
+
+def offaxis_geometry(number):
+    """Asserts that the case's samples lie where DESIGN 3.31 says they do (which branch of the kernel each takes), and
+    returns the figures as a string."""
+    case, flags, params = offaxis_case(number)
+    dx, dy = trial_offsets(params)
+    r2 = dz_radius(case["G"], dx, dy) ** 2
+    kept = r2[flags == 0]
+    d2 = dx.astype(np.float32) ** 2 + dy.astype(np.float32) ** 2  # the float32 sum the row's DetConst branches on
+    assert np.abs(d2.astype(np.float64) - 0.09).min() > 1e-5  # no row on the threshold itself, in float32 or float64
+    if number in (1, 6):
+        assert r2.min() > 0.0101  # every sample of every row past the switch to asinf
+    if number == 2:
+        assert (kept < 0.01).mean() >= 0.1 and (kept >= 0.01).mean() >= 0.1
+    if number == 3:
+        assert d2.max() < 0.09 and d2.min() > 4e-3 and r2.max() < 0.01  # both series, with a visible h
+    if number in (4, 6):
+        assert np.all(d2 >= np.float32(0.09))
+    if number == 5:
+        assert (d2 < np.float32(0.09)).sum() >= 3 and (d2 >= np.float32(0.09)).sum() >= 3
+    return (f"case {number}: |dz|^2 of kept samples {kept.min():.4f} .. {kept.max():.4f} ({100 * (kept < 0.01).mean():.0f} % below 0.01); "
+            f"dx^2 + dy^2 {d2.min():.4f} .. {d2.max():.4f} ({int((d2 < np.float32(0.09)).sum())} rows below 0.09)")
+
+
+D_PROBE, T_PROBE = 33, 2 * 16384 + 1024 + 5  # three groups of rows, the last of one row; three chunks, the last of two tiles
+# lane 0 and lane 63, q = 0 and 3, every wave's edge in a tile, both chunk seams, the last tile's byte-wise tail
+PROBE_POSITIONS = (0, 1, 3, 4, 252, 255, 256, 259, 1020, 1023, 1024, 1027, 16380, 16383, 16384, 16387, 32767, 32768, T_PROBE - 5, T_PROBE - 4,
+                   T_PROBE - 1)
+
+
+def probe_flags(rotate):
+    """(flags [D_PROBE, T_PROBE] of ones with a single 0 a live row, kept [D_PROBE] the position or -1): rows 0 .. 15, 31 and
+    32 keep PROBE_POSITIONS[(row + rotate) mod 21]; rows 16 .. 30 keep nothing, so the second group of 16 runs on row 31
+    alone."""
+    flags = np.ones((D_PROBE, T_PROBE), np.uint8)
+    kept = np.full(D_PROBE, -1)
+    for j, d in enumerate(list(range(16)) + [31, 32]):
+        kept[d] = PROBE_POSITIONS[(j + rotate) % len(PROBE_POSITIONS)]
+        flags[d, kept[d]] = 0
+    return flags, kept
+
+
+def seeded_flags(D, T, seed):
+    """[D, T] uint8: runs of random length covering about 30 % of every row plus isolated single flags (2 %), in the values
+    1, 4 and 128; below T = 8 every sample is flagged with probability 0.3."""
+    rng = np.random.default_rng(seed)
+    values = np.array([1, 4, 128], np.uint8)
+    f = np.zeros((D, T), np.uint8)
+    for d in range(D):
+        if T < 8:
+            f[d] = np.where(rng.random(T) < 0.3, rng.choice(values, T), 0)
+            continue
+        while (f[d] != 0).mean() < 0.3:
+            a = int(rng.integers(T))
+            f[d, a:a + int(rng.integers(1, max(2, min(T // 4, 400))))] = rng.choice(values)
+        single = rng.random(T) < 0.02
+        f[d, single] = rng.choice(values, int(single.sum()))
+    return f

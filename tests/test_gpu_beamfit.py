@@ -2,7 +2,8 @@
 against its float64 restatement, tests/beamfit_ref.py.
 
 Both kernels launch a plain grid, one workgroup per (tile or chunk of 16 tiles, group of 16 rows): no workgroup strides
-over work items, so there is no resident-grid case here.
+over work items, so there is no resident-grid case here.  Off the field centre, at the seams of the tile, the row group
+and the chunk, and the C entries' refusals: tests/test_gpu_beamfit_edges.py.
 
 The kernel's pointing is float32 and the reference's float64, so the sums are compared under an envelope and not a
 constant: four times the change of the reference's own sum when its offsets move by one float32 spacing, plus float64

@@ -204,6 +204,89 @@ def test_inject_source_is_the_reference_model():
     assert np.abs(got - (want + 0.25)).max() <= 2.0**-23 * np.abs(want + 0.25).max() and np.all(base == 0.25)
 
 
+MARGIN = 4.0  # the kernel tests' acceptance in envelopes (test_gpu_beamfit.MARGIN)
+
+
+def test_offaxis_builder_moves_the_array_and_the_centre():
+    """``make_offaxis_case`` with nothing moved is ``make_case``'s geometry with the source at the array's mean; moved, the
+    detectors still cross the source, which sits ``center_shift`` from the centre."""
+    plain = R.make_case("ra/dec", drift=False, K=7)
+    same = R.make_offaxis_case("ra/dec", K=7)
+    assert set(same) == set(plain) and same["center"] == plain["center"] and np.array_equal(same["az"], plain["az"])
+    assert np.array_equal(same["G"], plain["G"]) and np.array_equal(same["nominal"][:-1], plain["nominal"][:-1])
+    assert same["src"].dtype == np.float32 and same["src"].shape == (same["T"], 2) and np.all(same["src"] == same["src"][0])
+    assert np.hypot(*same["src"][0]) < np.radians(0.1)  # the array's mean over a daisy: near the scan's centre
+    for number in (2, 6):
+        case, flags, params = R.offaxis_case(number)
+        make = R.OFFAXIS[number]["make"]
+        assert set(case) == set(plain) and case["x"].dtype == np.float32 and case["x"].shape == (R.D_CASE, R.T_CASE)
+        r = np.hypot(*case["src"].astype(np.float64).T)
+        shift, common = make["center_shift"], np.hypot(*make.get("common", (0.0, 0.0)))
+        assert np.all((r > abs(shift - common) - 0.01) & (r < shift + common + 0.01)), (r.min(), r.max())  # (a triangle on the sphere)
+        assert (case["src"][-1] != case["src"][0]).all() == bool(make.get("drift"))
+        hits = (R.window_of(case) == 0).sum(axis=1)
+        assert hits.min() > 100 and case["x"].max() > 0.7  # every detector crosses the source
+        assert np.abs(case["nominal"] - np.asarray(make.get("common", (0.0, 0.0))) - same["nominal"]).max() < 1e-15
+
+
+@pytest.mark.parametrize("number", sorted(R.OFFAXIS))
+def test_offaxis_cases_show_the_jacobian_terms(number):
+    """What makes the kernel test of an off-axis case mean something: its samples lie in the branches DESIGN 3.31 names
+    (``offaxis_geometry``), and the reference with the Jacobian's asin(r)/r factor set to 1 (cases 1, 2, 6) or its
+    curvature term h set to 0 (cases 3 - 6) differs from the true one by more than 2 MARGIN envelopes in at least one
+    entry of JtJ of EVERY row with hits: a kernel wrong in that term cannot pass.  For the flag test of cases 1 and 6:
+    fewer than 1 % of the samples lie within MARGIN spacings (and within 6e-7 rad) of the radius."""
+    case, flags, params = R.offaxis_case(number)
+    print(R.offaxis_geometry(number))
+    hits, _, JtJ, _ = R.sums(case["x"], case["G"], params, flags, None, case["src"])
+    env = R.envelope(case["x"], case["G"], params, flags, None, case["src"])[1]
+    live = hits > 0
+    assert live.sum() == case["D"] - 1 and not live[3] and hits[live].min() > 100
+    assert np.array_equal(R.mutant_JtJ(case["x"], case["G"], params, flags, case["src"]), JtJ)  # (no mutation: the reference itself)
+    for name in R.OFFAXIS[number]["mutants"]:
+        mutant = R.mutant_JtJ(case["x"], case["G"], params, flags, case["src"], **{name: True})
+        ratio = (np.abs(mutant - JtJ)[live] / env[live]).reshape(int(live.sum()), -1).max(axis=1)
+        print(f"case {number} {name}: |mutant - reference| / envelope, the rows' largest entries {ratio.min():.1f} .. {ratio.max():.1f}")
+        assert ratio.min() > 2.0 * MARGIN, (name, float(ratio.min()))
+    if number in (1, 6):
+        dist = np.sqrt(case["dist2"])
+        for radius in (R.RADIUS, 0.4 * R.RADIUS):
+            assert (np.abs(dist - radius) <= 6e-7).mean() < 0.01 and 0.02 < (dist <= radius).mean() < 0.98
+
+
+@pytest.mark.parametrize("frame,K,D,T", [("az/el", 5, 1, 1), ("ra/dec", 7, 17, 5), ("az/el", 7, 33, 1025), ("ra/dec", 5, 3, 32769)])
+def test_hover_builder_keeps_every_sample_in_the_beam(frame, K, D, T):
+    """``make_hover_case`` asserts its own property (exp(-q / 2) in [0.05, 1] for every sample of every row at the truth and
+    at the trial point); here also that the sums of a single sample are of unit size and the source is in the data."""
+    case = R.make_hover_case(frame, K, D, T)
+    assert case["src"] is None and case["x"].shape == (D, T) and case["x"].dtype == np.float32 and np.isfinite(case["x"]).all()
+    assert np.hypot(*case["nominal"].T).max() <= 0.2 * R.FWHM * (1 + 1e-12) and np.sqrt(case["dist2"].max()) < 1.0 * R.FWHM
+    assert case["x"].min() >= -0.011 and case["x"].max() <= 1.26  # A g + c with A in 0.8 .. 1.2, g in 0.05 .. 1, |c| <= 0.05
+    hits, chi2, JtJ, Jtr = R.sums(case["x"][:, :1], case["G"][:1], R.start_of(case))
+    assert np.all(hits == 1) and np.all(JtJ[:, 0, 0] >= 0.05**2) and np.all(JtJ[:, -1, -1] == 1.0)
+
+
+def test_seeded_flags_and_probe_positions():
+    for D, T in ((17, 1), (17, 5), (17, 1025), (3, 32769)):
+        f = R.seeded_flags(D, T, seed=T)
+        assert f.shape == (D, T) and f.dtype == np.uint8 and set(np.unique(f)) <= {0, 1, 4, 128}
+        assert (f == 0).any()
+        if T >= 1025:
+            frac = (f != 0).mean(axis=1)
+            assert np.all((frac >= 0.3) & (frac < 0.5)) and set(np.unique(f)) == {0, 1, 4, 128}
+            single = (f[:, 1:-1] != 0) & (f[:, :-2] == 0) & (f[:, 2:] == 0)
+            assert single.sum() >= D  # isolated flags beside the runs
+    seen = set()
+    for rotate in (0, 7, 14, 3):
+        flags, kept = R.probe_flags(rotate)
+        assert flags.shape == (R.D_PROBE, R.T_PROBE) and np.array_equal((flags == 0).sum(axis=1), (kept >= 0).astype(int))
+        assert np.all(kept[16:31] == -1) and kept[31] >= 0 and kept[32] >= 0 and np.all(kept[:16] >= 0)
+        assert all(flags[d, kept[d]] == 0 for d in np.flatnonzero(kept >= 0))
+        seen |= set(kept[kept >= 0].tolist())
+    assert seen == set(R.PROBE_POSITIONS) and max(R.PROBE_POSITIONS) == R.T_PROBE - 1
+    assert -(-R.T_PROBE // 1024) == 34 and -(-34 // 16) == 3  # 34 tiles in three chunks of 16, 16 and 2
+
+
 def test_entries_are_declared_and_bound():
     from maria_amd import _lib
 
