@@ -22,8 +22,8 @@ from typing import NamedTuple
 
 import numpy as np
 
-from .flagging import _check_flags, _check_x, _context
-from .ground import _check_like
+from ._tod_args import check_like, check_min_hits, check_x
+from ._tod_args import context as _context  # under this name the host tests replace it
 
 FWHM_PER_SIGMA = float(np.sqrt(8.0 * np.log(2.0)))
 
@@ -176,7 +176,7 @@ def source_flags(pointing, center, radius, src=None, inside=True, value=1, flags
     if flags is not None:
         if not isinstance(flags, torch.Tensor) or flags.dim() != 2:
             raise ValueError(f"flags must be a [{D}, {T}] uint8 tensor")
-        ld_f = _check_flags(flags, flags, D, T)
+        ld_f = check_like(flags, "flags", flags, D, T, "uint8")
     like = az if flags is None else flags
     az, el, transform, dx, dy = _check_pointing(pointing, like, D, T, True)
     phi, theta = _check_center(center)
@@ -217,9 +217,9 @@ def normal_equations(x, pointing, center, params, flags=None, model=None, src=No
 
     from ._lib import ptr
 
-    D, T, ld_x = _check_x(x)
-    ld_f = _check_flags(flags, x, D, T) if flags is not None else 0
-    ld_m = _check_like(model, "model", x, D, T) if model is not None else 0
+    D, T, ld_x = check_x(x)
+    ld_f = check_like(flags, "flags", x, D, T, "uint8") if flags is not None else 0
+    ld_m = check_like(model, "model", x, D, T) if model is not None else 0
     az, el, transform, dx, dy = _check_pointing(pointing, x, D, T, False)
     phi, theta = _check_center(center)
     params = _check_params(params, x, D)
@@ -277,7 +277,7 @@ def fit(x, pointing, center, init, flags, model=None, src=None, elliptical=False
 
     from . import regress
 
-    D, T, _ = _check_x(x)
+    D, T, _ = check_x(x)
     if flags is None:
         raise ValueError("flags: the [D, T] uint8 window of the fit (source_flags(..., inside=False))")
     init = _check_params(init, x, D)
@@ -285,8 +285,7 @@ def fit(x, pointing, center, init, flags, model=None, src=None, elliptical=False
         raise ValueError(f"n_iter {n_iter}: an integer >= 1")
     if not (np.isfinite(float(tol)) and float(tol) > 0) or not (np.isfinite(float(lam0)) and float(lam0) > 0):
         raise ValueError("tol and lam0: finite and > 0")
-    if isinstance(min_hits, bool) or int(min_hits) != min_hits or int(min_hits) < 0:
-        raise ValueError(f"min_hits {min_hits}: an integer >= 0")
+    min_hits = check_min_hits(min_hits, allow_bool=False)
     if not 0.0 <= float(rcond) < 1.0:
         raise ValueError(f"rcond {rcond}: in [0, 1)")
     if elliptical and init.shape[1] == 5:
@@ -294,7 +293,7 @@ def fit(x, pointing, center, init, flags, model=None, src=None, elliptical=False
     if not elliptical and init.shape[1] != 5:
         raise ValueError("a [D, 7] init needs elliptical=True")
     K = int(init.shape[1])
-    floor = max(int(min_hits), K + 1)
+    floor = max(min_hits, K + 1)
     ctx = _context(ctx, x) if x.is_cuda else ctx
     az, el, transform, dx0, dy0 = _check_pointing(pointing, x, D, T, False)
     point = {"az": az, "el": el, "transform": transform}

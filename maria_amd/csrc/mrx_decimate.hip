@@ -119,8 +119,7 @@ int mrx_tod_decimate(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, 
   // as many workgroups as stay resident (8 a CU at most, fewer where the window is large); the rest of the tiles by stride
   const size_t lds_cu = ctx->lds_per_cu > 0 ? (size_t)ctx->lds_per_cu : 160 * 1024;
   const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, lds_cu / lds));
-  const long long resident = (long long)std::max(1, ctx->n_cu) * per_cu;
-  const unsigned blocks = (unsigned)std::min(n_tiles, resident);
+  const unsigned blocks = mrx_resident_blocks(ctx, n_tiles, per_cu);
   const unsigned q_magic = 0xFFFFFFFFu / (unsigned)q + 1u;  // floor(m q_magic / 2^32) = m / q for m < 2^32 / q
   hipLaunchKernelGGL(tod_decimate_kernel, dim3(blocks), dim3(kThreads), lds, ctx->stream, d_x, ld_x, T, q, q_magic, d_taps, n_taps, d_y,
                      ld_y, (int)T_out, tiles_per_row, n_tiles);

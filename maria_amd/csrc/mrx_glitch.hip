@@ -216,7 +216,7 @@ Grid tile_grid(const mrx_ctx* ctx, int D, int T) {
   Grid g;
   g.tiles_per_row = (T + kTileSamples - 1) / kTileSamples;
   g.n_tiles = (long long)D * g.tiles_per_row;
-  g.blocks = (unsigned)std::min(g.n_tiles, (long long)std::max(1, ctx->n_cu) * 8);
+  g.blocks = mrx_resident_blocks(ctx, g.n_tiles);
   return g;
 }
 

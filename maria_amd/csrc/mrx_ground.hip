@@ -134,11 +134,6 @@ __global__ __launch_bounds__(kThreads) void bin_apply_kernel(const float* x, siz
   }
 }
 
-// workgroups stride over the work items: as many as stay resident (8 a CU)
-unsigned resident_blocks(const mrx_ctx* ctx, long long items) { return (unsigned)std::min(items, (long long)std::max(1, ctx->n_cu) * 8); }
-
-bool aligned16(const void* p, size_t ld_elems) { return (((uintptr_t)p | (uintptr_t)(ld_elems * sizeof(float))) & 15u) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -158,7 +153,7 @@ int mrx_tod_bin_reduce(mrx_ctx* ctx, const float* d_x, size_t ld_x, const float*
               "ld_x, ld_m or ld_f smaller than T");
   const int groups_per_row = (K + kWaves - 1) / kWaves;
   const long long n_groups = (long long)D * groups_per_row;
-  hipLaunchKernelGGL(bin_reduce_kernel, dim3(resident_blocks(ctx, n_groups)), dim3(kThreads), 0, ctx->stream, d_x, ld_x, d_model, ld_m,
+  hipLaunchKernelGGL(bin_reduce_kernel, dim3(mrx_resident_blocks(ctx, n_groups)), dim3(kThreads), 0, ctx->stream, d_x, ld_x, d_model, ld_m,
                      d_flags, ld_f, T, d_order, n_order, d_start, K, (unsigned)std::max(min_hits, 1), d_sum, d_hits, d_template,
                      groups_per_row, n_groups);
   MRX_CHECK_LAUNCH(ctx);
@@ -176,8 +171,8 @@ int mrx_tod_bin_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T,
   MRX_REQUIRE(ctx, ld_x >= (size_t)T && ld_y >= (size_t)T, "ld_x or ld_y smaller than T");
   const int tiles_per_row = (T + kTileSamples - 1) / kTileSamples;
   const long long n_tiles = (long long)D * tiles_per_row;
-  const int wide = aligned16(d_x, ld_x) && aligned16(d_y, ld_y) && aligned16(d_bin, 0) ? 1 : 0;
-  hipLaunchKernelGGL(bin_apply_kernel, dim3(resident_blocks(ctx, n_tiles)), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, d_bin, d_template,
+  const int wide = mrx_aligned16(d_x, ld_x * sizeof(float)) && mrx_aligned16(d_y, ld_y * sizeof(float)) && mrx_aligned16(d_bin, 0) ? 1 : 0;
+  hipLaunchKernelGGL(bin_apply_kernel, dim3(mrx_resident_blocks(ctx, n_tiles)), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, d_bin, d_template,
                      K, sign, d_y, ld_y, wide, tiles_per_row, n_tiles);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;

@@ -199,8 +199,6 @@ __global__ __launch_bounds__(kModThreads) void tod_hwp_modulate_kernel(const flo
   }
 }
 
-bool aligned16(const void* p, size_t ld_bytes) { return (((uintptr_t)p | (uintptr_t)ld_bytes) & 15u) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -225,8 +223,7 @@ int mrx_tod_demodulate(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T
   // as many workgroups as stay resident (8 a CU at most, fewer where the windows are large); the rest of the tiles by stride
   const size_t lds_cu = ctx->lds_per_cu > 0 ? (size_t)ctx->lds_per_cu : 160 * 1024;
   const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, lds_cu / lds));
-  const long long resident = (long long)std::max(1, ctx->n_cu) * per_cu;
-  const unsigned blocks = (unsigned)std::min(n_tiles, resident);
+  const unsigned blocks = mrx_resident_blocks(ctx, n_tiles, per_cu);
   const unsigned q_magic = 0xFFFFFFFFu / (unsigned)q + 1u;  // floor(m q_magic / 2^32) = m / q for m < 2^32 / q
   if (d_t) {
     MRX_LDS_CAP(ctx, tod_demodulate_kernel<true>, lds);
@@ -250,11 +247,11 @@ int mrx_tod_hwp_modulate(mrx_ctx* ctx, const float* d_i, const float* d_c, const
   MRX_REQUIRE(ctx, ld_in >= (size_t)T && ld_out >= (size_t)T, "ld_in or ld_out smaller than T");
   MRX_REQUIRE(ctx, (const void*)d_out != (const void*)d_c && (const void*)d_out != (const void*)d_s, "d_out must not be d_c or d_s");
   MRX_REQUIRE(ctx, d_out != d_i || ld_out == ld_in, "in place (d_out == d_i) needs ld_out == ld_in");
-  const int wide = (aligned16(d_i, ld_in * 4) ? kWideI : 0) | (aligned16(d_c, ld_in * 4) ? kWideC : 0) | (aligned16(d_s, ld_in * 4) ? kWideS : 0) |
-                   (aligned16(d_out, ld_out * 4) ? kWideOut : 0) | (aligned16(d_carrier, 0) ? kWideCarrier : 0);
+  const int wide = (mrx_aligned16(d_i, ld_in * 4) ? kWideI : 0) | (mrx_aligned16(d_c, ld_in * 4) ? kWideC : 0) | (mrx_aligned16(d_s, ld_in * 4) ? kWideS : 0) |
+                   (mrx_aligned16(d_out, ld_out * 4) ? kWideOut : 0) | (mrx_aligned16(d_carrier, 0) ? kWideCarrier : 0);
   const int tiles_per_row = (T + kModTile - 1) / kModTile;
   const long long n_tiles = (long long)D * tiles_per_row;
-  const unsigned blocks = (unsigned)std::min(n_tiles, (long long)std::max(1, ctx->n_cu) * 8);
+  const unsigned blocks = mrx_resident_blocks(ctx, n_tiles);
   hipLaunchKernelGGL(tod_hwp_modulate_kernel, dim3(blocks), dim3(kModThreads), 0, ctx->stream, d_i, d_c, d_s, ld_in, T, d_carrier, d_out, ld_out,
                      wide, tiles_per_row, n_tiles);
   MRX_CHECK_LAUNCH(ctx);

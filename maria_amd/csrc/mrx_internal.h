@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -222,4 +223,14 @@ constexpr int kBlock = 256;
 
 static inline int mrx_ceil_div(long long a, long long b) {
   return (int)((a + b - 1) / b);
+}
+
+// the grid of a kernel whose workgroups stride over `items` work items: as many as stay resident, `per_cu` a CU
+static inline unsigned mrx_resident_blocks(const mrx_ctx* ctx, long long items, int per_cu = 8) {
+  return (unsigned)std::min(items, (long long)std::max(1, ctx->n_cu) * per_cu);
+}
+
+// may rows that start at `p`, `ld_bytes` BYTES apart (0: a single row), be moved in 16-byte pieces?
+static inline bool mrx_aligned16(const void* p, size_t ld_bytes) {
+  return (((uintptr_t)p | (uintptr_t)ld_bytes) & 15u) == 0;
 }

@@ -249,9 +249,6 @@ __global__ __launch_bounds__(kThreads) void regress_apply_kernel(const float* x,
   }
 }
 
-// workgroups stride over the work items: as many as stay resident (8 a CU)
-unsigned resident_blocks(const mrx_ctx* ctx, long long items) { return (unsigned)std::min(items, (long long)std::max(1, ctx->n_cu) * 8); }
-
 bool aligned(const void* p, size_t ld_bytes, unsigned to) { return (((uintptr_t)p | (uintptr_t)ld_bytes) & (to - 1u)) == 0; }
 
 int wide_inputs(const float* x, size_t ld_x, const float* model, size_t ld_m, const uint8_t* flags, size_t ld_f) {
@@ -283,7 +280,7 @@ int mrx_tod_column_mean(mrx_ctx* ctx, const float* d_x, size_t ld_x, const float
               "ld_x, ld_m, ld_f or ld_c smaller than T");
   const int tiles = (T + kTileSamples - 1) / kTileSamples;
   const long long n_items = (long long)G * tiles;
-  hipLaunchKernelGGL(column_mean_kernel, dim3(resident_blocks(ctx, n_items)), dim3(kThreads), 0, ctx->stream, d_x, ld_x, d_model, ld_m, d_flags,
+  hipLaunchKernelGGL(column_mean_kernel, dim3(mrx_resident_blocks(ctx, n_items)), dim3(kThreads), 0, ctx->stream, d_x, ld_x, d_model, ld_m, d_flags,
                      ld_f, D, T, d_group, d_u, d_v, d_off, d_S, d_W, d_mean, ld_c, wide_inputs(d_x, ld_x, d_model, ld_m, d_flags, ld_f), tiles,
                      n_items);
   MRX_CHECK_LAUNCH(ctx);
@@ -326,7 +323,7 @@ int mrx_tod_regress_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, in
   const int tiles_per_row = (T + kTileSamples - 1) / kTileSamples;
   const long long n_tiles = (long long)D * tiles_per_row;
   const int wide = (aligned(d_x, ld_x * 4, 16) ? kWideX : 0) | (aligned(d_B, ld_b * 4, 16) ? kWideB : 0) | (aligned(d_y, ld_y * 4, 16) ? kWideY : 0);
-  hipLaunchKernelGGL(regress_apply_kernel, dim3(resident_blocks(ctx, n_tiles)), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, d_group, G, d_B,
+  hipLaunchKernelGGL(regress_apply_kernel, dim3(mrx_resident_blocks(ctx, n_tiles)), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, d_group, G, d_B,
                      ld_b, K, d_a, sign, d_y, ld_y, wide, tiles_per_row, n_tiles);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;

@@ -238,13 +238,10 @@ __global__ __launch_bounds__(kThreads) void segment_flag_kernel(unsigned char* f
   }
 }
 
-// workgroups stride over the work items: as many as stay resident (8 a CU)
-unsigned resident_blocks(const mrx_ctx* ctx, long long items) { return (unsigned)std::min(items, (long long)std::max(1, ctx->n_cu) * 8); }
-
 template <bool kModel, bool kFlags>
 void launch_moments(mrx_ctx* ctx, const float* x, size_t ld_x, const float* model, size_t ld_m, const uint8_t* flags, size_t ld_f, int T,
                     const int32_t* bound, int S, double* stat, uint32_t* count, long long n_items) {
-  hipLaunchKernelGGL((segment_moments_kernel<kModel, kFlags>), dim3(resident_blocks(ctx, (n_items + kWaves - 1) / kWaves)), dim3(kThreads), 0,
+  hipLaunchKernelGGL((segment_moments_kernel<kModel, kFlags>), dim3(mrx_resident_blocks(ctx, (n_items + kWaves - 1) / kWaves)), dim3(kThreads), 0,
                      ctx->stream, x, ld_x, model, ld_m, flags, ld_f, T, bound, S, stat, count, n_items);
 }
 
@@ -284,8 +281,8 @@ int mrx_tod_segment_flag(mrx_ctx* ctx, uint8_t* d_flags, size_t ld_f, int D, int
   MRX_REQUIRE(ctx, ld_f >= (size_t)T, "ld_f smaller than T");
   const int tiles_per_row = (T + kFlagTile - 1) / kFlagTile;
   const long long n_tiles = (long long)D * tiles_per_row;
-  const int wide = (((uintptr_t)d_flags | (uintptr_t)ld_f) & 15u) == 0;
-  hipLaunchKernelGGL(segment_flag_kernel, dim3(resident_blocks(ctx, n_tiles)), dim3(kThreads), 0, ctx->stream, d_flags, ld_f, T, d_bound, S,
+  const int wide = mrx_aligned16(d_flags, ld_f);
+  hipLaunchKernelGGL(segment_flag_kernel, dim3(mrx_resident_blocks(ctx, n_tiles)), dim3(kThreads), 0, ctx->stream, d_flags, ld_f, T, d_bound, S,
                      d_mask, (unsigned)value, wide, tiles_per_row, n_tiles);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;

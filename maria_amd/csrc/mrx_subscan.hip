@@ -194,15 +194,12 @@ __global__ __launch_bounds__(kThreads) void segment_apply_kernel(const float* x,
   }
 }
 
-// workgroups stride over the work items: as many as stay resident (8 a CU)
-unsigned resident_blocks(const mrx_ctx* ctx, long long items) { return (unsigned)std::min(items, (long long)std::max(1, ctx->n_cu) * 8); }
-
 bool aligned(const void* p, size_t ld_bytes, unsigned to) { return (((uintptr_t)p | (uintptr_t)ld_bytes) & (to - 1u)) == 0; }
 
 template <int K>
 void launch_normal(mrx_ctx* ctx, const float* x, size_t ld_x, const float* model, size_t ld_m, const uint8_t* flags, size_t ld_f, int T,
                    const int32_t* bound, int S, double* N, double* r, uint32_t* hits, long long n_items) {
-  hipLaunchKernelGGL(segment_normal_kernel<K>, dim3(resident_blocks(ctx, (n_items + kWaves - 1) / kWaves)), dim3(kThreads), 0, ctx->stream, x, ld_x,
+  hipLaunchKernelGGL(segment_normal_kernel<K>, dim3(mrx_resident_blocks(ctx, (n_items + kWaves - 1) / kWaves)), dim3(kThreads), 0, ctx->stream, x, ld_x,
                      model, ld_m, flags, ld_f, T, bound, S, N, r, hits, n_items);
 }
 
@@ -254,7 +251,7 @@ int mrx_tod_segment_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, in
   const int tiles_per_row = (T + kTileSamples - 1) / kTileSamples;
   const long long n_tiles = (long long)D * tiles_per_row;
   const int wide = (aligned(d_x, ld_x * 4, 16) ? kWideX : 0) | (aligned(d_y, ld_y * 4, 16) ? kWideY : 0);
-  hipLaunchKernelGGL(segment_apply_kernel, dim3(resident_blocks(ctx, n_tiles)), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, d_bound, S, K,
+  hipLaunchKernelGGL(segment_apply_kernel, dim3(mrx_resident_blocks(ctx, n_tiles)), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, d_bound, S, K,
                      d_a, sign, d_y, ld_y, wide, tiles_per_row, n_tiles);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;

@@ -224,7 +224,7 @@ int mrx_tod_onepole_inverse(mrx_ctx* ctx, const float* d_y, size_t ld_y, int D, 
   const int chunk_tiles = d_x == d_y ? tiles_per_row : std::min(tiles_per_row, kChunkTiles);  // in place: a workgroup a row
   const int chunks_per_row = (tiles_per_row + chunk_tiles - 1) / chunk_tiles;
   const long long n_items = (long long)D * chunks_per_row;
-  const unsigned blocks = (unsigned)std::min(n_items, (long long)std::max(1, ctx->n_cu) * 8);  // as many as stay resident
+  const unsigned blocks = mrx_resident_blocks(ctx, n_items);  // as many as stay resident
   const int wide = (aligned(d_y, ld_y * 4, 16) ? kWideY : 0) | (aligned(d_x, ld_x * 4, 16) ? kWideX : 0);
   hipLaunchKernelGGL(onepole_inverse_kernel, dim3(blocks), dim3(kThreads), 0, ctx->stream, d_y, ld_y, T, d_a, init, d_x, ld_x, wide,
                      tiles_per_row, chunk_tiles, chunks_per_row, n_items);

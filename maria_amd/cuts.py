@@ -20,8 +20,7 @@ from typing import NamedTuple
 
 import numpy as np
 
-from .flagging import _check_flags, _check_x, _context
-from .ground import _check_like
+from ._tod_args import check_like, check_min_hits, check_x, context
 from .subscans import _check_bounds
 
 MAD_TO_SIGMA = 1.4826  # the median absolute deviation of a Gaussian is sigma / 1.4826
@@ -65,16 +64,16 @@ def moments(x, bounds=None, flags=None, model=None, ctx=None):
 
     from ._lib import ptr
 
-    D, T, ld_x = _check_x(x)
+    D, T, ld_x = check_x(x)
     d_bounds, S = _check_bounds(np.array([0, T], np.int64) if bounds is None else bounds, x)
-    ld_f = _check_flags(flags, x, D, T) if flags is not None else 0
-    ld_m = _check_like(model, "model", x, D, T) if model is not None else 0
+    ld_f = check_like(flags, "flags", x, D, T, "uint8") if flags is not None else 0
+    ld_m = check_like(model, "model", x, D, T) if model is not None else 0
     if not x.is_cuda:  # the last refusal: a host tensor gets every other one first
         raise ValueError("x must be a device tensor")
     stat = torch.empty((D, S, 8), dtype=torch.float64, device=x.device)
     count = torch.empty((D, S, 2), dtype=torch.int32, device=x.device)
-    _context(ctx, x).call("mrx_tod_segment_moments", ptr(x), ld_x, ptr(model), ld_m, ptr(flags), ld_f, D, T, ptr(d_bounds), S, ptr(stat),
-                          ptr(count))
+    context(ctx, x).call("mrx_tod_segment_moments", ptr(x), ld_x, ptr(model), ld_m, ptr(flags), ld_f, D, T, ptr(d_bounds), S, ptr(stat),
+                         ptr(count))
     count = count.to(torch.int64)
     return Moments(count[..., 0], count[..., 1], *(stat[..., i] for i in range(7)))
 
@@ -123,7 +122,7 @@ def flag_segments(flags, bounds, mask, value=1, ctx=None):
     if not isinstance(flags, torch.Tensor) or flags.dim() != 2 or flags.dtype != torch.uint8 or flags.shape[0] < 1 or flags.shape[1] < 1:
         raise ValueError("flags must be a [D, T] uint8 tensor with D >= 1 and T >= 1")
     D, T = int(flags.shape[0]), int(flags.shape[1])
-    ld_f = _check_flags(flags, flags, D, T)
+    ld_f = check_like(flags, "flags", flags, D, T, "uint8")
     d_bounds, S = _check_bounds(bounds, flags)
     if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (D, S) or mask.device != flags.device:
         raise ValueError(f"mask must be a [{D}, {S}] bool or uint8 tensor on the flags' device")
@@ -132,7 +131,7 @@ def flag_segments(flags, bounds, mask, value=1, ctx=None):
     if not flags.is_cuda:
         raise ValueError("flags must be a device tensor")
     d_mask = mask.to(torch.uint8).contiguous()
-    _context(ctx, flags).call("mrx_tod_segment_flag", ptr(flags), ld_f, D, T, ptr(d_bounds), S, ptr(d_mask), int(value))
+    context(ctx, flags).call("mrx_tod_segment_flag", ptr(flags), ld_f, D, T, ptr(d_bounds), S, ptr(d_mask), int(value))
     return flags
 
 
@@ -215,15 +214,14 @@ def _check_rules(n_sigma, n_sigma_segment, max_flagged, max_bad_segments, min_hi
     criteria = (criteria,) if isinstance(criteria, str) else tuple(criteria)
     if not criteria or any(c not in CRITERIA for c in criteria):
         raise ValueError(f"criteria {criteria}: one or more of {CRITERIA}")
-    if isinstance(min_hits, bool) or int(min_hits) != min_hits or int(min_hits) < 0:
-        raise ValueError(f"min_hits {min_hits}: an integer >= 0")
+    min_hits = check_min_hits(min_hits, allow_bool=False)
     for name, f in (("max_flagged", max_flagged), ("max_bad_segments", max_bad_segments)):
         if not 0.0 <= float(f) <= 1.0:
             raise ValueError(f"{name} {f}: in [0, 1]")
     for name, f in (("n_sigma", n_sigma), ("n_sigma_segment", n_sigma_segment)):
         if not (f is None and name == "n_sigma_segment") and not (np.isfinite(float(f)) and float(f) > 0):
             raise ValueError(f"{name} {f}: finite and > 0")
-    return criteria, max(int(min_hits), 1)
+    return criteria, max(min_hits, 1)
 
 
 def bad_segments(seg, groups=None, n_sigma_segment=5.0, min_hits=8):

@@ -12,6 +12,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._tod_args import check_out, check_x, context, row_pitch, to_numpy
+
 TILE_OUTPUTS = 256   # consecutive outputs of a row one workgroup produces (mrx_decimate.hip: kTileOutputs)
 MIN_FACTOR, MAX_FACTOR = 2, 32
 MAX_TAPS = 1025
@@ -48,15 +50,7 @@ def truncated_sums(taps, T, q):
 
 def _check(x, q, taps):
     """The refusals of ``mrx_tod_decimate`` and the taps' truncated sums, on the host: (D, T, row pitch of x)."""
-    import torch
-
-    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32:
-        raise ValueError("x must be a [D, T] float32 tensor")
-    D, T = int(x.shape[0]), int(x.shape[1])
-    if D < 1 or T < 1:
-        raise ValueError(f"x of shape {tuple(x.shape)}: need D >= 1 rows of T >= 1 samples")
-    if (T > 1 and x.stride(1) != 1) or (D > 1 and x.stride(0) < T):
-        raise ValueError("x must have unit stride along time and a row pitch >= T")
+    D, T, ld_x = check_x(x)
     if int(q) != q or not MIN_FACTOR <= int(q) <= MAX_FACTOR:
         raise ValueError(f"q {q}: an integer in {MIN_FACTOR} .. {MAX_FACTOR}")
     if taps.ndim != 1 or not 1 <= taps.size <= MAX_TAPS or taps.size % 2 == 0:
@@ -67,13 +61,7 @@ def _check(x, q, taps):
     if not np.all(sums > 0):
         j = int(np.argmin(sums))
         raise ValueError(f"the taps that meet the row at output {j} sum to {sums[j]:g}: every truncated sum must be > 0")
-    return D, T, (x.stride(0) if D > 1 else T)
-
-
-def _byte_span(t):
-    """[first, past-the-last) byte addresses a 2-D tensor's elements lie in."""
-    last = sum((n - 1) * st for n, st in zip(t.shape, t.stride()))
-    return t.data_ptr(), t.data_ptr() + (last + 1) * t.element_size()
+    return D, T, ld_x
 
 
 def upload_taps(taps, device):
@@ -94,37 +82,27 @@ def decimate(x, q, taps=None, ctx=None, out=None, device_taps=None):
     ValueError before any device call."""
     import torch
 
-    from ._lib import Context, ptr
+    from ._lib import ptr
 
     if taps is None:
         if int(q) != q or not MIN_FACTOR <= int(q) <= MAX_FACTOR:
             raise ValueError(f"q {q}: an integer in {MIN_FACTOR} .. {MAX_FACTOR}")
         h = design_taps(q)
     else:
-        h = np.ascontiguousarray(taps.detach().cpu().numpy() if isinstance(taps, torch.Tensor) else taps, np.float64)
+        h = np.ascontiguousarray(to_numpy(taps), np.float64)
     D, T, ld_x = _check(x, q, h)
     q = int(q)
     T_out = output_length(T, q)
     if out is None:
         out = torch.empty((D, T_out), dtype=torch.float32, device=x.device) if x.is_cuda else x.new_empty((D, T_out))
     else:
-        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (D, T_out) or out.device != x.device:
-            raise ValueError(f"out must be a [{D}, {T_out}] float32 tensor on x's device")
-        if (T_out > 1 and out.stride(1) != 1) or (D > 1 and out.stride(0) < T_out):
-            raise ValueError("out must have unit stride along time and a row pitch >= T_out")
-        (x0, x1), (y0, y1) = _byte_span(x), _byte_span(out)
-        if x0 < y1 and y0 < x1:
-            raise ValueError("out must not overlap x")
-    ld_y = out.stride(0) if D > 1 else T_out
+        check_out(out, x, D, T_out, length="T_out")
     if device_taps is not None and (not isinstance(device_taps, torch.Tensor) or device_taps.dtype != torch.float64
                                     or tuple(device_taps.shape) != h.shape or not device_taps.is_contiguous()
                                     or device_taps.device != x.device):
         raise ValueError(f"device_taps must be the {h.size} taps as a contiguous float64 tensor on x's device")
     if not x.is_cuda:  # the last refusal: a host tensor gets every other one first
         raise ValueError("x must be a device tensor")
-    if ctx is None:
-        ctx = Context(x.device.index or 0)
-        ctx.set_stream(torch.cuda.current_stream(x.device))
     d_taps = upload_taps(h, x.device) if device_taps is None else device_taps
-    ctx.call("mrx_tod_decimate", ptr(x), ld_x, D, T, q, ptr(d_taps), h.size, ptr(out), ld_y)
+    context(ctx, x).call("mrx_tod_decimate", ptr(x), ld_x, D, T, q, ptr(d_taps), h.size, ptr(out), row_pitch(out))
     return out

@@ -18,6 +18,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._tod_args import check_count, check_like, check_out, check_scratch_bytes, check_x, context, row_pitch, to_numpy
+
 TILE_SAMPLES = 1024  # consecutive samples of a row one workgroup flags (mrx_glitch.hip: kTileSamples)
 MAX_HALF_WINDOW = 15
 MAX_GROW = 64
@@ -25,35 +27,8 @@ MAX_FIT = 16
 MAD_TO_SIGMA = 1.4826
 
 
-def _check_x(x, name="x"):
-    """(D, T, row pitch) of a [D, T] float32 tensor with unit stride along time."""
-    import torch
-
-    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32:
-        raise ValueError(f"{name} must be a [D, T] float32 tensor")
-    D, T = int(x.shape[0]), int(x.shape[1])
-    if D < 1 or T < 1:
-        raise ValueError(f"{name} of shape {tuple(x.shape)}: need D >= 1 rows of T >= 1 samples")
-    if (T > 1 and x.stride(1) != 1) or (D > 1 and x.stride(0) < T):
-        raise ValueError(f"{name} must have unit stride along time and a row pitch >= T")
-    return D, T, (x.stride(0) if D > 1 else T)
-
-
 def _check_half_window(h):
-    if int(h) != h or not 1 <= int(h) <= MAX_HALF_WINDOW:
-        raise ValueError(f"half_window {h}: an integer in 1 .. {MAX_HALF_WINDOW}")
-    return int(h)
-
-
-def _context(ctx, x):
-    import torch
-
-    from ._lib import Context
-
-    if ctx is None:
-        ctx = Context(x.device.index or 0)
-        ctx.set_stream(torch.cuda.current_stream(x.device))
-    return ctx
+    return check_count(h, "half_window", MAX_HALF_WINDOW)
 
 
 def median_residual(x, half_window=5, ctx=None, out=None):
@@ -64,23 +39,16 @@ def median_residual(x, half_window=5, ctx=None, out=None):
     import torch
 
     from ._lib import ptr
-    from .downsample import _byte_span
 
-    D, T, ld_x = _check_x(x)
+    D, T, ld_x = check_x(x)
     h = _check_half_window(half_window)
     if out is None:
         out = torch.empty((D, T), dtype=torch.float32, device=x.device)
     else:
-        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (D, T) or out.device != x.device:
-            raise ValueError(f"out must be a [{D}, {T}] float32 tensor on x's device")
-        if (T > 1 and out.stride(1) != 1) or (D > 1 and out.stride(0) < T):
-            raise ValueError("out must have unit stride along time and a row pitch >= T")
-        (x0, x1), (y0, y1) = _byte_span(x), _byte_span(out)
-        if x0 < y1 and y0 < x1:
-            raise ValueError("out must not overlap x")
+        check_out(out, x, D, T)
     if not x.is_cuda:  # the last refusal: a host tensor gets every other one first
         raise ValueError("x must be a device tensor")
-    _context(ctx, x).call("mrx_tod_median_residual", ptr(x), ld_x, D, T, h, ptr(out), out.stride(0) if D > 1 else T)
+    context(ctx, x).call("mrx_tod_median_residual", ptr(x), ld_x, D, T, h, ptr(out), row_pitch(out))
     return out
 
 
@@ -90,14 +58,13 @@ def robust_sigma(x, half_window=5, ctx=None, scratch_bytes=1 << 30):
     (at least one), so the scratch stays within ``scratch_bytes`` however large the TOD is."""
     import torch
 
-    D, T, _ = _check_x(x)
+    D, T, _ = check_x(x)
     h = _check_half_window(half_window)
-    if int(scratch_bytes) != scratch_bytes or scratch_bytes < 1:
-        raise ValueError(f"scratch_bytes {scratch_bytes}: a positive integer")
+    scratch_bytes = check_scratch_bytes(scratch_bytes)
     if not x.is_cuda:
         raise ValueError("x must be a device tensor")
-    ctx = _context(ctx, x)
-    rows = max(1, min(D, int(scratch_bytes) // (4 * T)))
+    ctx = context(ctx, x)
+    rows = max(1, min(D, scratch_bytes // (4 * T)))
     buf = torch.empty((rows, T), dtype=torch.float32, device=x.device)
     sigma = torch.empty(D, dtype=torch.float64, device=x.device)
     for d0 in range(0, D, rows):
@@ -109,12 +76,10 @@ def robust_sigma(x, half_window=5, ctx=None, scratch_bytes=1 << 30):
 
 def _threshold(n_sigma, sigma, D):
     """[D] float32 host array float32(n_sigma * sigma); refuses what is not finite or is negative."""
-    import torch
-
     n_sigma = float(n_sigma)
     if not np.isfinite(n_sigma) or n_sigma < 0:
         raise ValueError(f"n_sigma {n_sigma}: finite and >= 0")
-    s = np.asarray(sigma.detach().cpu().numpy() if isinstance(sigma, torch.Tensor) else sigma, np.float64)
+    s = np.asarray(to_numpy(sigma), np.float64)
     if s.ndim == 0:
         s = np.full(D, float(s))
     if s.shape != (D,):
@@ -145,7 +110,7 @@ def find_glitches(x, n_sigma=6.0, half_window=5, grow=(2, 8), sigma=None, ctx=No
 
     from ._lib import ptr
 
-    D, T, ld_x = _check_x(x)
+    D, T, ld_x = check_x(x)
     h = _check_half_window(half_window)
     before, after = _check_grow(grow)
     thresh = None if sigma is None else _threshold(n_sigma, sigma, D)
@@ -153,7 +118,7 @@ def find_glitches(x, n_sigma=6.0, half_window=5, grow=(2, 8), sigma=None, ctx=No
         _threshold(n_sigma, 0.0, D)
     if not x.is_cuda:
         raise ValueError("x must be a device tensor")
-    ctx = _context(ctx, x)
+    ctx = context(ctx, x)
     if thresh is None:
         thresh = _threshold(n_sigma, robust_sigma(x, h, ctx=ctx), D)
     d_thresh = torch.as_tensor(thresh).to(x.device)
@@ -161,16 +126,6 @@ def find_glitches(x, n_sigma=6.0, half_window=5, grow=(2, 8), sigma=None, ctx=No
     count = torch.empty(D, dtype=torch.int32, device=x.device)
     ctx.call("mrx_tod_glitch_flag", ptr(x), ld_x, D, T, h, ptr(d_thresh), before, after, ptr(flags), T, ptr(count))
     return flags, count.to(torch.int64)
-
-
-def _check_flags(flags, x, D, T):
-    import torch
-
-    if not isinstance(flags, torch.Tensor) or flags.dtype != torch.uint8 or tuple(flags.shape) != (D, T) or flags.device != x.device:
-        raise ValueError(f"flags must be a [{D}, {T}] uint8 tensor on x's device")
-    if (T > 1 and flags.stride(1) != 1) or (D > 1 and flags.stride(0) < T):
-        raise ValueError("flags must have unit stride along time and a row pitch >= T")
-    return flags.stride(0) if D > 1 else T
 
 
 def gap_fill(x, flags, n_fit=4, ctx=None):
@@ -181,14 +136,13 @@ def gap_fill(x, flags, n_fit=4, ctx=None):
 
     from ._lib import ptr
 
-    D, T, ld_x = _check_x(x)
-    ld_f = _check_flags(flags, x, D, T)
-    if int(n_fit) != n_fit or not 1 <= int(n_fit) <= MAX_FIT:
-        raise ValueError(f"n_fit {n_fit}: an integer in 1 .. {MAX_FIT}")
+    D, T, ld_x = check_x(x)
+    ld_f = check_like(flags, "flags", x, D, T, "uint8")
+    n_fit = check_count(n_fit, "n_fit", MAX_FIT)
     if not x.is_cuda:
         raise ValueError("x must be a device tensor")
     filled = torch.empty(D, dtype=torch.int32, device=x.device)
-    _context(ctx, x).call("mrx_tod_gap_fill", ptr(x), ld_x, D, T, ptr(flags), ld_f, int(n_fit), ptr(filled))
+    context(ctx, x).call("mrx_tod_gap_fill", ptr(x), ld_x, D, T, ptr(flags), ld_f, n_fit, ptr(filled))
     return filled.to(torch.int64)
 
 

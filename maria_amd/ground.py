@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .flagging import _check_flags, _check_x, _context
+from ._tod_args import check_like, check_min_hits, check_out, check_sign, check_x, context, row_pitch, to_numpy
 
 MAX_BINS = 4096  # mrx_ground.hip: kMaxBins
 
@@ -54,9 +54,7 @@ def azimuth_bins(az, n_bins, lo=None, hi=None):
 
 def _check_bins(bins, n_bins, T=None):
     """The int32 host array of a [T] key; refuses entries outside -1 .. n_bins - 1 and a wrong length."""
-    import torch
-
-    b = np.asarray(bins.detach().cpu().numpy() if isinstance(bins, torch.Tensor) else bins)
+    b = np.asarray(to_numpy(bins))
     if b.ndim != 1 or b.dtype.kind not in "iu":
         raise ValueError("bins must be a one-dimensional integer array")
     if T is not None and b.size != T:
@@ -78,16 +76,6 @@ def bin_lists(bins, n_bins):
     return order, start
 
 
-def _check_like(a, name, x, D, T):
-    import torch
-
-    if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or tuple(a.shape) != (D, T) or a.device != x.device:
-        raise ValueError(f"{name} must be a [{D}, {T}] float32 tensor on x's device")
-    if (T > 1 and a.stride(1) != 1) or (D > 1 and a.stride(0) < T):
-        raise ValueError(f"{name} must have unit stride along time and a row pitch >= T")
-    return a.stride(0) if D > 1 else T
-
-
 def bin_template(x, bins, n_bins, flags=None, model=None, min_hits=1, ctx=None):
     """``(template, hits, sums)`` of a [D, T] float32 device tensor ``x`` (any row pitch) under the [T] key ``bins``
     (-1 .. n_bins - 1): [D, n_bins] device tensors, float32, int64 and float64 (the formulas are at the top of the
@@ -99,13 +87,12 @@ def bin_template(x, bins, n_bins, flags=None, model=None, min_hits=1, ctx=None):
 
     from ._lib import ptr
 
-    D, T, ld_x = _check_x(x)
+    D, T, ld_x = check_x(x)
     n_bins = _check_n_bins(n_bins)
     b = _check_bins(bins, n_bins, T)
-    ld_f = _check_flags(flags, x, D, T) if flags is not None else 0
-    ld_m = _check_like(model, "model", x, D, T) if model is not None else 0
-    if int(min_hits) != min_hits or int(min_hits) < 0:
-        raise ValueError(f"min_hits {min_hits}: an integer >= 0")
+    ld_f = check_like(flags, "flags", x, D, T, "uint8") if flags is not None else 0
+    ld_m = check_like(model, "model", x, D, T) if model is not None else 0
+    min_hits = check_min_hits(min_hits)
     if not x.is_cuda:  # the last refusal: a host tensor gets every other one first
         raise ValueError("x must be a device tensor")
     order, start = bin_lists(b, n_bins)
@@ -114,8 +101,8 @@ def bin_template(x, bins, n_bins, flags=None, model=None, min_hits=1, ctx=None):
     sums = torch.empty((D, n_bins), dtype=torch.float64, device=x.device)
     hits = torch.empty((D, n_bins), dtype=torch.int32, device=x.device)
     template = torch.empty((D, n_bins), dtype=torch.float32, device=x.device)
-    _context(ctx, x).call("mrx_tod_bin_reduce", ptr(x), ld_x, ptr(model), ld_m, ptr(flags), ld_f, D, T, ptr(d_order), int(order.size),
-                          ptr(d_start), n_bins, int(min_hits), ptr(sums), ptr(hits), ptr(template))
+    context(ctx, x).call("mrx_tod_bin_reduce", ptr(x), ld_x, ptr(model), ld_m, ptr(flags), ld_f, D, T, ptr(d_order), int(order.size),
+                         ptr(d_start), n_bins, min_hits, ptr(sums), ptr(hits), ptr(template))
     return template, hits.to(torch.int64), sums
 
 
@@ -127,28 +114,22 @@ def apply_template(x, bins, template, sign=-1, out=None, ctx=None):
     import torch
 
     from ._lib import ptr
-    from .downsample import _byte_span
 
-    D, T, ld_x = _check_x(x)
+    D, T, ld_x = check_x(x)
     if not isinstance(template, torch.Tensor) or template.dim() != 2 or template.dtype != torch.float32 or template.shape[0] != D \
             or template.device != x.device or not template.is_contiguous():
         raise ValueError(f"template must be a contiguous [{D}, K] float32 tensor on x's device")
     K = _check_n_bins(template.shape[1])
     b = _check_bins(bins, K, T)
-    if sign not in (-1, 1):
-        raise ValueError(f"sign {sign}: -1 or +1")
+    sign = check_sign(sign)
     if out is None:
         out = torch.empty((D, T), dtype=torch.float32, device=x.device)
-    elif out is not x:
-        ld = _check_like(out, "out", x, D, T)
-        (x0, x1), (y0, y1) = _byte_span(x), _byte_span(out)
-        if x0 < y1 and y0 < x1 and not (x0 == y0 and ld == ld_x):
-            raise ValueError("out must be x or must not overlap it")
+    else:
+        check_out(out, x, D, T, in_place=True)
     if not x.is_cuda:
         raise ValueError("x must be a device tensor")
     d_bin = torch.as_tensor(b).to(x.device)
-    _context(ctx, x).call("mrx_tod_bin_apply", ptr(x), ld_x, D, T, ptr(d_bin), ptr(template), K, int(sign), ptr(out),
-                          out.stride(0) if D > 1 else T)
+    context(ctx, x).call("mrx_tod_bin_apply", ptr(x), ld_x, D, T, ptr(d_bin), ptr(template), K, sign, ptr(out), row_pitch(out))
     return out
 
 
@@ -160,11 +141,10 @@ def shared_template(sums, hits, min_hits=1):
 
     if not isinstance(sums, torch.Tensor) or not isinstance(hits, torch.Tensor) or sums.dim() != 2 or sums.shape != hits.shape:
         raise ValueError("sums and hits must be [D, K] tensors of one shape")
-    if int(min_hits) != min_hits or int(min_hits) < 0:
-        raise ValueError(f"min_hits {min_hits}: an integer >= 0")
+    min_hits = check_min_hits(min_hits)
     n = hits.to(torch.float64).sum(dim=0)
     s = sums.to(torch.float64).sum(dim=0)
-    ok = n >= max(int(min_hits), 1)
+    ok = n >= max(min_hits, 1)
     row = torch.where(ok, s / torch.where(ok, n, torch.ones_like(n)), torch.zeros_like(s)).to(torch.float32)
     return row[None, :].expand(sums.shape[0], -1).contiguous()
 

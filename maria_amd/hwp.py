@@ -27,7 +27,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from .downsample import MAX_TAPS, _byte_span, _check, output_length, upload_taps
+from ._tod_args import check_like, check_x, context, overlaps, row_pitch, same_rows, to_numpy
+from .downsample import MAX_TAPS, _check, output_length, upload_taps
 
 TILE_OUTPUTS = 128  # consecutive outputs of a row one workgroup produces (mrx_hwp.hip: kTileOutputs)
 MAX_HARMONICS = 4   # of remove_hwpss: two templates each, regress.MAX_TEMPLATES is 8
@@ -97,9 +98,7 @@ def max_factor(sample_rate, f_hwp, pass_edge=0.5, stop_edge=2.0):
 
 
 def _host_taps(taps):
-    import torch
-
-    return np.ascontiguousarray(taps.detach().cpu().numpy() if isinstance(taps, torch.Tensor) else taps, np.float64)
+    return np.ascontiguousarray(to_numpy(taps), np.float64)
 
 
 def _device_carrier(c, T, device):
@@ -127,7 +126,7 @@ def demodulate(x, carrier, q, taps_t=None, taps_p=None, ctx=None, out=None, want
     of this T, raise ValueError before any device call."""
     import torch
 
-    from ._lib import Context, ptr
+    from ._lib import ptr
 
     if taps_t is None and taps_p is None:
         raise ValueError("no taps: give taps_p (design_taps(sample_rate, f_hwp)), taps_t, or both")
@@ -149,60 +148,47 @@ def demodulate(x, carrier, q, taps_t=None, taps_p=None, ctx=None, out=None, want
         outs = list(out)
         if len(outs) != 3 or (outs[0] is None) != (not want_t):
             raise ValueError("out must be (y_t, y_q, y_u), y_t None exactly where want_t is False")
-        spans = [_byte_span(x)]
+        seen = [x]
         for name, o in zip(names, outs):
             if o is None:
                 continue
-            if not isinstance(o, torch.Tensor) or o.dtype != torch.float32 or tuple(o.shape) != (D, T_out) or o.device != x.device:
-                raise ValueError(f"out's {name} must be a [{D}, {T_out}] float32 tensor on x's device")
-            if (T_out > 1 and o.stride(1) != 1) or (D > 1 and o.stride(0) < T_out):
-                raise ValueError(f"out's {name} must have unit stride along time and a row pitch >= T_out")
+            check_like(o, f"out's {name}", x, D, T_out, length="T_out")
             if D > 1 and o.stride(0) != outs[1].stride(0):
                 raise ValueError("out's tensors must have one row pitch")
-            lo, hi = _byte_span(o)
-            if any(lo < b and a < hi for a, b in spans):
+            if any(overlaps(o, a) for a in seen):
                 raise ValueError("out's tensors must overlap neither x nor each other")
-            spans.append((lo, hi))
-    ld_y = outs[1].stride(0) if D > 1 else T_out
+            seen.append(o)
     if not x.is_cuda:  # the last refusal: a host tensor gets every other one first
         raise ValueError("x must be a device tensor")
-    if ctx is None:
-        ctx = Context(x.device.index or 0)
-        ctx.set_stream(torch.cuda.current_stream(x.device))
     d_hp = upload_taps(hp, x.device)
     d_ht = (d_hp if ht is hp else upload_taps(ht, x.device)) if want_t else None
-    ctx.call("mrx_tod_demodulate", ptr(x), ld_x, D, T, q, ptr(d_carrier), ptr(d_ht), ptr(d_hp), hp.size, ptr(outs[0]), ptr(outs[1]),
-             ptr(outs[2]), ld_y)
+    context(ctx, x).call("mrx_tod_demodulate", ptr(x), ld_x, D, T, q, ptr(d_carrier), ptr(d_ht), ptr(d_hp), hp.size, ptr(outs[0]),
+                         ptr(outs[1]), ptr(outs[2]), row_pitch(outs[1]))
     return tuple(outs)
 
 
 def modulate(s_i, s_c, s_s, carrier, out=None, ctx=None):
     """float32(s_i + s_c cos 4 chi + s_s sin 4 chi), evaluated in float64 and rounded once (``mrx_tod_hwp_modulate``), of
     three [D, T] float32 device tensors of ONE row pitch and the [T, 2] float64 ``carrier``.  ``out``: None (a new
-    tensor), ``s_i`` itself (in place), or a [D, T] float32 tensor of any row pitch that overlaps none of the three.
+    tensor), ``s_i`` itself or an equal view of it (in place), or a [D, T] float32 tensor of any row pitch that overlaps none of the three.
     Everything the entry refuses raises ValueError before any device call."""
     import torch
 
     from ._lib import ptr
-    from .flagging import _check_x, _context
-    from .ground import _check_like
 
-    D, T, ld = _check_x(s_i, "s_i")
+    D, T, ld = check_x(s_i, "s_i")
     for name, a in (("s_c", s_c), ("s_s", s_s)):
-        if _check_like(a, name, s_i, D, T) != ld:
+        if check_like(a, name, s_i, D, T) != ld:
             raise ValueError("s_i, s_c and s_s must have one row pitch")
     d_carrier = _device_carrier(carrier, T, s_i.device)
     if out is None:
         out = torch.empty((D, T), dtype=torch.float32, device=s_i.device)
-    ld_out = ld if out is s_i else _check_like(out, "out", s_i, D, T)
-    o0, o1 = _byte_span(out)
-    for a in (s_c, s_s) + (() if out is s_i else (s_i,)):
-        a0, a1 = _byte_span(a)
-        if a0 < o1 and o0 < a1:
-            raise ValueError("out must be s_i or overlap none of the inputs")
+    ld_out = check_like(out, "out", s_i, D, T)
+    if any(overlaps(out, a) for a in (s_c, s_s) + (() if same_rows(out, s_i) else (s_i,))):
+        raise ValueError("out must be s_i or overlap none of the inputs")
     if not s_i.is_cuda:
         raise ValueError("s_i must be a device tensor")
-    _context(ctx, s_i).call("mrx_tod_hwp_modulate", ptr(s_i), ptr(s_c), ptr(s_s), ld, D, T, ptr(d_carrier), ptr(out), ld_out)
+    context(ctx, s_i).call("mrx_tod_hwp_modulate", ptr(s_i), ptr(s_c), ptr(s_s), ld, D, T, ptr(d_carrier), ptr(out), ld_out)
     return out
 
 

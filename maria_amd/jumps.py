@@ -22,7 +22,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from .flagging import MAD_TO_SIGMA, _check_flags, _check_grow, _check_x, _context, _threshold
+from ._tod_args import check_like, check_out, check_scratch_bytes, check_x, context, row_pitch, to_numpy
+from .flagging import MAD_TO_SIGMA, _check_grow, _threshold
 
 TILE_SAMPLES = 1024  # consecutive samples of a row one workgroup takes (mrx_jumps.hip: kTileSamples)
 MAX_WINDOW = 256
@@ -52,18 +53,9 @@ def _check_sep(sep, window):
     return int(sep)
 
 
-def _check_scratch(scratch_bytes):
-    if int(scratch_bytes) != scratch_bytes or scratch_bytes < 1:
-        raise ValueError(f"scratch_bytes {scratch_bytes}: a positive integer")
-    return int(scratch_bytes)
-
-
 def _check_lists(row_start, pos, D, x):
     """(row_start, pos) as int32 tensors on x's device, n; the lists must be what the definitions ask for."""
-    import torch
-
-    rs = np.asarray(row_start.detach().cpu().numpy() if isinstance(row_start, torch.Tensor) else row_start)
-    ps = np.asarray(pos.detach().cpu().numpy() if isinstance(pos, torch.Tensor) else pos)
+    rs, ps = np.asarray(to_numpy(row_start)), np.asarray(to_numpy(pos))
     if rs.ndim != 1 or rs.shape[0] != D + 1 or rs.dtype.kind not in "iu":
         raise ValueError(f"row_start must be {D + 1} integers")
     if ps.ndim != 1 or (ps.size and ps.dtype.kind not in "iu"):
@@ -92,24 +84,17 @@ def step_statistic(x, window, gap=0, flags=None, min_count=None, ctx=None, out=N
     import torch
 
     from ._lib import ptr
-    from .downsample import _byte_span
 
-    D, T, ld_x = _check_x(x)
+    D, T, ld_x = check_x(x)
     w, g, m = _check_window(window, gap, min_count)
-    ld_f = 0 if flags is None else _check_flags(flags, x, D, T)
+    ld_f = 0 if flags is None else check_like(flags, "flags", x, D, T, "uint8")
     if out is not None:
-        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (D, T) or out.device != x.device:
-            raise ValueError(f"out must be a [{D}, {T}] float32 tensor on x's device")
-        if (T > 1 and out.stride(1) != 1) or (D > 1 and out.stride(0) < T):
-            raise ValueError("out must have unit stride along time and a row pitch >= T")
-        (x0, x1), (y0, y1) = _byte_span(x), _byte_span(out)
-        if x0 < y1 and y0 < x1:
-            raise ValueError("out must not overlap x")
+        check_out(out, x, D, T)
     if not x.is_cuda:  # the last refusal: a host tensor gets every other one first
         raise ValueError("x must be a device tensor")
     if out is None:
         out = torch.empty((D, T), dtype=torch.float32, device=x.device)
-    _context(ctx, x).call("mrx_tod_step_stat", ptr(x), ld_x, ptr(flags), ld_f, D, T, w, g, m, ptr(out), out.stride(0) if D > 1 else T)
+    context(ctx, x).call("mrx_tod_step_stat", ptr(x), ld_x, ptr(flags), ld_f, D, T, w, g, m, ptr(out), row_pitch(out))
     return out
 
 
@@ -119,8 +104,8 @@ def robust_scale(s, scratch_bytes=1 << 30):
     (4 T)`` rows at a time (at least one)."""
     import torch
 
-    D, T, _ = _check_x(s, "s")
-    rows = max(1, min(D, _check_scratch(scratch_bytes) // (4 * T)))
+    D, T, _ = check_x(s, "s")
+    rows = max(1, min(D, check_scratch_bytes(scratch_bytes) // (4 * T)))
     scale = torch.empty(D, dtype=torch.float64, device=s.device)
     for d0 in range(0, D, rows):
         scale[d0:d0 + rows] = MAD_TO_SIGMA * torch.median(s[d0:d0 + rows].abs(), dim=1).values.double()
@@ -140,18 +125,18 @@ def find_jumps(x, window=64, n_sigma=8.0, sep=None, grow=(4, 4), flags=None, min
 
     from ._lib import ptr
 
-    D, T, ld_x = _check_x(x)
+    D, T, ld_x = check_x(x)
     w, _, m = _check_window(window, 0, min_count)
     sep = _check_sep(sep, w)
     before, after = _check_grow(grow)
-    ld_f = 0 if flags is None else _check_flags(flags, x, D, T)
+    ld_f = 0 if flags is None else check_like(flags, "flags", x, D, T, "uint8")
     thresh = None if sigma is None else _threshold(n_sigma, sigma, D)
     if sigma is None:
         _threshold(n_sigma, 0.0, D)
-    rows = max(1, min(D, _check_scratch(scratch_bytes) // (4 * T)))
+    rows = max(1, min(D, check_scratch_bytes(scratch_bytes) // (4 * T)))
     if not x.is_cuda:
         raise ValueError("x must be a device tensor")
-    ctx = _context(ctx, x)
+    ctx = context(ctx, x)
     buf = torch.empty((rows, T), dtype=torch.float32, device=x.device)
     jump_flags = torch.empty((D, T), dtype=torch.uint8, device=x.device)
     count = torch.empty(D, dtype=torch.int32, device=x.device)
@@ -183,17 +168,17 @@ def jump_heights(x, row_start, pos, window, gap, flags=None, min_count=None, ctx
 
     from ._lib import ptr
 
-    D, T, ld_x = _check_x(x)
+    D, T, ld_x = check_x(x)
     w, g, m = _check_window(window, gap, min_count)
-    ld_f = 0 if flags is None else _check_flags(flags, x, D, T)
+    ld_f = 0 if flags is None else check_like(flags, "flags", x, D, T, "uint8")
     rs, ps, n = _check_lists(row_start, pos, D, x)
     if not x.is_cuda:
         raise ValueError("x must be a device tensor")
     d_rs, d_ps = torch.as_tensor(rs).to(x.device), torch.as_tensor(ps).to(x.device)
     height = torch.zeros(n, dtype=torch.float64, device=x.device)
     ok = torch.zeros(n, dtype=torch.uint8, device=x.device)
-    _context(ctx, x).call("mrx_tod_jump_height", ptr(x), ld_x, ptr(flags), ld_f, D, T, ptr(d_rs), ptr(d_ps) if n else None, n, w, g, m,
-                          ptr(height) if n else None, ptr(ok) if n else None)
+    context(ctx, x).call("mrx_tod_jump_height", ptr(x), ld_x, ptr(flags), ld_f, D, T, ptr(d_rs), ptr(d_ps) if n else None, n, w, g, m,
+                         ptr(height) if n else None, ptr(ok) if n else None)
     return height, ok.bool()
 
 
@@ -210,28 +195,19 @@ def cumulative_heights(row_start, height):
 def fix_jumps(x, row_start, pos, height, out=None, ctx=None):
     """y = x less, at every sample, the sum of the ``height`` ([n] float64) of the row's listed jumps at or before it, as
     a [D, T] float32 device tensor: one float64 subtraction a sample, rounded once.  ``out``: a tensor to write into
-    (any row pitch); ``out=x`` works in place, any other overlap is refused.  The per-row cumulative sums are formed on the
+    (any row pitch); ``out=x`` (or an equal view of x) works in place, any other overlap is refused.  The per-row cumulative sums are formed on the
     host in float64 (``cumulative_heights``): the lists are small."""
     import torch
 
     from ._lib import ptr
-    from .downsample import _byte_span
 
-    D, T, ld_x = _check_x(x)
+    D, T, ld_x = check_x(x)
     rs, ps, n = _check_lists(row_start, pos, D, x)
-    h = np.asarray(height.detach().cpu().numpy() if isinstance(height, torch.Tensor) else height, np.float64)
+    h = np.asarray(to_numpy(height), np.float64)
     if h.shape != (n,) or not np.all(np.isfinite(h)):
         raise ValueError(f"height must be {n} finite numbers")
-    in_place = out is x or (isinstance(out, torch.Tensor) and out.data_ptr() == x.data_ptr() and out.stride() == x.stride()
-                            and out.shape == x.shape and out.dtype == x.dtype)
-    if out is not None and not in_place:
-        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (D, T) or out.device != x.device:
-            raise ValueError(f"out must be a [{D}, {T}] float32 tensor on x's device")
-        if (T > 1 and out.stride(1) != 1) or (D > 1 and out.stride(0) < T):
-            raise ValueError("out must have unit stride along time and a row pitch >= T")
-        (x0, x1), (y0, y1) = _byte_span(x), _byte_span(out)
-        if x0 < y1 and y0 < x1:
-            raise ValueError("out must be x itself or not overlap it")
+    if out is not None:
+        check_out(out, x, D, T, in_place=True)
     if not x.is_cuda:
         raise ValueError("x must be a device tensor")
     if out is None:
@@ -239,8 +215,8 @@ def fix_jumps(x, row_start, pos, height, out=None, ctx=None):
     d_rs = torch.as_tensor(rs).to(x.device)
     d_ps = torch.as_tensor(ps).to(x.device)
     d_cum = torch.as_tensor(cumulative_heights(rs, h)).to(x.device)
-    _context(ctx, x).call("mrx_tod_jump_fix", ptr(x), ld_x, D, T, ptr(d_rs), ptr(d_ps) if n else None, ptr(d_cum) if n else None, n,
-                          ptr(out), ld_x if in_place else (out.stride(0) if D > 1 else T))
+    context(ctx, x).call("mrx_tod_jump_fix", ptr(x), ld_x, D, T, ptr(d_rs), ptr(d_ps) if n else None, ptr(d_cum) if n else None, n,
+                         ptr(out), row_pitch(out))
     return out
 
 

@@ -18,23 +18,10 @@ from __future__ import annotations
 
 import numpy as np
 
-from .flagging import _check_flags, _check_x, _context
-from .ground import _check_like
+from ._tod_args import check_count, check_like, check_min_hits, check_out, check_sign, check_x, context, row_pitch
 
 MAX_GROUPS = 16    # mrx_regress.hip: kMaxGroups
 MAX_TEMPLATES = 8  # mrx_regress.hip: kMaxTemplates
-
-
-def _check_count(n, name, hi):
-    if int(n) != n or not 1 <= int(n) <= hi:
-        raise ValueError(f"{name} {n}: an integer in 1 .. {hi}")
-    return int(n)
-
-
-def _check_min_hits(min_hits):
-    if int(min_hits) != min_hits or int(min_hits) < 0:
-        raise ValueError(f"min_hits {min_hits}: an integer >= 0")
-    return int(min_hits)
 
 
 def _check_groups(groups, x, D):
@@ -68,7 +55,7 @@ def _check_templates(B, x, G, T):
 
     if not isinstance(B, torch.Tensor) or B.dim() != 3 or B.dtype != torch.float32 or B.shape[0] != G or B.shape[2] != T or B.device != x.device:
         raise ValueError(f"B must be a [{G}, K, {T}] float32 tensor on x's device")
-    K = _check_count(B.shape[1], "K", MAX_TEMPLATES)
+    K = check_count(B.shape[1], "K", MAX_TEMPLATES)
     ld = B.stride(1) if K > 1 else (B.stride(0) if G > 1 else T)
     if (T > 1 and B.stride(2) != 1) or ld < T or (G > 1 and B.stride(0) != K * ld):
         raise ValueError("B must have unit stride along time and one row pitch >= T for all of its G * K rows")
@@ -85,20 +72,20 @@ def column_mean(x, u, v, off=None, groups=None, n_groups=1, flags=None, model=No
 
     from ._lib import ptr
 
-    D, T, ld_x = _check_x(x)
-    G = _check_count(n_groups, "n_groups", MAX_GROUPS)
+    D, T, ld_x = check_x(x)
+    G = check_count(n_groups, "n_groups", MAX_GROUPS)
     u, v = _check_vector(u, "u", x, D), _check_vector(v, "v", x, D)
     off = _check_vector(off, "off", x, D) if off is not None else None
     groups = _check_groups(groups, x, D)
-    ld_f = _check_flags(flags, x, D, T) if flags is not None else 0
-    ld_m = _check_like(model, "model", x, D, T) if model is not None else 0
+    ld_f = check_like(flags, "flags", x, D, T, "uint8") if flags is not None else 0
+    ld_m = check_like(model, "model", x, D, T) if model is not None else 0
     if not x.is_cuda:  # the last refusal: a host tensor gets every other one first
         raise ValueError("x must be a device tensor")
     S = torch.empty((G, T), dtype=torch.float64, device=x.device)
     W = torch.empty((G, T), dtype=torch.float64, device=x.device)
     mean = torch.empty((G, T), dtype=torch.float32, device=x.device)
-    _context(ctx, x).call("mrx_tod_column_mean", ptr(x), ld_x, ptr(model), ld_m, ptr(flags), ld_f, D, T, ptr(groups), G, ptr(u), ptr(v),
-                          ptr(off), ptr(S), ptr(W), ptr(mean), T)
+    context(ctx, x).call("mrx_tod_column_mean", ptr(x), ld_x, ptr(model), ld_m, ptr(flags), ld_f, D, T, ptr(groups), G, ptr(u), ptr(v),
+                         ptr(off), ptr(S), ptr(W), ptr(mean), T)
     return mean, S, W
 
 
@@ -111,21 +98,21 @@ def normal_equations(x, B, groups=None, flags=None, model=None, ctx=None):
 
     from ._lib import ptr
 
-    D, T, ld_x = _check_x(x)
+    D, T, ld_x = check_x(x)
     if not isinstance(B, torch.Tensor) or B.dim() != 3:
         raise ValueError("B must be a [G, K, T] float32 tensor on x's device")
-    G = _check_count(B.shape[0], "the number of groups", MAX_GROUPS)
+    G = check_count(B.shape[0], "the number of groups", MAX_GROUPS)
     K, ld_b = _check_templates(B, x, G, T)
     groups = _check_groups(groups, x, D)
-    ld_f = _check_flags(flags, x, D, T) if flags is not None else 0
-    ld_m = _check_like(model, "model", x, D, T) if model is not None else 0
+    ld_f = check_like(flags, "flags", x, D, T, "uint8") if flags is not None else 0
+    ld_m = check_like(model, "model", x, D, T) if model is not None else 0
     if not x.is_cuda:
         raise ValueError("x must be a device tensor")
     N = torch.empty((D, K, K), dtype=torch.float64, device=x.device)
     r = torch.empty((D, K), dtype=torch.float64, device=x.device)
     hits = torch.empty((D,), dtype=torch.int32, device=x.device)
-    _context(ctx, x).call("mrx_tod_regress_normal", ptr(x), ld_x, ptr(model), ld_m, ptr(flags), ld_f, D, T, ptr(groups), G, ptr(B), ld_b, K,
-                          ptr(N), ptr(r), ptr(hits))
+    context(ctx, x).call("mrx_tod_regress_normal", ptr(x), ld_x, ptr(model), ld_m, ptr(flags), ld_f, D, T, ptr(groups), G, ptr(B), ld_b, K,
+                         ptr(N), ptr(r), ptr(hits))
     return N, r, hits.to(torch.int64)
 
 
@@ -137,28 +124,23 @@ def apply(x, B, a, groups=None, sign=-1, out=None, ctx=None):
     import torch
 
     from ._lib import ptr
-    from .downsample import _byte_span
 
-    D, T, ld_x = _check_x(x)
+    D, T, ld_x = check_x(x)
     if not isinstance(B, torch.Tensor) or B.dim() != 3:
         raise ValueError("B must be a [G, K, T] float32 tensor on x's device")
-    G = _check_count(B.shape[0], "the number of groups", MAX_GROUPS)
+    G = check_count(B.shape[0], "the number of groups", MAX_GROUPS)
     K, ld_b = _check_templates(B, x, G, T)
     a = _check_vector(a, "a", x, D, K)
     groups = _check_groups(groups, x, D)
-    if sign not in (-1, 1):
-        raise ValueError(f"sign {sign}: -1 or +1")
+    sign = check_sign(sign)
     if out is None:
         out = torch.empty((D, T), dtype=torch.float32, device=x.device)
-    elif out is not x:
-        ld = _check_like(out, "out", x, D, T)
-        (x0, x1), (y0, y1) = _byte_span(x), _byte_span(out)
-        if x0 < y1 and y0 < x1 and not (x0 == y0 and ld == ld_x):
-            raise ValueError("out must be x or must not overlap it")
+    else:
+        check_out(out, x, D, T, in_place=True)
     if not x.is_cuda:
         raise ValueError("x must be a device tensor")
-    _context(ctx, x).call("mrx_tod_regress_apply", ptr(x), ld_x, D, T, ptr(groups), G, ptr(B), ld_b, K, ptr(a), int(sign), ptr(out),
-                          out.stride(0) if D > 1 else T)
+    context(ctx, x).call("mrx_tod_regress_apply", ptr(x), ld_x, D, T, ptr(groups), G, ptr(B), ld_b, K, ptr(a), sign, ptr(out),
+                         row_pitch(out))
     return out
 
 
@@ -174,10 +156,10 @@ def solve(N, r, hits, min_hits=8, rcond=1e-10):
             or N.shape[:2] != r.shape or N.dtype != torch.float64 or r.dtype != torch.float64:
         raise ValueError("N must be a [D, K, K] and r a [D, K] float64 tensor")
     D, K = r.shape
-    _check_count(K, "K", MAX_TEMPLATES)
+    check_count(K, "K", MAX_TEMPLATES)
     if not isinstance(hits, torch.Tensor) or tuple(hits.shape) != (D,) or hits.dtype.is_floating_point:
         raise ValueError(f"hits must be {D} integers, one per row")
-    floor = max(_check_min_hits(min_hits), K)
+    floor = max(check_min_hits(min_hits), K)
     if not 0.0 <= float(rcond) < 1.0:
         raise ValueError(f"rcond {rcond}: in [0, 1)")
     diag = torch.diagonal(N, dim1=1, dim2=2)
@@ -248,10 +230,10 @@ def fit_common_mode(x, groups=None, n_groups=1, flags=None, model=None, extra=No
     The coefficients of the last fit are the result; c is not recomputed after it.  No host synchronisation."""
     import torch
 
-    D, T, _ = _check_x(x)
-    G = _check_count(n_groups, "n_groups", MAX_GROUPS)
-    n_iter = _check_count(n_iter, "n_iter", 64)
-    min_hits = _check_min_hits(min_hits)
+    D, T, _ = check_x(x)
+    G = check_count(n_groups, "n_groups", MAX_GROUPS)
+    n_iter = check_count(n_iter, "n_iter", 64)
+    min_hits = check_min_hits(min_hits)
     if extra is not None:
         extra = extra if isinstance(extra, torch.Tensor) else torch.as_tensor(np.asarray(extra))
         if extra.dim() != 2 or extra.shape[1] != T or extra.dtype != torch.float32 or not 2 + extra.shape[0] <= MAX_TEMPLATES:
@@ -259,12 +241,12 @@ def fit_common_mode(x, groups=None, n_groups=1, flags=None, model=None, extra=No
     Ke = 0 if extra is None else int(extra.shape[0])
     d_groups = _check_groups(groups, x, D)
     if flags is not None:
-        _check_flags(flags, x, D, T)
+        check_like(flags, "flags", x, D, T, "uint8")
     if model is not None:
-        _check_like(model, "model", x, D, T)
+        check_like(model, "model", x, D, T)
     if not x.is_cuda:
         raise ValueError("x must be a device tensor")
-    ctx = _context(ctx, x)
+    ctx = context(ctx, x)
     dev = x.device
     idx = torch.zeros(D, dtype=torch.int64, device=dev) if d_groups is None else d_groups.to(torch.int64)
     grouped = (idx >= 0) & (idx < G)

@@ -14,6 +14,7 @@ import time as ttime
 
 import numpy as np
 
+from . import _tod_args
 from .atmosphere import Atmosphere
 from .instrument import Instrument, Site
 
@@ -228,8 +229,7 @@ class TOD:
         if int(q) != q or not MIN_FACTOR <= int(q) <= MAX_FACTOR:
             raise ValueError(f"q {q}: an integer in {MIN_FACTOR} .. {MAX_FACTOR}")
         q = int(q)
-        h = design_taps(q) if taps is None else np.ascontiguousarray(
-            taps.detach().cpu().numpy() if isinstance(taps, torch.Tensor) else taps, np.float64)
+        h = design_taps(q) if taps is None else np.ascontiguousarray(_tod_args.to_numpy(taps), np.float64)
         data, d_taps = {}, {}  # the taps go to a device once, and one context serves every field
         for name, v in self.data.items():
             v = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
@@ -295,7 +295,7 @@ class TOD:
         if int(q) != q or not MIN_FACTOR <= int(q) <= MAX_FACTOR:
             raise ValueError(f"q {q}: an integer in {MIN_FACTOR} .. {MAX_FACTOR}")
         q = int(q)
-        host = lambda h: np.ascontiguousarray(h.detach().cpu().numpy() if isinstance(h, torch.Tensor) else h, np.float64)  # noqa: E731
+        host = lambda h: np.ascontiguousarray(_tod_args.to_numpy(h), np.float64)  # noqa: E731
         if taps_t is None and taps_p is None:
             ht = hp = mhwp.design_taps(fs, hwp.frequency)
         else:  # one of them given serves for both
@@ -475,8 +475,7 @@ class TOD:
         if bins is None:
             bins, lo, hi = ground.azimuth_bins(self.coords._baz, n_bins)
         bins = ground._check_bins(bins, n_bins, T)
-        if int(min_hits) != min_hits or int(min_hits) < 0:
-            raise ValueError(f"min_hits {min_hits}: an integer >= 0")
+        min_hits = _tod_args.check_min_hits(min_hits)
         data, signal, model, flags, into, ctx = self._device_fields(model, into, ctx, device)
         template, hits, sums = ground.bin_template(signal, bins, n_bins, flags=flags, model=model, min_hits=min_hits, ctx=ctx)
         del signal
@@ -539,7 +538,7 @@ class TOD:
 
         from . import regress
 
-        min_hits = regress._check_min_hits(min_hits)
+        min_hits = _tod_args.check_min_hits(min_hits)
         B = templates if isinstance(templates, torch.Tensor) else torch.as_tensor(np.asarray(templates))
         T = int(np.asarray(self.coords.t).size)
         if B.dim() != 2 or B.shape[1] != T or not 1 <= B.shape[0] <= regress.MAX_TEMPLATES:
@@ -574,7 +573,7 @@ class TOD:
         and ``failed_rows``.  This TOD is left as it is."""
         from . import regress
 
-        min_hits = regress._check_min_hits(min_hits)
+        min_hits = _tod_args.check_min_hits(min_hits)
         T = int(np.asarray(self.coords.t).size)
         if isinstance(groups, str):
             if groups != "band":
@@ -586,7 +585,7 @@ class TOD:
                 raise ValueError("groups must be a one-dimensional integer array with entries >= -1")
             groups = groups.astype(np.int32)
         G = 1 if groups is None or not groups.size else max(int(groups.max()) + 1, 1)
-        regress._check_count(G, "the number of groups", regress.MAX_GROUPS)
+        _tod_args.check_count(G, "the number of groups", regress.MAX_GROUPS)
         if int(poly_order) != poly_order or int(poly_order) < 0 or 2 + int(poly_order) + bool(airmass) > regress.MAX_TEMPLATES:
             raise ValueError(f"poly_order {poly_order}: an integer >= 0 with 2 + poly_order + airmass <= {regress.MAX_TEMPLATES}")
         extra = [regress.legendre_templates(T, int(poly_order))[1:]]
@@ -626,12 +625,12 @@ class TOD:
         TOD is left as it is."""
         import torch
 
-        from . import regress, subscans
+        from . import subscans
 
         if int(order) != order or not 0 <= int(order) < subscans.MAX_ORDER:
             raise ValueError(f"order {order}: an integer in 0 .. {subscans.MAX_ORDER - 1}")
         K = int(order) + 1
-        min_hits = regress._check_min_hits(min_hits)
+        min_hits = _tod_args.check_min_hits(min_hits)
         if not 0.0 <= float(rcond) < 1.0:
             raise ValueError(f"rcond {rcond}: in [0, 1)")
         T = int(np.asarray(self.coords.t).size)

@@ -20,9 +20,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from .flagging import _check_flags, _check_x, _context
-from .ground import _check_like
-from .regress import MAX_TEMPLATES, _check_count, _check_min_hits, solve
+from ._tod_args import check_count, check_like, check_min_hits, check_out, check_sign, check_x, context, row_pitch
+from .regress import MAX_TEMPLATES, solve
 
 MAX_ORDER = MAX_TEMPLATES  # mrx_subscan.hip: kMaxOrder, the number K of polynomials P_0 .. P_{K - 1}
 
@@ -101,7 +100,7 @@ def _check_coefficients(a, x, D, S):
 
     if not isinstance(a, torch.Tensor) or a.dtype != torch.float64 or a.dim() != 3 or tuple(a.shape[:2]) != (D, S) or a.device != x.device:
         raise ValueError(f"a must be a [{D}, {S}, K] float64 tensor on x's device")
-    return a.contiguous(), _check_count(a.shape[2], "K", MAX_ORDER)
+    return a.contiguous(), check_count(a.shape[2], "K", MAX_ORDER)
 
 
 def normal_equations(x, bounds, K, flags=None, model=None, ctx=None):
@@ -113,18 +112,18 @@ def normal_equations(x, bounds, K, flags=None, model=None, ctx=None):
 
     from ._lib import ptr
 
-    D, T, ld_x = _check_x(x)
-    K = _check_count(K, "K", MAX_ORDER)
+    D, T, ld_x = check_x(x)
+    K = check_count(K, "K", MAX_ORDER)
     d_bounds, S = _check_bounds(bounds, x)
-    ld_f = _check_flags(flags, x, D, T) if flags is not None else 0
-    ld_m = _check_like(model, "model", x, D, T) if model is not None else 0
+    ld_f = check_like(flags, "flags", x, D, T, "uint8") if flags is not None else 0
+    ld_m = check_like(model, "model", x, D, T) if model is not None else 0
     if not x.is_cuda:  # the last refusal: a host tensor gets every other one first
         raise ValueError("x must be a device tensor")
     N = torch.empty((D, S, K, K), dtype=torch.float64, device=x.device)
     r = torch.empty((D, S, K), dtype=torch.float64, device=x.device)
     hits = torch.empty((D, S), dtype=torch.int32, device=x.device)
-    _context(ctx, x).call("mrx_tod_segment_normal", ptr(x), ld_x, ptr(model), ld_m, ptr(flags), ld_f, D, T, ptr(d_bounds), S, K, ptr(N), ptr(r),
-                          ptr(hits))
+    context(ctx, x).call("mrx_tod_segment_normal", ptr(x), ld_x, ptr(model), ld_m, ptr(flags), ld_f, D, T, ptr(d_bounds), S, K, ptr(N), ptr(r),
+                         ptr(hits))
     return N, r, hits.to(torch.int64)
 
 
@@ -133,7 +132,7 @@ def fit(x, bounds, K, flags=None, model=None, min_hits=8, rcond=1e-10, ctx=None)
     ``regress.solve`` of ``normal_equations`` on their [D S, ..] views with its ``min_hits`` and ``rcond``: a pair that is
     not ok (fewer than max(min_hits, K) samples kept, or polynomials degenerate on them) gets a = 0.  No host
     synchronisation once ``bounds`` is on the device."""
-    min_hits = _check_min_hits(min_hits)
+    min_hits = check_min_hits(min_hits)
     if not 0.0 <= float(rcond) < 1.0:
         raise ValueError(f"rcond {rcond}: in [0, 1)")
     N, r, hits = normal_equations(x, bounds, K, flags=flags, model=model, ctx=ctx)
@@ -151,24 +150,18 @@ def apply(x, bounds, a, sign=-1, out=None, ctx=None):
     import torch
 
     from ._lib import ptr
-    from .downsample import _byte_span
 
-    D, T, ld_x = _check_x(x)
+    D, T, ld_x = check_x(x)
     d_bounds, S = _check_bounds(bounds, x)
     a, K = _check_coefficients(a, x, D, S)
-    if sign not in (-1, 1):
-        raise ValueError(f"sign {sign}: -1 or +1")
+    sign = check_sign(sign)
     if out is None:
         out = torch.empty((D, T), dtype=torch.float32, device=x.device)
-    elif out is not x:
-        ld = _check_like(out, "out", x, D, T)
-        (x0, x1), (y0, y1) = _byte_span(x), _byte_span(out)
-        if x0 < y1 and y0 < x1 and not (x0 == y0 and ld == ld_x):
-            raise ValueError("out must be x or must not overlap it")
+    else:
+        check_out(out, x, D, T, in_place=True)
     if not x.is_cuda:
         raise ValueError("x must be a device tensor")
-    _context(ctx, x).call("mrx_tod_segment_apply", ptr(x), ld_x, D, T, ptr(d_bounds), S, K, ptr(a), int(sign), ptr(out),
-                          out.stride(0) if D > 1 else T)
+    context(ctx, x).call("mrx_tod_segment_apply", ptr(x), ld_x, D, T, ptr(d_bounds), S, K, ptr(a), sign, ptr(out), row_pitch(out))
     return out
 
 

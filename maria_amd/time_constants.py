@@ -16,8 +16,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .flagging import _check_x, _context
-from .ground import _check_like
+from ._tod_args import check_out, check_x, context, row_pitch, to_numpy
 
 INITS = {"zero": 0, "steady": 1}  # mrx.h: init
 
@@ -56,7 +55,7 @@ def _check_poles(a, x, D):
     """The [D] float64 tensor of the poles on x's device: every one finite and in [0, 1)."""
     import torch
 
-    host = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    host = np.asarray(to_numpy(a))
     if host.ndim != 1 or host.shape[0] != D or host.dtype != np.float64:
         raise ValueError(f"a must be a [{D}] float64 array or tensor: one pole a row")
     if not np.all((host >= 0.0) & (host < 1.0)):  # (a NaN compares false)
@@ -70,21 +69,17 @@ def _run(entry, x, a, init, out, ctx):
     import torch
 
     from ._lib import ptr
-    from .downsample import _byte_span
 
-    D, T, ld_x = _check_x(x)
+    D, T, ld_x = check_x(x)
     d_a = _check_poles(a, x, D)
     init = _check_init(init)
     if out is None:
         out = torch.empty((D, T), dtype=torch.float32, device=x.device)
-    elif out is not x:
-        ld = _check_like(out, "out", x, D, T)
-        (x0, x1), (y0, y1) = _byte_span(x), _byte_span(out)
-        if x0 < y1 and y0 < x1 and not (x0 == y0 and ld == ld_x):
-            raise ValueError("out must be x or must not overlap it")
+    else:
+        check_out(out, x, D, T, in_place=True)
     if not x.is_cuda:  # the last refusal: a host tensor gets every other one first
         raise ValueError("x must be a device tensor")
-    _context(ctx, x).call(entry, ptr(x), ld_x, D, T, ptr(d_a), init, ptr(out), out.stride(0) if D > 1 else T)
+    context(ctx, x).call(entry, ptr(x), ld_x, D, T, ptr(d_a), init, ptr(out), row_pitch(out))
     return out
 
 
