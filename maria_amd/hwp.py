@@ -245,6 +245,4 @@ def inject_hwpss(tod, amplitudes, hwp=None, into=None, ctx=None, device="cuda:0"
     data, _, _, _, into, ctx = tod._device_fields(None, into, ctx, device)
     x = data[into]
     regress.apply(x, torch.as_tensor(B).to(x.device)[None], torch.as_tensor(np.ascontiguousarray(a)).to(x.device), sign=+1, out=x, ctx=ctx)
-    out = type(tod)(data=data, dets=tod.dets, coords=tod.coords, units=tod.units, metadata=dict(tod.metadata), flags=tod.flags)
-    out._calibrator = getattr(tod, "_calibrator", None)
-    return out
+    return tod._derived(data=data, record={})

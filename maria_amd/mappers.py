@@ -22,6 +22,7 @@ import torch
 from . import destripe_prior, noise_estimate, noise_filter, noise_modes
 from ._lib import Context, MrxSkyMap, ptr
 from .map import ProjectionMap
+from .tod import field_sum, sky_transform_stack
 
 logger = logging.getLogger("maria")
 
@@ -128,8 +129,6 @@ class _GridMapper:
         The weight is the pre-processing's window times ``tod.flags == 0`` where the TOD has flags.
         ``unit_i_response``: the Stokes weights over the detector's I weight (its Mueller [0, 0]).  ``with_operator``:
         ``(TodInputs, op)``, op the pre-processing as a ``tod_processing.PreprocessOperator`` (no steps: the identity)."""
-        from .sim import sky_transform_stack
-
         dev = self.device
         dets, coords = tod.dets, tod.coords
         f32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float32)).to(dev)  # noqa: E731
@@ -146,12 +145,7 @@ class _GridMapper:
             if not np.all(done.weight == 1.0):  # the window is the processed TOD's weight (processing.py:193)
                 weight = torch.as_tensor(np.ascontiguousarray(done.weight, np.float32)).to(dev).expand(signal.shape[0], -1).contiguous()
         else:
-            signal = None
-            for field in tod.data.values():  # tod.signal: the sum of the fields
-                f = field if isinstance(field, torch.Tensor) else torch.as_tensor(field)
-                f = f.to(dev, torch.float32)
-                signal = f.clone() if signal is None else signal.add_(f)
-            signal = signal.contiguous()
+            signal = field_sum(tod.data.values(), dev)  # tod.signal, on the mapper's own device
         if getattr(tod, "flags", None) is not None:  # flagged samples get no weight (TOD.flag_glitches)
             good = (torch.as_tensor(tod.flags).to(dev) == 0).to(torch.float32)
             weight = good if weight is None else weight * good

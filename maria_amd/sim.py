@@ -14,94 +14,18 @@ import time as ttime
 
 import numpy as np
 
-from . import _tod_args
 from .atmosphere import Atmosphere
 from .instrument import Instrument, Site
+from .tod import TOD, Coordinates, sky_transform_stack  # noqa: F401  (their home until DESIGN 3.33; imported from here still)
 
 logger = logging.getLogger("maria")
 
 MIN_ELEVATION_WARN = 10  # sim/observation.py
 MIN_ELEVATION_ERROR = 5
-HALF_PI_F32 = np.float32(np.pi / 2)
 
 
 class PointingError(Exception):
     """maria/errors/__init__.py:8."""
-
-
-class Coordinates:
-    """az/el pointing of a boresight or of detectors around it (host-side numpy).
-
-    The slice of ``maria.coords.Coordinates`` the atmosphere set-up needs:
-    ``downsample`` (coordinates.py:286-304), ``broadcast`` to detector offsets in
-    float32 like jax does (coordinates.py:378-386, transforms.py:10-29) and the
-    unit-height ground projection (coordinates.py:333-349)."""
-
-    def __init__(self, t, az, el, offsets=None):
-        self.t = np.asarray(t, float)
-        self._baz, self._bel = np.asarray(az, float), np.asarray(el, float)
-        self.offsets = None if offsets is None else np.atleast_2d(np.asarray(offsets, float))
-        self._azel = None
-
-    def _pointing(self):
-        if self.offsets is None:
-            return self._baz, self._bel
-        if self._azel is None:
-            f32 = np.float32
-            dx, dy = self.offsets[:, 0, None].astype(f32), self.offsets[:, 1, None].astype(f32)
-            r = np.sqrt(dx * dx + dy * dy)
-            p = np.arctan2(-dx, -dy)
-            a = self._bel[None].astype(f32) - HALF_PI_F32
-            a_re, a_im = np.sin(r) * np.cos(p), np.cos(r)
-            re = a_re * np.cos(a) - a_im * np.sin(a)
-            im = a_re * np.sin(a) + a_im * np.cos(a)
-            self._azel = (np.arctan2(np.sin(r) * np.sin(p), re) + self._baz[None].astype(f32), np.arcsin(im))
-        return self._azel
-
-    @property
-    def az(self):
-        return self._pointing()[0]
-
-    @property
-    def el(self):
-        return self._pointing()[1]
-
-    @property
-    def shape(self):
-        return self.az.shape
-
-    def downsample(self, timestep):
-        ds_t = np.arange(self.t.min(), self.t.max(), timestep)
-        return Coordinates(ds_t, np.interp(ds_t, self.t, self._baz), np.interp(ds_t, self.t, self._bel))
-
-    def broadcast(self, offsets):
-        return Coordinates(self.t, self._baz, self._bel, offsets=offsets)
-
-    def project_unit(self):
-        """(cos az / tan el, sin az / tan el) [.., Ta, 2]: ``project(z=1)`` from the origin."""
-        az, el = self._pointing()
-        tan_el = np.tan(el)
-        return np.stack([np.cos(az) / tan_el, np.sin(az) / tan_el], axis=-1).astype(np.float64)
-
-
-def sky_transform_stack(t, latitude_deg, longitude_deg):
-    """[T, 3, 3] float64 with ``xyz(az, el) @ M[t] = xyz(ra, dec)``: the per-sample transform
-    coords/coordinates.py:184-236 fits to astropy's AltAz -> ICRS at fiducial times and
-    interpolates.  astropy is not available to this package, so the rotation is the
-    textbook one -- horizon to hour angle/declination at the site's latitude, then the local
-    sidereal angle (GMST of IAU 1982 + longitude) -- without precession, nutation, aberration
-    or refraction: coordinates "of date", self-consistent within a simulation.  A caller with
-    astropy hands its own stack to ``mrx_map_sample``."""
-    t = np.asarray(t, float)
-    lat = np.radians(latitude_deg)
-    days = t / 86400.0 + 2440587.5 - 2451545.0
-    lst = np.radians(15.0 * ((18.697374558 + 24.06570982441908 * days) % 24.0) + longitude_deg)
-    A = np.array([[-np.sin(lat), 0.0, np.cos(lat)], [0.0, -1.0, 0.0], [np.cos(lat), 0.0, np.sin(lat)]])  # (N, E, U) -> hour-angle frame
-    B = np.zeros((len(t), 3, 3))
-    B[:, 0, 0], B[:, 0, 1] = np.cos(lst), np.sin(lst)
-    B[:, 1, 0], B[:, 1, 1] = np.sin(lst), -np.cos(lst)
-    B[:, 2, 2] = 1.0
-    return A[None] @ B
 
 
 class Plan:
@@ -162,801 +86,6 @@ class Observation:
             else:
                 self.atmosphere = Atmosphere(model=atmosphere, timestamp=float(plan.time.mean()), region=site.region, altitude=site.altitude, **atmosphere_kwargs)
         self.loading = {}
-
-
-class TOD:
-    """The slice of ``maria.tod.TOD`` this path fills: ``data`` (dict of [ndet, nt]
-    float32 arrays, numpy or device tensors), ``dets``, ``coords``, ``units``, ``metadata``.  ``flags``: None, or a
-    [ndet, nt] uint8 device tensor whose nonzero entries mark samples the mappers give no weight (``flag_glitches``,
-    ``fix_jumps``, ``filter_subscans``, ``cut``)."""
-
-    def __init__(self, data, dets, coords, units="pW", metadata=None, flags=None):
-        self.data, self.dets, self.coords, self.units = data, dets, coords, units
-        self.metadata = metadata or {}
-        self.flags = flags
-
-    @property
-    def fields(self):
-        return list(self.data)
-
-    @property
-    def signal(self):
-        return sum(self.data.values())
-
-    @property
-    def time(self):
-        return self.coords.t
-
-    def psd(self, nperseg=None, field=None, ctx=None, device="cuda:0"):
-        """The Welch spectrum of every detector's row of ``field`` (default: the signal, the sum of the fields) on the
-        device: ``(f, psd)``, maria_amd.noise_estimate.welch."""
-        import torch
-
-        from .noise_estimate import welch
-
-        fields = [self.data[field]] if field is not None else list(self.data.values())
-        x = None
-        for v in fields:
-            v = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
-            dev = v.device if v.is_cuda else torch.device(device)
-            x = v.to(dev, torch.float32).clone() if x is None else x.add_(v.to(x.device, torch.float32))
-        t = np.asarray(self.coords.t, float)
-        fs = (t.size - 1) / (t[-1] - t[0])
-        return welch(x.contiguous(), fs, nperseg=nperseg, ctx=ctx)
-
-    def fit_noise(self, nperseg=None, field=None, f_min=None, f_max=None, n_bins=32, ctx=None, device="cuda:0"):
-        """Per detector, the noise law fitted to :meth:`psd` (maria_amd.noise_estimate.fit_noise): a dict of ``white``,
-        ``knee``, ``alpha``, ``sigma`` and ``knee_at_floor`` tensors."""
-        from .noise_estimate import fit_noise
-
-        f, p = self.psd(nperseg=nperseg, field=field, ctx=ctx, device=device)
-        return fit_noise(f, p, f_min=f_min, f_max=f_max, n_bins=n_bins)
-
-    def downsample(self, q, taps=None, ctx=None, device="cuda:0"):
-        """A new TOD at 1 / q of the sample rate (q = 2 .. 32): every field low-passed and decimated on the device by
-        maria_amd.downsample.decimate (``taps`` None: scipy.signal.decimate's FIR for q), one field at a time, into
-        float32 device tensors; the boresight picked at every q-th sample (it is smooth, and picking keeps azimuth wraps
-        out of the filter), output sample j at time t[j q].  ``dets``, ``units`` and ``metadata`` are carried over and
-        ``metadata["downsample"]`` records the factor, the tap count and the new sample rate.  The pW <-> K_RJ
-        calibrator is NOT carried over (it closes over full-rate tables): ``to()`` on the result raises
-        NotImplementedError, so convert units first.  ``flags`` become ``flagging.downsample_flags(flags, q)``: an output is
-        flagged if any input within q samples of it is.  This TOD is left as it is."""
-        import torch
-
-        from ._lib import Context
-        from .downsample import MAX_FACTOR, MIN_FACTOR, decimate, design_taps, upload_taps
-
-        if int(q) != q or not MIN_FACTOR <= int(q) <= MAX_FACTOR:
-            raise ValueError(f"q {q}: an integer in {MIN_FACTOR} .. {MAX_FACTOR}")
-        q = int(q)
-        h = design_taps(q) if taps is None else np.ascontiguousarray(_tod_args.to_numpy(taps), np.float64)
-        data, d_taps = {}, {}  # the taps go to a device once, and one context serves every field
-        for name, v in self.data.items():
-            v = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
-            dev = v.device if v.is_cuda else torch.device(device)
-            x = v.to(dev, torch.float32)
-            if x.dim() == 2 and x.shape[1] > 1 and x.stride(1) != 1:
-                x = x.contiguous()
-            if ctx is None:
-                ctx = Context(dev.index or 0)
-                ctx.set_stream(torch.cuda.current_stream(dev))
-            if dev not in d_taps:
-                d_taps[dev] = upload_taps(h, dev)
-            data[name] = decimate(x, q, taps=h, ctx=ctx, device_taps=d_taps[dev])
-        c = self.coords
-        t = np.asarray(c.t, float)
-        coords = Coordinates(t[::q], c._baz[::q], c._bel[::q], offsets=c.offsets)
-        metadata = dict(self.metadata)
-        rate = (t.size - 1) / (t[-1] - t[0]) / q if t.size > 1 else float("nan")
-        metadata["downsample"] = {"factor": q, "n_taps": int(h.size), "sample_rate": float(rate)}
-        flags = None
-        if self.flags is not None:
-            from .flagging import downsample_flags
-
-            flags = downsample_flags(self.flags, q)
-        return TOD(data=data, dets=self.dets, coords=coords, units=self.units, metadata=metadata, flags=flags)
-
-    def demodulate(self, hwp=None, q=None, taps_t=None, taps_p=None, ctx=None, device="cuda:0"):
-        """A new TOD at 1 / q of the sample rate whose rows are the T, Q and U series of every detector behind a rotating
-        half-wave plate (maria_amd.hwp.demodulate): every field locked in against the carrier
-        (cos 4 chi, sin 4 chi) and low-passed on the device, one field at a time, into float32 device tensors of
-        D + 2 D_pol rows -- the T rows of all D detectors, then the Q rows and then the U rows of the D_pol polarised
-        ones (an unpolarised detector carries no polarisation signal).  ``hwp``: the maria_amd.hwp.HWP (None:
-        ``metadata["hwp"]``, which the simulation wrote); ``q`` (2 .. 32; None: min(32, hwp.max_factor(...)));
-        ``taps_t``, ``taps_p``: the low-passes of T and of Q / U (one of them given serves for both; neither:
-        ``hwp.design_taps(sample rate, f_hwp)``).  The
-        boresight and the times are picked at every q-th sample, output sample j at time t[j q].  ``dets`` is
-        ``hwp.demodulated_detectors(self.dets)``, whose ``stokes_rows()`` the mappers take: a Q row is a detector of angle
-        -gamma without I weight, a U row one of angle pi / 4 - gamma; ``coords.offsets`` are repeated to match.  ``units``
-        and ``metadata`` are carried over and ``metadata["demodulate"]`` records ``f_hwp``, ``factor``, ``n_taps``,
-        ``sample_rate`` and the row ranges ``rows`` of T, Q and U.  The pW <-> K_RJ calibrator is NOT carried over: ``to()``
-        on the result raises NotImplementedError, so convert units first.  ``flags`` become
-        ``flagging.downsample_flags(flags, q)``, repeated for the Q / U rows.  This TOD is left as it is.  Its place in
-        the chain is downsample's, after deconvolve_time_constants and instead of downsample: a detector lag attenuates and
-        delays the 4 f carrier, which rotates Q into U."""
-        import torch
-
-        from . import hwp as mhwp
-        from ._lib import Context
-        from .downsample import MAX_FACTOR, MIN_FACTOR
-
-        if "demodulate" in self.metadata or "downsample" in self.metadata:
-            raise ValueError("demodulate takes the TOD at the rate the half-wave plate modulated it: this one is already reduced")
-        if hwp is None:
-            if "hwp" not in self.metadata:
-                raise ValueError('no hwp given and no metadata["hwp"]: this TOD was not simulated behind a half-wave plate')
-            hwp = mhwp.HWP.from_metadata(self.metadata["hwp"])
-        t = np.asarray(self.coords.t, float)
-        if t.size < 2:
-            raise ValueError("demodulate needs at least two samples to know the sample rate")
-        fs = (t.size - 1) / (t[-1] - t[0])
-        if q is None:
-            q = min(MAX_FACTOR, mhwp.max_factor(fs, hwp.frequency))
-        if int(q) != q or not MIN_FACTOR <= int(q) <= MAX_FACTOR:
-            raise ValueError(f"q {q}: an integer in {MIN_FACTOR} .. {MAX_FACTOR}")
-        q = int(q)
-        host = lambda h: np.ascontiguousarray(_tod_args.to_numpy(h), np.float64)  # noqa: E731
-        if taps_t is None and taps_p is None:
-            ht = hp = mhwp.design_taps(fs, hwp.frequency)
-        else:  # one of them given serves for both
-            hp = host(taps_t if taps_p is None else taps_p)
-            ht = hp if taps_t is None else host(taps_t)
-        c = mhwp.carrier(hwp.angle(t))
-        D = self.dets.n
-        pol = mhwp.polarized_rows(self.dets)
-        Dp = int(pol.size)
-        T_out = (t.size + q - 1) // q
-        data, d_carrier = {}, {}  # the carrier goes to a device once, and one context serves every field
-        for name, v in self.data.items():
-            v = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
-            dev = v.device if v.is_cuda else torch.device(device)
-            x = v.to(dev, torch.float32)
-            if x.dim() == 2 and x.shape[1] > 1 and x.stride(1) != 1:
-                x = x.contiguous()
-            if ctx is None:
-                ctx = Context(dev.index or 0)
-                ctx.set_stream(torch.cuda.current_stream(dev))
-            if dev not in d_carrier:
-                d_carrier[dev] = torch.as_tensor(c).to(dev)
-            y = torch.empty((D + 2 * Dp, T_out), dtype=torch.float32, device=dev)
-            if Dp == D:  # every detector has Q and U rows: the three outputs are the three blocks of the field
-                mhwp.demodulate(x, d_carrier[dev], q, ht, hp, ctx=ctx, out=(y[:D], y[D:2 * D], y[2 * D:]))
-            else:
-                _, yq, yu = mhwp.demodulate(x, d_carrier[dev], q, ht, hp, ctx=ctx, out=(y[:D], *torch.empty((2, D, T_out), dtype=torch.float32, device=dev)))
-                rows = torch.as_tensor(pol).to(dev)
-                y[D:D + Dp] = yq.index_select(0, rows)
-                y[D + Dp:] = yu.index_select(0, rows)
-            data[name] = y
-        idx = np.concatenate([np.arange(D), pol, pol])
-        cd = self.coords
-        coords = Coordinates(t[::q], cd._baz[::q], cd._bel[::q], offsets=None if cd.offsets is None else cd.offsets[idx])
-        metadata = dict(self.metadata)
-        metadata["demodulate"] = {"f_hwp": hwp.frequency, "factor": q, "n_taps": int(hp.size), "sample_rate": float(fs / q),
-                                  "rows": {"T": (0, D), "Q": (D, D + Dp), "U": (D + Dp, D + 2 * Dp)}}
-        flags = None
-        if self.flags is not None:
-            from .flagging import downsample_flags
-
-            low = downsample_flags(torch.as_tensor(self.flags), q)
-            flags = low.index_select(0, torch.as_tensor(idx).to(low.device))
-        return TOD(data=data, dets=mhwp.demodulated_detectors(self.dets), coords=coords, units=self.units, metadata=metadata, flags=flags)
-
-    def remove_hwpss(self, harmonics=(1, 2), hwp=None, **regress_kw):
-        """A new TOD with the half-wave plate's synchronous signal fitted and removed: ``TOD.regress`` on the templates
-        cos k chi, sin k chi of the ``harmonics`` k (at most 4: regress takes 8 templates), ``hwp.harmonic_templates``.
-        ``hwp`` None: ``metadata["hwp"]``; ``regress_kw``: ``model``, ``into``, ``min_hits``, ``rcond``, ``ctx``,
-        ``device``.  It runs at the full rate, before ``demodulate``.  Removing harmonic 4 also removes any polarisation
-        that is constant in the instrument's frame -- and with it the part of the sky's that happens to be.
-        ``metadata["regress"]`` is regress's, and ``metadata["hwpss"]`` records the harmonics."""
-        from . import hwp as mhwp
-
-        ks = tuple(harmonics)
-        if not 1 <= len(ks) <= mhwp.MAX_HARMONICS:
-            raise ValueError(f"harmonics {harmonics}: 1 .. {mhwp.MAX_HARMONICS} of them")
-        if hwp is None:
-            if "hwp" not in self.metadata:
-                raise ValueError('no hwp given and no metadata["hwp"]: this TOD was not simulated behind a half-wave plate')
-            hwp = mhwp.HWP.from_metadata(self.metadata["hwp"])
-        out = self.regress(mhwp.harmonic_templates(hwp.angle(self.coords.t), ks), **regress_kw)
-        out.metadata["hwpss"] = {"harmonics": tuple(int(k) for k in ks)}
-        return out
-
-    def flag_glitches(self, n_sigma=6.0, half_window=5, grow=(2, 8), n_fit=4, fill=True, ctx=None, device="cuda:0"):
-        """A new TOD with glitches flagged and, with ``fill``, filled (maria_amd.flagging).  Glitches are
-        detected on the signal (the sum of the fields): samples further than ``n_sigma`` robust sigmas from the running
-        median of 2 * half_window + 1 samples, grown by ``grow = (before, after)`` samples, ORed into any ``flags`` this
-        TOD already has.  Every field of the result is a float32 device copy whose flagged samples are replaced by the
-        line between the means of the ``n_fit`` unflagged samples either side (no noise is added), so that the
-        pre-processing filters do not ring; ``flags`` is the [D, T] uint8 device tensor the mappers take as zero weight, and
-        ``metadata["glitches"]`` records the parameters, ``flagged_fraction`` and the per-row ``counts``.  ``dets``,
-        ``coords``, ``units`` and the pW <-> K_RJ calibrator are carried over.  This TOD is left as it is."""
-        import torch
-
-        from ._lib import Context
-        from .flagging import find_glitches, gap_fill
-
-        data, signal, dev = {}, None, None
-        for name, v in self.data.items():
-            v = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
-            if dev is None:  # the first field's device (a host field: ``device``) takes them all
-                dev = v.device if v.is_cuda else torch.device(device)
-            data[name] = v.to(dev, torch.float32, copy=True).contiguous()
-            signal = data[name].clone() if signal is None else signal.add_(data[name])
-        if ctx is None:
-            ctx = Context(dev.index or 0)
-            ctx.set_stream(torch.cuda.current_stream(dev))
-        flags, count = find_glitches(signal, n_sigma=n_sigma, half_window=half_window, grow=grow, ctx=ctx)
-        del signal
-        if self.flags is not None:
-            flags |= torch.as_tensor(self.flags).to(dev, torch.uint8)
-            count = (flags != 0).sum(dim=1)
-        if fill:
-            for x in data.values():
-                gap_fill(x, flags, n_fit=n_fit, ctx=ctx)
-        metadata = dict(self.metadata)
-        counts = count.cpu().numpy().astype(np.int64)
-        metadata["glitches"] = {"n_sigma": float(n_sigma), "half_window": int(half_window), "grow": (int(grow[0]), int(grow[1])),
-                                "n_fit": int(n_fit), "fill": bool(fill), "flagged_fraction": float(counts.sum() / flags.numel()),
-                                "counts": counts}
-        out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=flags)
-        out._calibrator = getattr(self, "_calibrator", None)
-        return out
-
-    def fix_jumps(self, window=64, n_sigma=8.0, gap=4, sep=None, grow=(4, 4), min_count=None, model=None, into=None, n_fit=4, fill=True,
-                  ctx=None, device="cuda:0"):
-        """A new TOD with the jumps of every detector found, taken out and flagged (maria_amd.jumps).  Jumps
-        are the peaks of the step statistic of the signal (the sum of the fields, less ``model``): the mean of the
-        ``window`` samples after a sample less the mean of those before it, above ``n_sigma`` robust scales of the
-        statistic itself and more than ``sep`` (None: window) samples apart.  Samples with nonzero ``flags`` are kept
-        out of every mean, so run ``flag_glitches`` first: a 40 sigma spike shifts the statistic by 40 sigma / window
-        over window samples.  A jump's height is the same difference of means with the ``gap`` samples either side of
-        it left out and the windows clipped at the neighbouring jumps; the steps are subtracted from the field ``into``
-        (default: the first; the mappers bin the sum).  A jump with fewer than ``min_count`` (None: window // 2) valid
-        samples on a side has no height: it is flagged, counted in ``unfixed`` and left in the data.  The samples within
-        ``grow = (before, after)`` of a jump are ORed into the flags and, with ``fill``, every field is filled over the
-        new flags by ``flagging.gap_fill`` with ``n_fit``.  ``model``: the expected sky signal, or a drift to keep out of
-        the statistic.  Every field of the result is a float32 device copy; ``dets``, ``coords``, ``units`` and the
-        pW <-> K_RJ calibrator are carried over; ``metadata["jumps"]`` records the parameters, the per-row ``counts``,
-        ``positions`` and ``heights`` (a list of arrays, one a row; 0 for an unfixed jump), ``unfixed`` and
-        ``flagged_fraction``.  This TOD is left as it is."""
-        import torch
-
-        from . import jumps
-        from .flagging import MAX_FIT, _check_grow, gap_fill
-
-        w, g, m = jumps._check_window(window, gap, min_count)
-        sep = jumps._check_sep(sep, w)
-        grow = _check_grow(grow)
-        if int(n_fit) != n_fit or not 1 <= int(n_fit) <= MAX_FIT:
-            raise ValueError(f"n_fit {n_fit}: an integer in 1 .. {MAX_FIT}")
-        data, signal, model, flags, into, ctx = self._device_fields(model, into, ctx, device)
-        if model is not None:
-            signal.sub_(model)
-        row_start, pos, jump_flags, count = jumps.find_jumps(signal, window=w, n_sigma=n_sigma, sep=sep, grow=grow, flags=flags,
-                                                             min_count=m, ctx=ctx)
-        height, ok = jumps.jump_heights(signal, row_start, pos, w, g, flags=flags, min_count=m, ctx=ctx)
-        del signal
-        jumps.fix_jumps(data[into], row_start, pos, height, out=data[into], ctx=ctx)
-        if flags is not None:
-            jump_flags |= flags
-        if fill:
-            for x in data.values():
-                gap_fill(x, jump_flags, n_fit=int(n_fit), ctx=ctx)
-        rs, ps, hs = row_start.cpu().numpy(), pos.cpu().numpy().astype(np.int64), height.cpu().numpy()
-        metadata = dict(self.metadata)
-        metadata["jumps"] = {"window": w, "n_sigma": float(n_sigma), "gap": g, "sep": sep, "grow": grow, "min_count": m, "n_fit": int(n_fit),
-                             "fill": bool(fill), "into": into, "counts": count.cpu().numpy().astype(np.int64),
-                             "positions": [ps[a:b] for a, b in zip(rs[:-1], rs[1:])], "heights": [hs[a:b] for a, b in zip(rs[:-1], rs[1:])],
-                             "unfixed": int((~ok).sum()), "flagged_fraction": float((jump_flags != 0).sum()) / jump_flags.numel()}
-        out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=jump_flags)
-        out._calibrator = getattr(self, "_calibrator", None)
-        return out
-
-    def remove_ground(self, n_bins=64, bins=None, model=None, shared=False, min_hits=8, into=None, ctx=None, device="cuda:0"):
-        """A new TOD with the scan-synchronous ground pickup removed (maria_amd.ground): per detector, the mean
-        of the signal (the sum of the fields) in each of ``n_bins`` uniform bins of the boresight azimuth
-        (``ground.azimuth_bins``), subtracted from every sample of the bin.  ``model``: a [D, T] array or tensor of the
-        expected sky signal (a previous map sampled back through ``Simulation(map=...)``, or a field of this TOD), taken
-        off the signal before the means are formed, so that the subtraction does not eat the sky; without it the template
-        holds the sky's own mean in every bin.  Samples with nonzero ``flags`` take no part in the means, and are
-        subtracted from like the rest.  ``bins``: any int32 [T] key in -1 .. n_bins - 1 in place of the azimuth bins
-        (-1: the sample is left as it is).  ``shared``: one template for all detectors (``ground.shared_template``).
-        A (detector, bin) pair with fewer than ``min_hits`` samples gets no template and its samples stay as they are.
-        Every field of the result is a float32 device copy; the template is subtracted from the field ``into`` (default:
-        the first), the mappers bin the sum.  ``flags``, ``dets``, ``coords``, ``units`` and the pW <-> K_RJ calibrator
-        are carried over; ``metadata["ground"]`` records ``n_bins``, ``lo``, ``hi`` (None with ``bins``), ``min_hits``,
-        ``shared``, ``empty_bins`` (the (detector, bin) pairs without a template) and the [D, n_bins] float32
-        ``template``.  This TOD is left as it is."""
-        from . import ground
-
-        n_bins = ground._check_n_bins(n_bins)
-        T = int(np.asarray(self.coords.t).size)
-        lo = hi = None
-        if bins is None:
-            bins, lo, hi = ground.azimuth_bins(self.coords._baz, n_bins)
-        bins = ground._check_bins(bins, n_bins, T)
-        min_hits = _tod_args.check_min_hits(min_hits)
-        data, signal, model, flags, into, ctx = self._device_fields(model, into, ctx, device)
-        template, hits, sums = ground.bin_template(signal, bins, n_bins, flags=flags, model=model, min_hits=min_hits, ctx=ctx)
-        del signal
-        floor = max(int(min_hits), 1)
-        if shared:
-            template = ground.shared_template(sums, hits, min_hits)
-            empty = int((hits.sum(dim=0) < floor).sum()) * int(hits.shape[0])
-        else:
-            empty = int((hits < floor).sum())
-        ground.apply_template(data[into], bins, template, sign=-1, out=data[into], ctx=ctx)
-        metadata = dict(self.metadata)
-        metadata["ground"] = {"n_bins": n_bins, "lo": lo, "hi": hi, "min_hits": int(min_hits), "shared": bool(shared),
-                              "empty_bins": empty, "template": template.cpu().numpy()}
-        out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=self.flags)
-        out._calibrator = getattr(self, "_calibrator", None)
-        return out
-
-    def _device_fields(self, model, into, ctx, device):
-        """(data, signal, model, flags, into, ctx) for ``remove_ground``, ``regress``, ``remove_common_mode`` and the like: float32
-        device copies of the fields, their sum, the model and the flags on the same device."""
-        import torch
-
-        from ._lib import Context
-
-        T = int(np.asarray(self.coords.t).size)
-        into = self.fields[0] if into is None else into
-        if into not in self.data:
-            raise ValueError(f"into {into!r}: one of the fields {self.fields}")
-        data, signal, dev = {}, None, None
-        for name, v in self.data.items():
-            v = v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
-            if dev is None:  # the first field's device (a host field: ``device``) takes them all
-                dev = v.device if v.is_cuda else torch.device(device)
-            data[name] = v.to(dev, torch.float32, copy=True).contiguous()
-            signal = data[name].clone() if signal is None else signal.add_(data[name])
-        if tuple(signal.shape) != (signal.shape[0], T):
-            raise ValueError(f"fields of shape {tuple(signal.shape)}: the coordinates have {T} samples")
-        if model is not None:
-            model = model if isinstance(model, torch.Tensor) else torch.as_tensor(np.asarray(model))
-            if tuple(model.shape) != tuple(signal.shape):
-                raise ValueError(f"model of shape {tuple(model.shape)}: the fields' {tuple(signal.shape)}")
-            model = model.to(dev, torch.float32).contiguous()
-        flags = None if self.flags is None else torch.as_tensor(self.flags).to(dev, torch.uint8).contiguous()
-        if ctx is None:
-            ctx = Context(dev.index or 0)
-            ctx.set_stream(torch.cuda.current_stream(dev))
-        return data, signal, model, flags, into, ctx
-
-    def regress(self, templates, model=None, into=None, min_hits=8, rcond=1e-10, ctx=None, device="cuda:0"):
-        """A new TOD with the [K, T] time ``templates`` (K <= 8; float32, shared by all detectors: ``regress.
-        legendre_templates``, ``regress.airmass_template``, anything else) fitted to the signal (the sum of the fields,
-        less ``model``) of every detector by least squares and subtracted from the field ``into`` (default: the first; the
-        mappers bin the sum) (maria_amd.regress).  Samples with nonzero ``flags`` take no part in the fit,
-        and are subtracted from like the rest.  A detector with fewer than max(min_hits, K) samples left, or whose
-        templates are degenerate on them (``regress.solve``), is left as it is.  Every field of the result is a float32
-        device copy; ``flags``, ``dets``, ``coords``, ``units`` and the pW <-> K_RJ calibrator are carried over;
-        ``metadata["regress"]`` records ``n_templates``, ``min_hits``, ``rcond``, the [D, K] float64 ``coefficients`` and
-        ``failed_rows``.  This TOD is left as it is."""
-        import torch
-
-        from . import regress
-
-        min_hits = _tod_args.check_min_hits(min_hits)
-        B = templates if isinstance(templates, torch.Tensor) else torch.as_tensor(np.asarray(templates))
-        T = int(np.asarray(self.coords.t).size)
-        if B.dim() != 2 or B.shape[1] != T or not 1 <= B.shape[0] <= regress.MAX_TEMPLATES:
-            raise ValueError(f"templates must be a [K, {T}] array with K in 1 .. {regress.MAX_TEMPLATES}")
-        data, signal, model, flags, into, ctx = self._device_fields(model, into, ctx, device)
-        B = B.to(signal.device, torch.float32).contiguous()[None]
-        N, r, hits = regress.normal_equations(signal, B, flags=flags, model=model, ctx=ctx)
-        del signal
-        a, ok = regress.solve(N, r, hits, min_hits=min_hits, rcond=rcond)
-        regress.apply(data[into], B, a, sign=-1, out=data[into], ctx=ctx)
-        metadata = dict(self.metadata)
-        metadata["regress"] = {"n_templates": int(B.shape[1]), "min_hits": min_hits, "rcond": float(rcond),
-                               "coefficients": a.cpu().numpy(), "failed_rows": np.flatnonzero(~ok.cpu().numpy())}
-        out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=self.flags)
-        out._calibrator = getattr(self, "_calibrator", None)
-        return out
-
-    def remove_common_mode(self, groups="band", n_iter=3, poly_order=0, airmass=False, model=None, into=None, min_hits=8, rcond=1e-10,
-                           ctx=None, device="cuda:0"):
-        """A new TOD with the common mode removed (maria_amd.regress.fit_common_mode): per group of
-        detectors the gain-weighted mean of the signal (the sum of the fields, less ``model``) sample by sample, every
-        detector fitted to [1, common mode, further templates] by least squares, the fit subtracted from the field
-        ``into`` (default: the first), the constant included.  ``groups``: "band" (``dets.band_index``), None (one group)
-        or an integer array, -1 leaving a detector out and as it is (at most 16 groups).  Further templates: the Legendre
-        polynomials P_1 .. P_poly_order of the time axis and, with ``airmass``, 1 / sin(elevation) less its mean.  Mean
-        and fit are iterated ``n_iter`` times, the gains of one fit weighting the next mean.  ``model``: the expected sky
-        signal, kept out of mean and fit.  Samples with nonzero ``flags`` take part in neither and are subtracted from
-        like the rest; a detector that cannot be fitted (``regress.solve``) is left as it is.  Every field of the result
-        is a float32 device copy; ``flags``, ``dets``, ``coords``, ``units`` and the pW <-> K_RJ calibrator are carried
-        over; ``metadata["common_mode"]`` records ``n_groups``, ``n_iter``, ``poly_order``, ``airmass``, ``min_hits``,
-        ``rcond``, the [D] ``gains`` and ``offsets``, the [D, K] ``coefficients``, the [G, T] float32 ``common_mode``
-        and ``failed_rows``.  This TOD is left as it is."""
-        from . import regress
-
-        min_hits = _tod_args.check_min_hits(min_hits)
-        T = int(np.asarray(self.coords.t).size)
-        if isinstance(groups, str):
-            if groups != "band":
-                raise ValueError(f'groups {groups!r}: "band", None or an integer array')
-            groups = np.asarray(self.dets.band_index, np.int32)
-        elif groups is not None:
-            groups = np.asarray(groups)
-            if groups.ndim != 1 or groups.dtype.kind not in "iu" or (groups.size and groups.min() < -1):
-                raise ValueError("groups must be a one-dimensional integer array with entries >= -1")
-            groups = groups.astype(np.int32)
-        G = 1 if groups is None or not groups.size else max(int(groups.max()) + 1, 1)
-        _tod_args.check_count(G, "the number of groups", regress.MAX_GROUPS)
-        if int(poly_order) != poly_order or int(poly_order) < 0 or 2 + int(poly_order) + bool(airmass) > regress.MAX_TEMPLATES:
-            raise ValueError(f"poly_order {poly_order}: an integer >= 0 with 2 + poly_order + airmass <= {regress.MAX_TEMPLATES}")
-        extra = [regress.legendre_templates(T, int(poly_order))[1:]]
-        if airmass:
-            extra.append(regress.airmass_template(self.coords._bel)[None])
-        extra = np.concatenate(extra)
-        data, signal, model, flags, into, ctx = self._device_fields(model, into, ctx, device)
-        c, a, gains, ok, B = regress.fit_common_mode(signal, groups=groups, n_groups=G, flags=flags, model=model,
-                                                     extra=extra if extra.shape[0] else None, n_iter=n_iter, min_hits=min_hits,
-                                                     rcond=rcond, ctx=ctx)
-        del signal
-        regress.apply(data[into], B, a, groups=groups, sign=-1, out=data[into], ctx=ctx)
-        metadata = dict(self.metadata)
-        a_host = a.cpu().numpy()
-        grouped = np.ones(a_host.shape[0], bool) if groups is None else groups >= 0  # a detector left out has not failed
-        metadata["common_mode"] = {"n_groups": G, "n_iter": int(n_iter), "poly_order": int(poly_order), "airmass": bool(airmass),
-                                   "min_hits": min_hits, "rcond": float(rcond), "gains": gains.cpu().numpy(), "offsets": a_host[:, 0].copy(),
-                                   "coefficients": a_host, "common_mode": c.cpu().numpy(), "failed_rows": np.flatnonzero(~ok.cpu().numpy() & grouped)}
-        out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=self.flags)
-        out._calibrator = getattr(self, "_calibrator", None)
-        return out
-
-    def filter_subscans(self, order=3, bounds=None, turn_frac=0.9, flag_turnarounds=True, flag_failed=True, model=None, into=None,
-                        min_hits=8, rcond=1e-10, ctx=None, device="cuda:0"):
-        """A new TOD with a Legendre polynomial of degree ``order`` (0 .. 7) fitted to every detector's signal (the sum of
-        the fields, less ``model``) in every subscan and subtracted from the field ``into`` (default: the first; the
-        mappers bin the sum) (maria_amd.subscans).  The subscans are the stretches of the boresight azimuth
-        between two turnarounds (``subscans.find_subscans`` with ``turn_frac``), or the segments of ``bounds`` [S + 1],
-        ascending.  Samples with nonzero ``flags`` and the turnaround samples take no part in the fit, and are
-        subtracted from like the rest of their segment.  A (detector, segment) pair with fewer than max(min_hits,
-        order + 1) samples left, or whose polynomials are degenerate on them (``regress.solve``), is left bit for bit as
-        it was.  The result's flags are the old ones, ORed with the turnarounds (``flag_turnarounds``) and with every
-        sample of a segment that was not fitted (``flag_failed``).  Every field of the result is a float32 device copy;
-        ``dets``, ``coords``, ``units`` and the pW <-> K_RJ calibrator are carried over; ``metadata["subscans"]`` records
-        ``order``, ``bounds``, ``turn_frac``, ``min_hits``, ``rcond``, the [D, S, order + 1] float64 ``coefficients`` and
-        ``failed_segments``, the [n, 2] (detector, segment) pairs of the segments with samples that were not fitted.  This
-        TOD is left as it is."""
-        import torch
-
-        from . import subscans
-
-        if int(order) != order or not 0 <= int(order) < subscans.MAX_ORDER:
-            raise ValueError(f"order {order}: an integer in 0 .. {subscans.MAX_ORDER - 1}")
-        K = int(order) + 1
-        min_hits = _tod_args.check_min_hits(min_hits)
-        if not 0.0 <= float(rcond) < 1.0:
-            raise ValueError(f"rcond {rcond}: in [0, 1)")
-        T = int(np.asarray(self.coords.t).size)
-        found, turn = subscans.find_subscans(self.coords._baz, turn_frac)
-        if bounds is None:
-            bounds = found
-        else:
-            bounds = np.asarray(bounds)
-            if bounds.ndim != 1 or bounds.size < 2 or bounds.dtype.kind not in "iu" or np.any(np.diff(bounds.astype(np.int64)) < 0):
-                raise ValueError("bounds must be a one-dimensional array of S + 1 >= 2 ascending integers")
-            bounds = np.clip(bounds.astype(np.int64), 0, T).astype(np.int32)
-        if turn.size != T:
-            raise ValueError(f"the boresight has {turn.size} samples: the coordinates' time axis {T}")
-        data, signal, model, flags, into, ctx = self._device_fields(model, into, ctx, device)
-        dev = signal.device
-        d_turn = torch.as_tensor(turn).to(dev)
-        used = d_turn[None, :].expand(signal.shape[0], T).contiguous() if flags is None else flags | d_turn[None, :]
-        d_bounds = torch.as_tensor(bounds).to(dev)
-        a, ok = subscans.fit(signal, d_bounds, K, flags=used, model=model, min_hits=min_hits, rcond=rcond, ctx=ctx)
-        del signal
-        subscans.apply(data[into], d_bounds, a, sign=-1, out=data[into], ctx=ctx)
-        segment = np.full(T, -1, np.int64)  # every sample's segment
-        for s, (lo, hi) in enumerate(zip(bounds[:-1], bounds[1:])):
-            segment[lo:hi] = s
-        covered = torch.as_tensor(segment >= 0).to(dev)
-        failed = ~ok[:, torch.as_tensor(np.maximum(segment, 0)).to(dev)] & covered[None, :]  # [D, T]
-        new_flags = flags
-        if flag_turnarounds:
-            new_flags = used
-        if flag_failed:
-            new_flags = failed.to(torch.uint8) if new_flags is None else new_flags | failed.to(torch.uint8)
-        nonempty = np.diff(bounds.astype(np.int64)) > 0
-        metadata = dict(self.metadata)
-        metadata["subscans"] = {"order": int(order), "bounds": np.array(bounds, np.int32), "turn_frac": float(turn_frac), "min_hits": min_hits,
-                                "rcond": float(rcond), "coefficients": a.cpu().numpy(),
-                                "failed_segments": np.argwhere(~ok.cpu().numpy() & nonempty[None, :])}
-        out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=new_flags)
-        out._calibrator = getattr(self, "_calibrator", None)
-        return out
-
-    def deconvolve_time_constants(self, tau=None, init="steady", into=None, ctx=None, device="cuda:0"):
-        """A new TOD with the detectors' one-pole lag taken out of every field by its exact inverse, the two-tap FIR
-        x[t] = (y[t] - a y[t - 1]) / (1 - a) with a = exp(-1 / (fs tau)) (maria_amd.time_constants).  It is
-        the first step of time-domain cleaning, before anything is flagged or fitted: deconvolve_time_constants ->
-        downsample -> flag_glitches -> fix_jumps -> remove_ground -> remove_common_mode -> filter_subscans -> cut.  A pipeline
-        sees only the sum of the fields and the operation is linear, so every field is deconvolved, the noise with
-        them (the FIR raises white noise towards the Nyquist frequency by up to (1 + a) / (1 - a); ``downsample`` is the
-        next step and low-passes).  ``tau``: seconds, a scalar or one per detector (None: ``dets.time_constant``); an
-        explicit value lets one study a mis-estimated time constant.  ``init``: "steady" (the detector had seen the first
-        sample for ever, what ``Simulation`` applies) or "zero".  ``into``: accepted like the other steps' (a field's
-        name); every field is treated alike.  fs is (n - 1) / (t[-1] - t[0]) as in ``psd``.  Flags: sample t of the
-        result is flagged if t or t - 1 was, for its value depends on both.  On a TOD that was downsampled it raises
-        NotImplementedError: at the reduced rate the lag is no longer one pole, so deconvolve first.  Every field of the
-        result is a float32 device copy; ``dets``, ``coords``, ``units`` and the pW <-> K_RJ calibrator are carried over
-        (the conversion scales a row by a factor that changes over many time constants; exact where the run was made in
-        pW); ``metadata["time_constants"]`` gains ``deconvolved`` True, ``deconvolved_tau`` and ``deconvolved_init``.  This TOD
-        is left as it is."""
-        import torch
-
-        from . import time_constants
-
-        if "downsample" in self.metadata:
-            raise NotImplementedError("deconvolve_time_constants on a downsampled TOD: at the reduced rate the lag is no longer one "
-                                      "pole; deconvolve first, then downsample")
-        time_constants._check_init(init)
-        n = int(self.dets.n)
-        tau = np.asarray(self.dets.time_constant if tau is None else tau, float)
-        if tau.ndim > 1 or (tau.ndim == 1 and tau.shape[0] != n):
-            raise ValueError(f"tau must be a scalar or one time constant for each of the {n} detectors")
-        a = time_constants.poles(np.broadcast_to(tau, (n,)), time_constants.sample_rate_of(self.coords.t))
-        data, signal, _, flags, into, ctx = self._device_fields(None, into, ctx, device)
-        d_a = torch.as_tensor(a).to(signal.device)
-        del signal
-        for x in data.values():
-            time_constants.deconvolve(x, d_a, init=init, out=x, ctx=ctx)
-        if flags is not None:
-            grown = flags.clone()
-            grown[:, 1:] |= flags[:, :-1]
-            flags = grown
-        metadata = dict(self.metadata)
-        metadata["time_constants"] = dict(metadata.get("time_constants") or {}, deconvolved=True, deconvolved_tau=np.broadcast_to(tau, (n,)).copy(),
-                                          deconvolved_init=init)
-        out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=flags)
-        out._calibrator = getattr(self, "_calibrator", None)
-        return out
-
-    def _segment_bounds(self, bounds):
-        """[S + 1] int32 bounds for ``stats`` and ``cut``, clamped to 0 .. T: None (the whole row), "subscans"
-        (``subscans.find_subscans`` of the boresight azimuth), an int (chunks of that many samples) or an ascending
-        integer array."""
-        from . import cuts, subscans
-
-        T = int(np.asarray(self.coords.t).size)
-        if bounds is None:
-            return np.array([0, T], np.int32)
-        if isinstance(bounds, str):
-            if bounds != "subscans":
-                raise ValueError(f'bounds {bounds!r}: None, "subscans", a chunk length or an integer array')
-            found, _ = subscans.find_subscans(self.coords._baz)
-            if found[-1] != T:
-                raise ValueError(f"the boresight has {found[-1]} samples: the coordinates' time axis {T}")
-            return found
-        if isinstance(bounds, (int, np.integer)) and not isinstance(bounds, bool):
-            return cuts.chunk_bounds(T, bounds)
-        bounds = np.asarray(bounds)
-        if bounds.ndim != 1 or bounds.size < 2 or bounds.dtype.kind not in "iu" or np.any(np.diff(bounds.astype(np.int64)) < 0):
-            raise ValueError("bounds must be a one-dimensional array of S + 1 >= 2 ascending integers")
-        return np.clip(bounds.astype(np.int64), 0, T).astype(np.int32)
-
-    def stats(self, bounds=None, model=None, ctx=None, device="cuda:0"):
-        """The statistics of the signal (the sum of the fields, less ``model``) over the samples whose ``flags`` are 0
-        (maria_amd.cuts): a dict of ``bounds`` (the [S + 1] int32 segments used), ``segments`` (the
-        summary of ``cuts.summarize`` per (detector, segment): [D, S] float64 device tensors ``mean``, ``var``, ``std``,
-        ``skew``, ``kurtosis``, ``min``, ``max``, ``ptp``, ``sigma_diff``, ``flagged_fraction``, and int64 ``hits`` and
-        ``pairs``) and ``detectors`` (the same per detector, [D], from a second pass with the row as one segment).
-        ``bounds``: None (the whole row), "subscans" (``subscans.find_subscans``), an int (chunks of that many
-        samples) or an ascending integer array.  This TOD is left as it is."""
-        bounds = self._segment_bounds(bounds)
-        _, signal, model, flags, _, ctx = self._device_fields(model, None, ctx, device)
-        from . import cuts
-
-        seg = cuts.summarize(cuts.moments(signal, bounds, flags=flags, model=model, ctx=ctx), np.diff(bounds.astype(np.int64)))
-        det = seg if len(bounds) == 2 else cuts.summarize(cuts.moments(signal, None, flags=flags, model=model, ctx=ctx), [signal.shape[1]])
-        return {"bounds": bounds, "segments": seg, "detectors": {k: v[:, 0] for k, v in det.items()}}
-
-    def cut(self, bounds="subscans", groups="band", n_sigma=5.0, n_sigma_segment=5.0, max_flagged=0.5, max_bad_segments=0.5, min_hits=8,
-            criteria=("white", "rms", "skew", "kurtosis", "flagged"), value=1, model=None, ctx=None, device="cuda:0"):
-        """A new TOD whose flags also cover the detectors and the segments that are not worth mapping (maria_amd.cuts,
-        DESIGN 3.26); the last step of time-domain cleaning, after ``filter_subscans``.  The statistics of :meth:`stats`
-        are taken on the signal (the sum of the fields, less ``model``) over the samples whose flags are 0, per detector
-        and per segment of ``bounds`` (as in :meth:`stats`).  A detector is cut whole if, within its group (``groups``:
-        "band", None for one group, or an integer array, -1 leaving a detector out), it lies more than ``n_sigma``
-        robust scales (1.4826 times the median absolute deviation) from the median in log ``sigma_diff`` ("white"),
-        log ``std`` ("rms"), ``skew`` or ``kurtosis``, if more than ``max_flagged`` of its samples are flagged
-        ("flagged"), or if it is unusable: fewer than max(min_hits, 1) samples kept, or one of those values not finite
-        (a constant row).  A segment is bad if its ``sigma_diff`` lies more than ``n_sigma_segment`` robust scales
-        above the median over that detector's own segments (``cuts.bad_segments``; None: segments are not judged); a
-        detector with more than ``max_bad_segments`` of its non-empty segments bad is cut whole.  The segments are
-        judged first and the detectors on what is left, the bad segments flagged: one noisy subscan does not cost the
-        detector.  ``criteria`` picks among the five names.
-        ``value`` (1 .. 255) is ORed into the flags of every sample of a cut detector and of a bad segment
-        (``cuts.flag_segments``); the mappers give flagged samples no weight.  Every field of the result is a float32
-        device copy, unchanged; ``dets``, ``coords``, ``units`` and the pW <-> K_RJ calibrator are carried over;
-        ``metadata["cuts"]`` records the parameters, ``bounds``, the per-criterion [D] bool ``masks`` (with "unusable"
-        and "segments"), ``cut_detectors`` (indices), ``cut_segments`` (the [n, 2] (detector, segment) pairs flagged in
-        detectors that were not cut whole) and ``flagged_fraction_before`` / ``flagged_fraction_after``.  This TOD is
-        left as it is."""
-        import torch
-
-        from . import cuts
-
-        bounds = self._segment_bounds(bounds)
-        if isinstance(value, bool) or int(value) != value or not 1 <= int(value) <= 255:
-            raise ValueError(f"value {value}: an integer in 1 .. 255")
-        if isinstance(groups, str):
-            if groups != "band":
-                raise ValueError(f'groups {groups!r}: "band", None or an integer array')
-            groups = np.asarray(self.dets.band_index, np.int64)
-        elif groups is not None:
-            groups = np.asarray(groups)
-            if groups.ndim != 1 or groups.dtype.kind not in "iu" or (groups.size and groups.min() < -1):
-                raise ValueError("groups must be a one-dimensional integer array with entries >= -1")
-            groups = groups.astype(np.int64)
-        cuts._check_rules(n_sigma, n_sigma_segment, max_flagged, max_bad_segments, min_hits, criteria)
-        data, signal, model, flags, _, ctx = self._device_fields(model, None, ctx, device)
-        D, T = signal.shape
-        if groups is not None and groups.shape[0] != D:
-            raise ValueError(f"groups must have one entry for each of the {D} detectors")
-        seg = cuts.summarize(cuts.moments(signal, bounds, flags=flags, model=model, ctx=ctx), np.diff(bounds.astype(np.int64)))
-        bad = cuts.bad_segments(seg, groups, n_sigma_segment, min_hits)
-        new_flags = torch.zeros((D, T), dtype=torch.uint8, device=signal.device) if flags is None else flags.clone()
-        before = float((new_flags != 0).sum()) / new_flags.numel()
-        if bool(bad.any()):
-            cuts.flag_segments(new_flags, bounds, bad, value=int(value), ctx=ctx)
-        det = cuts.summarize(cuts.moments(signal, None, flags=new_flags, model=model, ctx=ctx), [T])  # without the bad segments
-        del signal
-        masks, cut = cuts.decide(det, seg, bad, groups, n_sigma, max_flagged, max_bad_segments, min_hits, criteria)
-        if bool(cut.any()):
-            cuts.flag_segments(new_flags, np.array([0, T], np.int32), cut[:, None], value=int(value), ctx=ctx)
-        metadata = dict(self.metadata)
-        metadata["cuts"] = {"bounds": np.array(bounds, np.int32), "n_sigma": float(n_sigma),
-                            "n_sigma_segment": None if n_sigma_segment is None else float(n_sigma_segment), "max_flagged": float(max_flagged),
-                            "max_bad_segments": float(max_bad_segments), "min_hits": int(min_hits), "criteria": tuple(criteria), "value": int(value),
-                            "groups": None if groups is None else groups.copy(), "masks": {k: v.cpu().numpy() for k, v in masks.items()},
-                            "cut_detectors": np.flatnonzero(cut.cpu().numpy()), "cut_segments": np.argwhere((bad & ~cut[:, None]).cpu().numpy()),
-                            "flagged_fraction_before": before, "flagged_fraction_after": float((new_flags != 0).sum()) / new_flags.numel()}
-        out = TOD(data=data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=new_flags)
-        out._calibrator = getattr(self, "_calibrator", None)
-        return out
-
-    def with_offsets(self, offsets):
-        """A TOD that shares this one's data, flags and metadata and whose ``coords.offsets`` and ``dets.offsets`` are
-        ``offsets`` [D, 2] (radians): a fitted table (``BeamFit.offsets()``) on its way into any mapper, or the nominal
-        table in place of the true one."""
-        offsets = np.array(offsets, float)
-        if offsets.shape != (self.dets.n, 2) or not np.all(np.isfinite(offsets)):
-            raise ValueError(f"offsets must be [{self.dets.n}, 2] finite numbers (radians)")
-        import copy
-
-        dets = copy.copy(self.dets)
-        dets.offsets = offsets
-        out = TOD(data=self.data, dets=dets, coords=self.coords.broadcast(offsets), units=self.units, metadata=self.metadata, flags=self.flags)
-        out._calibrator = getattr(self, "_calibrator", None)
-        return out
-
-    def beam_fwhm(self):
-        """[D] radians: the detector table's own beam FWHM, the one the simulation smooths a map with
-        (``compute_angular_fwhm`` of the mean ``primary_size`` at the detector's band centre)."""
-        from .instrument import compute_angular_fwhm
-
-        return np.asarray(compute_angular_fwhm(fwhm_0=float(self.dets.primary_size.mean()), z=np.inf, nu=self.dets.band_center), float)
-
-    def _source_frame(self, source, frame, src_track, degrees, device):
-        """(pointing dict of device tensors, centre (phi, theta) in radians, src [T, 2] or None) for ``mask_source`` and
-        ``fit_beams``: the frame's transform, the boresight and the detector table as the mappers hand them to the binning.
-        ``source`` None: the scan centre, the mean direction of the boresight in the frame."""
-        import torch
-
-        if frame not in ("ra/dec", "az/el"):
-            raise NotImplementedError(f"frame '{frame}': only 'ra/dec' and 'az/el' are built")
-        unit = np.pi / 180 if degrees else 1.0
-        T = int(np.asarray(self.coords.t).size)
-        stack = sky_transform_stack(self.coords.t, self.metadata["latitude"], self.metadata["longitude"]) if frame == "ra/dec" else None
-        if source is None:
-            from .beamfit import scan_center
-
-            center = scan_center(self.coords._baz, self.coords._bel, stack)
-        else:
-            source = np.asarray(source, float)
-            if source.shape != (2,) or not np.all(np.isfinite(source)):
-                raise ValueError("source must be (phi, theta): two finite angles")
-            center = (float(unit * source[0]), float(unit * source[1]))
-        if src_track is not None:
-            src_track = unit * np.asarray(src_track, float)
-            if src_track.shape != (T, 2) or not np.all(np.isfinite(src_track)):
-                raise ValueError(f"src_track must be [{T}, 2] finite offsets from the source's nominal position")
-            src_track = torch.as_tensor(np.ascontiguousarray(src_track, np.float32)).to(device)
-        f32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float32)).to(device)  # noqa: E731
-        point = {"az": f32(self.coords._baz), "el": f32(self.coords._bel),
-                 "transform": None if stack is None else torch.as_tensor(stack.reshape(-1, 9)).to(device),
-                 "dx": f32(self.coords.offsets[:, 0]), "dy": f32(self.coords.offsets[:, 1])}
-        return point, center, src_track
-
-    def mask_source(self, source=None, radius=None, frame="ra/dec", src_track=None, value=1, degrees=True, ctx=None, device="cuda:0"):
-        """A TOD whose flags also cover the neighbourhood of a point source (maria_amd.beamfit.source_flags):
-        ``value`` (1 .. 255) is ORed into the flags of every sample at which the detector, at its table offset, points
-        within ``radius`` of the source; the flags are created if the TOD has none.  ``source``: (phi, theta) in
-        ``frame`` ("ra/dec" or "az/el"), None for the scan centre; ``radius``: None for 3 x the largest beam FWHM of the
-        detector table; ``src_track`` [T, 2]: the source's offsets from ``source`` at every sample (a planet that
-        moves); angles in degrees with ``degrees``, else radians.  ``remove_common_mode`` and ``filter_subscans`` leave
-        flagged samples out of their fits, so a bright source masked first does not bias them.  The data are shared with
-        this TOD, which is left as it is."""
-        import torch
-
-        from . import beamfit
-
-        if radius is None:
-            radius = 3.0 * float(self.beam_fwhm().max())
-        else:
-            radius = float(radius) * (np.pi / 180 if degrees else 1.0)
-        if not (np.isfinite(radius) and radius >= 0):
-            raise ValueError(f"radius {radius}: finite and >= 0")
-        dev = torch.device(device) if self.flags is None or not torch.as_tensor(self.flags).is_cuda else torch.as_tensor(self.flags).device
-        point, center, src = self._source_frame(source, frame, src_track, degrees, dev)
-        D, T = int(self.dets.n), int(np.asarray(self.coords.t).size)
-        flags = torch.zeros((D, T), dtype=torch.uint8, device=dev) if self.flags is None else torch.as_tensor(self.flags).to(dev, torch.uint8).clone()
-        beamfit.source_flags(point, center, radius, src=src, inside=True, value=value, flags=flags, ctx=ctx)
-        metadata = dict(self.metadata)
-        metadata["source_mask"] = {"center": center, "radius": radius, "frame": frame, "value": int(value)}
-        out = TOD(data=self.data, dets=self.dets, coords=self.coords, units=self.units, metadata=metadata, flags=flags)
-        out._calibrator = getattr(self, "_calibrator", None)
-        return out
-
-    def fit_beams(self, source=None, frame="ra/dec", radius=None, elliptical=False, field=None, model=None, src_track=None, n_iter=20,
-                  degrees=True, ctx=None, device="cuda:0"):
-        """``beamfit.BeamFit``: every detector's beam, pointing offset and gain from this scan over a point source
-        (maria_amd.beamfit).  The signal is the sum of the fields (or the one ``field``), less ``model``.
-        The window is ``radius`` (None: 3 x the detector's own beam FWHM of the table, per band the largest) around the
-        source at the NOMINAL offsets of the table, ANDed with ``flags == 0``; it is fixed once.  The starting point
-        comes from ``cuts.moments`` over the window: c0 = mean, A0 = max - mean, the width from the detector table, the
-        offsets the nominal ones.  ``source``, ``frame``, ``src_track``, ``degrees`` as in :meth:`mask_source`.  Run
-        it on a source scan after ``flag_glitches`` / ``fix_jumps`` and before anything that filters (or filter with
-        the source masked); ``with_offsets(fit.offsets())`` then goes into any mapper, and ``fit.relative_gain()`` is
-        the flat field.  This TOD is left as it is."""
-        import torch
-
-        from . import beamfit, cuts
-
-        if field is not None and field not in self.data:
-            raise ValueError(f"field {field!r}: one of the fields {self.fields}")
-        fwhm = self.beam_fwhm()
-        if radius is None:
-            radius = 3.0 * float(fwhm.max())
-        else:
-            radius = float(radius) * (np.pi / 180 if degrees else 1.0)
-        if not (np.isfinite(radius) and radius > 0):
-            raise ValueError(f"radius {radius}: finite and > 0")
-        _, signal, model, flags, _, ctx = self._device_fields(model, None, ctx, device)
-        if field is not None:
-            v = self.data[field]
-            signal = (v if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))).to(signal.device, torch.float32).contiguous()
-        D, T = signal.shape
-        point, center, src = self._source_frame(source, frame, src_track, degrees, signal.device)
-        window = torch.zeros((D, T), dtype=torch.uint8, device=signal.device) if flags is None else (flags != 0).to(torch.uint8)
-        beamfit.source_flags(point, center, radius, src=src, inside=False, value=1, flags=window, ctx=ctx)
-        m = cuts.moments(signal, None, flags=window, model=model, ctx=ctx)
-        mean, peak = m.mean[:, 0], m.max[:, 0]
-        w0 = torch.as_tensor((beamfit.FWHM_PER_SIGMA / fwhm) ** 2).to(signal.device)
-        init = torch.stack([peak - mean, point["dx"].to(torch.float64), point["dy"].to(torch.float64), w0, mean], dim=1)
-        return beamfit.fit(signal, point, center, init, window, model=model, src=src, elliptical=elliptical, n_iter=n_iter,
-                           groups=np.asarray(self.dets.band_index, np.int64), ctx=ctx)
-
-    def to(self, units):
-        """tod/tod.py:106-142 between "pW" and "K_RJ" (``mrx_tod_to_krj`` / ``mrx_tod_from_krj`` on
-        every field), for a TOD that came out of ``Simulation.run``; other units stay with maria's
-        calibration graph."""
-        if units == self.units:
-            return self
-        if {units, self.units} != {"pW", "K_RJ"} or getattr(self, "_calibrator", None) is None:
-            raise NotImplementedError(
-                f"conversion {self.units} -> {units}: only pW <-> K_RJ of a TOD made by Simulation.run() is built"
-            )
-        out = TOD(data=self._calibrator(self.data, to_krj=(units == "K_RJ")), dets=self.dets, coords=self.coords, units=units,
-                  metadata=self.metadata, flags=self.flags)
-        out._calibrator = self._calibrator
-        return out
 
 
 class Simulation:
@@ -1139,6 +268,22 @@ class Simulation:
         path.check_flags()  # RuntimeError "introduced nans" like atmosphere.py:368-369
         return out
 
+    def _context(self, obs):
+        """(ctx, device) for the steps after the atmosphere: the context and device of the observation's atmosphere path,
+        else this Simulation's own context on ``self.device``, bound to torch's current stream there either way."""
+        import torch
+
+        if hasattr(obs, "atmosphere"):
+            path = obs.atmosphere._device_path()
+            ctx, device = path.ctx, path.device
+        else:
+            from ._lib import Context
+
+            device = torch.device(self.device)
+            self._noise_ctx = ctx = self._noise_ctx or Context(device.index or 0)
+        ctx.set_stream(torch.cuda.current_stream(device))
+        return ctx, device
+
     def _sample_maps(self, obs, rows=None, krj=None, gain=None, stokes_rows=None):
         """sim/map.py:76-172 on the device: one ``mrx_map_sample`` per band, [D, T] pW
         (``rows = (lo, hi)``: only this shard's detector rows).  ``krj`` (``DevicePath.krj_row_tables()``): the field in
@@ -1148,24 +293,16 @@ class Simulation:
         import torch
 
         from . import map as mmap
-        from ._lib import Context
         from .instrument import compute_angular_fwhm
 
         lo, hi = rows or (0, obs.instrument.dets.n)
         dets = obs.instrument.dets.subset(np.arange(lo, hi))
         offsets = obs.coords.offsets[lo:hi]
         atm = getattr(obs, "atmosphere", None)
-        if atm is not None:
-            path = atm._device_path()
-            ctx, device = path.ctx, path.device
-            # (sync=False below frees this call's temporaries while the kernel is in flight: safe only on torch's current
-            # stream, whatever stream path.run() left on the context)
-            ctx.set_stream(torch.cuda.current_stream(device))
-        else:
-            device = torch.device(self.device)
-            self._noise_ctx = self._noise_ctx or Context(device.index or 0)
-            ctx = self._noise_ctx
-            ctx.set_stream(torch.cuda.current_stream(device))
+        path = None if atm is None else atm._device_path()
+        # (sync=False below frees this call's temporaries while the kernel is in flight: safe only on torch's current
+        # stream, whatever stream path.run() left on the context)
+        ctx, device = self._context(obs)
         T = len(obs.coords.t)
         # what does not change from run to run lives on the device, per observation and per band: the boresight, the
         # sample times, the horizon -> equatorial transform (14 ms of host arithmetic and 17 MB a run when it was made
@@ -1265,6 +402,8 @@ class Simulation:
         from ._lib import Context
 
         dets = obs.instrument.dets
+        # (not _context(obs): on the atmosphere's path the stream stays as path.run() left it, and whether binding it to
+        # torch's current stream here would change anything is not known)
         if hasattr(obs, "atmosphere"):
             ctx, device = obs.atmosphere._device_path().ctx, obs.atmosphere._device_path().device
         else:
@@ -1411,11 +550,8 @@ class Simulation:
         """The map field behind the half-wave plate, [D, T] pW: S_I + S_c cos 4 chi + S_s sin 4 chi from three passes of
         the sampler -- the detectors' I weights alone, the Q / U weights of angle -gamma, those of pi / 4 - gamma --
         combined in place by ``mrx_tod_hwp_modulate``.  A map without Q and U has S_c = S_s = 0: one pass, no launch."""
-        import torch
-
         from . import hwp as mhwp
         from . import map as mmap
-        from ._lib import Context
 
         rows_i = np.zeros((dets.n, 4))
         rows_i[:, 0] = mmap.mueller_row(dets.gamma)[:, 0]
@@ -1427,14 +563,7 @@ class Simulation:
             w = mmap.mueller_row(g)
             w[:, 0] = w[:, 3] = 0.0
             fields.append(self._sample_maps(obs, rows, stokes_rows=w))
-        if hasattr(obs, "atmosphere"):
-            path = obs.atmosphere._device_path()
-            ctx, device = path.ctx, path.device
-        else:
-            device = torch.device(self.device)
-            self._noise_ctx = self._noise_ctx or Context(device.index or 0)
-            ctx = self._noise_ctx
-        ctx.set_stream(torch.cuda.current_stream(device))
+        ctx, _ = self._context(obs)
         return mhwp.modulate(out, fields[0], fields[1], mhwp.carrier(self.hwp.angle(obs.coords.t)), out=out, ctx=ctx)
 
     @staticmethod
@@ -1450,16 +579,8 @@ class Simulation:
         import torch
 
         from . import time_constants
-        from ._lib import Context
 
-        if hasattr(obs, "atmosphere"):
-            path = obs.atmosphere._device_path()
-            ctx, device = path.ctx, path.device
-        else:
-            device = torch.device(self.device)
-            self._noise_ctx = self._noise_ctx or Context(device.index or 0)
-            ctx = self._noise_ctx
-        ctx.set_stream(torch.cuda.current_stream(device))
+        ctx, device = self._context(obs)
         a = torch.as_tensor(time_constants.poles(tau, time_constants.sample_rate_of(obs.coords.t))).to(device)
         for field in fields:
             time_constants.apply(field, a, init="steady", out=field, ctx=ctx)

@@ -19,6 +19,7 @@ import scipy.signal
 import torch
 
 from ._lib import Context, ptr
+from .tod import field_sum
 
 # tod/processing.py:16-37: operation -> parameter -> (type, aliases of the keyword form)
 OPERATION_KWARGS = {
@@ -142,12 +143,7 @@ class ProcessedTOD:
 
 
 def _signal(tod, device):
-    total = None
-    for field in tod.data.values():
-        f = field if isinstance(field, torch.Tensor) else torch.as_tensor(np.asarray(field))
-        f = f.to(device, torch.float32)
-        total = f.clone() if total is None else total.add_(f)
-    return total.contiguous()
+    return field_sum(tod.data.values(), device)
 
 
 def process_tod(tod, config=None, ctx=None, device="cuda:0", **kwargs):
