@@ -1194,6 +1194,42 @@ int mrx_tod_segment_moments(mrx_ctx* ctx, const float* d_x, size_t ld_x, const f
 int mrx_tod_segment_flag(mrx_ctx* ctx, uint8_t* d_flags, size_t ld_f, int D, int T, const int32_t* d_bound, int S,
                          const uint8_t* d_mask, int value);
 
+/* ---- the covariance between detectors: the flag-aware Gram matrix (maria_amd/covariance.py) ----------- */
+
+/* The samples of one float32 chain of mrx_tod_gram: time is cut at the multiples of MRX_GRAM_BLOCK from t = 0. */
+#define MRX_GRAM_BLOCK 256
+
+/* G = Z Z^T over the rows a list names.  d_flags, d_model, their pitches, term(d, t), the alignment (none beyond the
+ * element size), "nothing is read past T in a row" and "inputs are never modified" are those of the block above
+ * mrx_tod_column_mean.
+ *  d_rows    [R] int32, the rows that take part, in any order (a row may be named twice); NULL: R = D and row i is i.  An
+ *            entry outside 0 .. D - 1 (an unsigned comparison) is a row of zeros: its row and column of G and n are 0
+ *  d_center  [D] float64, indexed by the row of x; NULL: zeros
+ *   z(d, t)  = flags[d][t] == 0 ? (float)(term(d, t) - center[d]) : 0.0f     (one float64 subtraction, one rounding to
+ *              float32).  A flagged sample is selected away, never multiplied: 1e30 or NaN under a flag changes no bit.
+ *              An unflagged NaN makes row and column i of G NaN and nothing else
+ *   G[i][j]  = sum over t of z(rows[i], t) * z(rows[j], t)
+ *   n[i][j]  = |{ t : flags[rows[i]][t] == 0 and flags[rows[j]][t] == 0 }|, exact; T for rows in range when d_flags is NULL
+ * G[i][j] and G[j][i] are the same bits: only the 128 x 128 tiles on and above the diagonal are computed, the rest is
+ * their mirror.
+ * Order of a sum.  Inside a block [b MRX_GRAM_BLOCK, min((b + 1) MRX_GRAM_BLOCK, T)) it is the float32 chain
+ *   s = 0.0f; for t ascending: s = fmaf(z_i(t), z_j(t), s)
+ * (v_mfma_f32_32x32x2_f32, which is that chain bit for bit); the block sums are added in float64 in ascending b from 0.0,
+ * one rounding each.  The order is a function of T alone: not of R, D, the row list, the flags, the pitches, the
+ * pointers' alignment or what else is in the call.  Time is not split across workgroups; no atomics.  The same inputs
+ * give the same bits on every call, and G[i][j] depends on rows[i], rows[j] and T only.  To first order
+ *   |G[i][j] - exact| <= (MRX_GRAM_BLOCK * 2^-24 + ceil(T / MRX_GRAM_BLOCK) * 2^-53) * sum over t of |z_i(t) z_j(t)|
+ * against the exact sum of the products of the rounded z.
+ *  d_x   [D][ld_x] float32
+ *  d_G   [R][R] float64, OVERWRITTEN
+ *  d_n   [R][R] uint32, OVERWRITTEN, or NULL.  With d_flags it is a second pass of the same kernel on the 0/1 weights
+ *        (their float32 block sums are exact integers); without d_flags a fill; with d_n NULL nothing is launched for it
+ * D < 1, T < 1, R < 1, a pitch (of an array that is given) < T, or a null d_x or d_G -> MRX_ERR_INVALID with the outputs
+ * untouched */
+int mrx_tod_gram(mrx_ctx* ctx, const float* d_x, size_t ld_x, const float* d_model, size_t ld_m,
+                 const uint8_t* d_flags, size_t ld_f, int D, int T, const int32_t* d_rows, int R,
+                 const double* d_center, double* d_G, uint32_t* d_n);
+
 /* ---- beam, pointing offset and gain per detector from a source scan (maria_amd/beamfit.py) ------------- */
 
 /* Common to the two entries below.  The pointing arguments are mrx_bin_map's, in its order (d_az, d_el [T] float32,

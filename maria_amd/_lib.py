@@ -35,6 +35,7 @@ OPT_SYNTH_TILE_ORDER = 11
 OPT_GAUSS_ACCUM = 12
 OPT_SYNTH_ACQUIRE = 13
 OPT_WRITER_GENERAL = 14
+GRAM_BLOCK = 256  # MRX_GRAM_BLOCK
 
 _STATUS = {
     0: "MRX_OK",
@@ -242,6 +243,7 @@ SIGNATURES = {
     "mrx_tod_segment_apply": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _i, _vp, _i, _vp, _sz]),
     "mrx_tod_segment_moments": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp, _i, _vp, _vp]),
     "mrx_tod_segment_flag": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _vp, _i]),
+    "mrx_tod_gram": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "mrx_tod_source_flag": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _d, _d, _vp, _d, _i, _i, _vp, _sz]),
     "mrx_tod_beam_normal_work_bytes": (_i, [_i, _i, _i, _vp]),
     "mrx_tod_beam_normal": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, _i, _d, _d, _vp, _vp, _i, _vp, _vp, _vp, _sz]),

@@ -582,6 +582,120 @@ class TOD:
                   "common_mode": c.cpu().numpy(), "failed_rows": np.flatnonzero(~ok.cpu().numpy() & grouped)}
         return self._derived(data=data, record={"common_mode": record})
 
+    def _covariance_groups(self, groups, D):
+        """(groups as [D] int32 or None, their number) for the covariance methods: at most 16 groups."""
+        from . import covariance
+
+        groups = self._groups(groups, np.int32)
+        if groups is not None and groups.shape[0] != D:
+            raise ValueError(f"groups must have one entry for each of the {D} detectors")
+        G = 1 if groups is None or not groups.size else max(int(groups.max()) + 1, 1)
+        return groups, _tod_args.check_count(G, "the number of groups", covariance.MAX_GROUPS)
+
+    def covariance(self, groups="band", field=None, model=None, min_hits=8, ctx=None, device="cuda:0"):
+        """``(tod, cov)``: the flag-aware covariance between the detectors of each group (maria_amd.covariance.covariance,
+        DESIGN 3.34) of the signal (the sum of the fields, or the one ``field``; less ``model``) over the samples whose
+        ``flags`` are 0, and this TOD with ``metadata["covariance"]`` recording ``n_groups``, ``min_hits``, ``field`` and
+        per group the ``rows``, the number of ``unusable`` rows and the largest eigenvalue's share of the usable
+        correlation matrix' trace.  ``groups``: "band", None (one group) or an integer array, -1 leaving a detector
+        out (at most 16 groups).  Nothing of this TOD is copied or changed."""
+        from . import covariance
+
+        min_hits = _tod_args.check_min_hits(min_hits)
+        if field is not None and field not in self.data:
+            raise ValueError(f"field {field!r}: one of the fields {self.fields}")
+        signal = self._signal(device, field)
+        groups, G = self._covariance_groups(groups, signal.shape[0])
+        model, flags, ctx = self._operands(signal, model, ctx)
+        cov = covariance.covariance(signal, groups=groups, n_groups=G, flags=flags, model=model, min_hits=min_hits, ctx=ctx)
+        per_group = []
+        for cg in cov.groups:
+            usable = int((~cg.unusable).sum())
+            share = float(covariance.leading_modes(cg, 1)[0][0]) / usable if usable else float("nan")
+            per_group.append({"rows": cg.rows.cpu().numpy(), "unusable": int(cg.unusable.sum()), "leading_share": share})
+        record = {"n_groups": G, "min_hits": min_hits, "field": field, "groups": per_group}
+        return self._derived(record={"covariance": record}), cov
+
+    def remove_modes(self, n_modes=1, groups="band", model=None, into=None, min_hits=8, rcond=1e-10, remove_mean=False, ctx=None,
+                     device="cuda:0"):
+        """A new TOD with the ``n_modes`` (1 .. 7) leading modes of each group's flag-aware correlation matrix removed
+        (maria_amd.covariance); after ``remove_common_mode`` or in its place, before ``filter_subscans``.
+        Per group of detectors (``groups`` as in :meth:`remove_common_mode`): the covariance of the signal (the sum of the
+        fields, less ``model``) over the samples whose flags are 0, the leading eigenvectors of its correlation matrix
+        (``covariance.leading_modes``), and per mode the time template that is the flag-aware projection of the
+        normalised detectors onto the eigenvector (``covariance.mode_templates``).  Every detector is fitted to
+        [1, the templates] by least squares (``regress.normal_equations``, ``regress.solve``) and the modes are subtracted
+        from the field ``into`` (default: the first), the constant too only with ``remove_mean``.  Flagged samples take
+        part in no sum and are subtracted from like the rest; a detector that cannot be fitted, and every detector of a
+        group with fewer usable rows than modes, is left as it is.  Every field of the result is a float32 device copy;
+        ``flags``, ``dets``, ``coords``, ``units`` and the calibrator are carried over; ``metadata["modes"]`` records
+        ``n_modes``, ``n_groups``, ``min_hits``, ``rcond``, ``remove_mean``, the [G, n_modes] ``eigenvalues``, the
+        [D, n_modes] ``loadings``, the [D, 1 + n_modes] ``coefficients``, the [G, 1 + n_modes, T] float32 ``templates``
+        and ``failed_rows``.  This TOD is left as it is."""
+        import torch
+
+        from . import covariance, regress
+
+        min_hits = _tod_args.check_min_hits(min_hits)
+        n_modes = _tod_args.check_count(n_modes, "n_modes", covariance.MAX_MODES)
+        data, signal, model, flags, into, ctx = self._device_fields(model, into, ctx, device)
+        groups, G = self._covariance_groups(groups, signal.shape[0])
+        cov = covariance.covariance(signal, groups=groups, n_groups=G, flags=flags, model=model, min_hits=min_hits, ctx=ctx)
+        eig, U = covariance.loadings(cov, n_modes)
+        B = torch.ones((G, 1 + n_modes, signal.shape[1]), dtype=torch.float32, device=signal.device)
+        B[:, 1:, :] = covariance.mode_templates(signal, cov, U, flags=flags, model=model, ctx=ctx)
+        N, r, hits = regress.normal_equations(signal, B, groups=groups, flags=flags, model=model, ctx=ctx)
+        del signal
+        a, ok = regress.solve(N, r, hits, min_hits=min_hits, rcond=rcond)
+        sub = a if remove_mean else torch.cat([torch.zeros_like(a[:, :1]), a[:, 1:]], dim=1).contiguous()
+        regress.apply(data[into], B, sub, groups=groups, sign=-1, out=data[into], ctx=ctx)
+        grouped = np.ones(a.shape[0], bool) if groups is None else groups >= 0  # a detector left out has not failed
+        record = {"n_modes": n_modes, "n_groups": G, "min_hits": min_hits, "rcond": float(rcond), "remove_mean": bool(remove_mean),
+                  "eigenvalues": eig.cpu().numpy(), "loadings": U.cpu().numpy(), "coefficients": a.cpu().numpy(),
+                  "templates": B.cpu().numpy(), "failed_rows": np.flatnonzero(~ok.cpu().numpy() & grouped)}
+        return self._derived(data=data, record={"modes": record})
+
+    def cut_uncorrelated(self, groups="band", n_sigma=5.0, min_correlation=None, min_hits=8, value=1, model=None, ctx=None,
+                         device="cuda:0"):
+        """``(tod, verdict)``: a new TOD whose flags also cover the detectors that do not see what their group sees
+        (maria_amd.covariance); after ``fix_jumps`` / ``mask_source`` and BEFORE ``remove_ground`` /
+        ``remove_common_mode``: once the common mode is out, a live detector no longer correlates with its neighbours.
+        Per group (``groups`` as in :meth:`cut`) a detector's score is the median of its correlation with the other
+        usable detectors (``covariance.correlation_score``) of the signal (the sum of the fields, less ``model``) over
+        the samples whose flags are 0.  A detector is cut if its score is a low-side outlier of its group's
+        (``cuts.find_outliers``, ``n_sigma`` robust scales below the median), if it is below ``min_correlation`` where
+        one is given, or if it is unusable (fewer than max(min_hits, 1) samples kept, a constant row, a NaN; no valid
+        partner).  ``value`` (1 .. 255) is ORed into the flags of every sample of a cut detector
+        (``cuts.flag_segments``).  ``verdict``: the [D] float64 ``score``, the [D] bool ``outlier``, ``below``,
+        ``unusable`` and ``cut`` and per group ``median`` and ``threshold`` (NaN where no scale exists), as numpy arrays;
+        ``metadata["uncorrelated"]`` records it with the parameters.  Every field of the result is a float32 device
+        copy, unchanged.  This TOD is left as it is."""
+        import torch
+
+        from . import covariance, cuts
+
+        min_hits = _tod_args.check_min_hits(min_hits, allow_bool=False)
+        if isinstance(value, bool) or int(value) != value or not 1 <= int(value) <= 255:
+            raise ValueError(f"value {value}: an integer in 1 .. 255")
+        n_sigma = float(n_sigma)
+        if not np.isfinite(n_sigma) or n_sigma <= 0:
+            raise ValueError(f"n_sigma {n_sigma}: finite and > 0")
+        if min_correlation is not None and not -1.0 <= float(min_correlation) <= 1.0:
+            raise ValueError(f"min_correlation {min_correlation}: None or in [-1, 1]")
+        data, signal, model, flags, _, ctx = self._device_fields(model, None, ctx, device)
+        D, T = signal.shape
+        groups, G = self._covariance_groups(groups, D)
+        cov = covariance.covariance(signal, groups=groups, n_groups=G, flags=flags, model=model, min_hits=min_hits, ctx=ctx)
+        del signal
+        verdict = covariance.judge(cov, n_sigma, min_correlation)
+        new_flags = torch.zeros((D, T), dtype=torch.uint8, device=cov.mean.device) if flags is None else flags.clone()
+        if bool(verdict["cut"].any()):
+            cuts.flag_segments(new_flags, np.array([0, T], np.int32), verdict["cut"][:, None], value=int(value), ctx=ctx)
+        verdict = {k: v.cpu().numpy() for k, v in verdict.items()}
+        record = dict(verdict, n_groups=G, n_sigma=n_sigma, min_correlation=None if min_correlation is None else float(min_correlation),
+                      min_hits=min_hits, value=int(value), cut_detectors=np.flatnonzero(verdict["cut"]))
+        return self._derived(data=data, flags=new_flags, record={"uncorrelated": record}), verdict
+
     def filter_subscans(self, order=3, bounds=None, turn_frac=0.9, flag_turnarounds=True, flag_failed=True, model=None, into=None,
                         min_hits=8, rcond=1e-10, ctx=None, device="cuda:0"):
         """A new TOD with a Legendre polynomial of degree ``order`` (0 .. 7) fitted to every detector's signal (the sum of
