@@ -1151,6 +1151,31 @@ int mrx_tod_segment_normal(mrx_ctx* ctx, const float* d_x, size_t ld_x, const fl
 int mrx_tod_segment_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, const int32_t* d_bound, int S, int K,
                           const double* d_a, int sign, float* d_y, size_t ld_y);
 
+/* The frozen projector of the subscan filter, in place on d_x, forward or transposed (maria_amd/subscans.py: freeze,
+ * project).  With M = (flags == 0), T the segment's basis and A = d_A[d][s] (the caller's N^-1, symmetric):
+ *   transpose 0:  F   = I - T A T^t M        transpose 1:  F^t = I - M T A T^t
+ * For every (row, segment) with d_ok[d][s] != 0 and hi > lo:
+ *   pass 1   r[i] = sum of P_i * (double)x[d][t] over the segment's t with flags[d][t] == 0 (transpose 0: a flagged
+ *            sample is selected away, never multiplied) or over all of its t (transpose 1), added in the order of
+ *            mrx_tod_segment_normal's r: the same bits as that entry gives for the same x and flags (without flags)
+ *   solve    a[i] = s, with s = 0.0; for j = 0 .. K - 1: s = s + A[i][j] * r[j]
+ *   pass 2   x[d][t] = x[d][t] - (float)s2, with s2 = 0.0; for i = 0 .. K - 1: s2 = s2 + a[i] * P_i(u(t))
+ *            (mrx_tod_segment_apply's expression, sign -1) on every t of the segment (transpose 0) or on those with
+ *            flags[d][t] == 0 (transpose 1)
+ * and d_a[d][s] = a.  A pair with d_ok == 0, or an empty segment, is neither read nor written in d_x; its d_a is zeros.
+ * Samples in no segment are untouched.  d_flags NULL: nothing is flagged.  Segments must not overlap (ascending bounds:
+ * the caller's business, as above); the bounds are clamped.  No atomics: the same bits on every call, for a row or a
+ * segment computed alone, and at any alignment.
+ *  d_x     [D][ld_x] float32, MODIFIED in place
+ *  d_A     [D][S][K][K] float64
+ *  d_ok    [D][S] uint8
+ *  d_a     [D][S][K] float64, OVERWRITTEN, or NULL
+ * D < 1, T < 1, S < 1, K outside 1 .. 8, transpose not 0 or 1, ld_x < T, ld_f < T with flags given, or a null d_x,
+ * d_bound, d_A or d_ok -> MRX_ERR_INVALID with d_x and d_a untouched */
+int mrx_tod_segment_project(mrx_ctx* ctx, float* d_x, size_t ld_x, const uint8_t* d_flags, size_t ld_f, int D, int T,
+                            const int32_t* d_bound, int S, int K, const double* d_A, const uint8_t* d_ok, int transpose,
+                            double* d_a);
+
 /* ---- statistics per (row, segment) and the flagging of whole segments (maria_amd/cuts.py) ------------- */
 
 /* Common to the two entries below.  d_flags, d_model, their pitches, term(d, t), the single float64 roundings (no fused

@@ -20,6 +20,10 @@
 // over the clamped bounds (the largest s with bound[s] <= t), keeps it while the following samples stay inside, and
 // checks lo <= t < hi: with bounds that do not ascend a sample may take another segment than the caller meant, but every
 // index is inside the arrays whatever d_bound holds.
+//
+// mrx_tod_segment_project.  The filter with its flags fixed, F = I - T A T^t M or its transpose, in place: the sums of the
+// first entry, a K x K product with the caller's frozen A = N^-1, and the subtraction of the second, one wave a (row,
+// segment) for all three.  Its comment is above its kernel.
 #include "mrx_internal.h"
 
 #include <algorithm>
@@ -194,6 +198,114 @@ __global__ __launch_bounds__(kThreads) void segment_apply_kernel(const float* x,
   }
 }
 
+// The frozen projector of a (row, segment), in place: r = sum P x (pass 1), a = A r, x -= (float)(sum a_i P_i) (pass 2).
+// Pass 1 is segment_normal_kernel's r, operation for operation (its kFlight loop, its selects, its butterfly), over the
+// unflagged samples (forward) or over all of them (transposed); pass 2 is segment_apply_kernel's expression on every
+// sample (forward) or on the unflagged ones (transposed), each lane on the samples it read in pass 1: lo + lane,
+// lo + lane + 64, ..  Pass 2 reads its samples from global memory a second time: a segment is a few KiB that one wave
+// has just streamed, and nobody else writes it.  A pair that is not ok, or is empty, touches no sample.
+template <int K>
+__global__ __launch_bounds__(kThreads) void segment_project_kernel(float* x, size_t ld_x, const unsigned char* __restrict__ flags, size_t ld_f, int T,
+                                                                   const int* __restrict__ bound, int S, const double* __restrict__ A,
+                                                                   const unsigned char* __restrict__ ok, int transpose, double* __restrict__ a_out,
+                                                                   long long n_items) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+  for (long long item = (long long)blockIdx.x * kWaves + wave; item < n_items; item += (long long)gridDim.x * kWaves) {
+    const long long d = item / S;
+    const int s = (int)(item - d * S);
+    const int lo = clamp_bound(bound[s], T), hi = clamp_bound(bound[s + 1], T);
+    const int L = hi - lo;
+    if (L <= 0 || ok[item] == 0) {  // the same for the whole wave
+      if (a_out && lane < K) a_out[(size_t)item * K + lane] = 0.0;
+      continue;
+    }
+    const double span = (double)(L - 1);
+    float* const xr = x + (size_t)d * ld_x;
+    const unsigned char* const fr = flags ? flags + (size_t)d * ld_f : nullptr;
+    const unsigned char* const f1 = transpose ? nullptr : fr;  // the mask of pass 1
+    const unsigned char* const f2 = transpose ? fr : nullptr;  // the mask of pass 2
+    double acc[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) acc[i] = 0.0;
+    for (int k0 = lane; k0 < L; k0 += kFlight * kWave) {
+      float xv[kFlight];
+      unsigned char fv[kFlight];
+#pragma unroll
+      for (int e = 0; e < kFlight; ++e) {
+        const int k = k0 + e * kWave;
+        const bool in = k < L;
+        xv[e] = in ? xr[lo + k] : 0.0f;
+        fv[e] = in ? (f1 ? f1[lo + k] : (unsigned char)0) : (unsigned char)1;
+      }
+#pragma unroll
+      for (int e = 0; e < kFlight; ++e) {
+        const int k = k0 + e * kWave;
+        const bool keep = fv[e] == 0;
+        const double u = L > 1 ? (2.0 * (double)k - span) / span : 0.0;
+        double P[K], b[K];
+        legendre<K>(u, P);
+#pragma unroll
+        for (int i = 0; i < K; ++i) b[i] = keep ? P[i] : 0.0;
+        const double term = keep ? (double)xv[e] : 0.0;
+#pragma unroll
+        for (int i = 0; i < K; ++i) acc[i] = acc[i] + b[i] * term;
+      }
+    }
+#pragma unroll
+    for (int o = kWave / 2; o >= 1; o >>= 1) {
+#pragma unroll
+      for (int i = 0; i < K; ++i) acc[i] = acc[i] + __shfl_xor(acc[i], o, kWave);
+    }
+    // every lane holds every r_i and forms every a_i: the same bits in all of them
+    const double* const As = A + (size_t)item * (K * K);
+    double a[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      double sum = 0.0;
+#pragma unroll
+      for (int j = 0; j < K; ++j) sum = sum + As[i * K + j] * acc[j];
+      a[i] = sum;
+    }
+    if (a_out) {
+      int me = lane;
+      asm volatile("" : "+v"(me));
+      double va = 0.0;
+#pragma unroll
+      for (int i = 0; i < K; ++i) va = me == i ? a[i] : va;
+      if (lane < K) a_out[(size_t)item * K + lane] = va;
+    }
+    for (int k0 = lane; k0 < L; k0 += kFlight * kWave) {
+      float xv[kFlight];
+      bool on[kFlight];
+#pragma unroll
+      for (int e = 0; e < kFlight; ++e) {
+        const int k = k0 + e * kWave;
+        on[e] = k < L && (f2 ? f2[lo + k] == 0 : true);
+        xv[e] = on[e] ? xr[lo + k] : 0.0f;
+      }
+#pragma unroll
+      for (int e = 0; e < kFlight; ++e) {
+        const int k = k0 + e * kWave;
+        const double u = L > 1 ? (2.0 * (double)k - span) / span : 0.0;
+        double P[K];
+        legendre<K>(u, P);
+        double sum = 0.0;
+#pragma unroll
+        for (int i = 0; i < K; ++i) sum = sum + a[i] * P[i];
+        if (on[e]) xr[lo + k] = xv[e] - (float)sum;
+      }
+    }
+  }
+}
+
+template <int K>
+void launch_project(mrx_ctx* ctx, float* x, size_t ld_x, const uint8_t* flags, size_t ld_f, int T, const int32_t* bound, int S, const double* A,
+                    const uint8_t* ok, int transpose, double* a, long long n_items) {
+  hipLaunchKernelGGL(segment_project_kernel<K>, dim3(mrx_resident_blocks(ctx, (n_items + kWaves - 1) / kWaves)), dim3(kThreads), 0, ctx->stream, x, ld_x,
+                     flags, ld_f, T, bound, S, A, ok, transpose, a, n_items);
+}
+
 bool aligned(const void* p, size_t ld_bytes, unsigned to) { return (((uintptr_t)p | (uintptr_t)ld_bytes) & (to - 1u)) == 0; }
 
 template <int K>
@@ -253,6 +365,37 @@ int mrx_tod_segment_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, in
   const int wide = (aligned(d_x, ld_x * 4, 16) ? kWideX : 0) | (aligned(d_y, ld_y * 4, 16) ? kWideY : 0);
   hipLaunchKernelGGL(segment_apply_kernel, dim3(mrx_resident_blocks(ctx, n_tiles)), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, d_bound, S, K,
                      d_a, sign, d_y, ld_y, wide, tiles_per_row, n_tiles);
+  MRX_CHECK_LAUNCH(ctx);
+  return MRX_OK;
+}
+
+int mrx_tod_segment_project(mrx_ctx* ctx, float* d_x, size_t ld_x, const uint8_t* d_flags, size_t ld_f, int D, int T, const int32_t* d_bound, int S,
+                            int K, const double* d_A, const uint8_t* d_ok, int transpose, double* d_a) {
+  MRX_ENTER(ctx);
+  if (!ctx) return MRX_ERR_INVALID;
+  MRX_REQUIRE(ctx, d_x && d_bound && d_A && d_ok, "null pointer");
+  MRX_REQUIRE(ctx, D >= 1 && T >= 1, "need D >= 1 rows of T >= 1 samples");
+  MRX_REQUIRE(ctx, S >= 1, "need S >= 1 segments");
+  MRX_REQUIRE(ctx, K >= 1 && K <= kMaxOrder, "K must be in 1 .. 8");
+  MRX_REQUIRE(ctx, transpose == 0 || transpose == 1, "transpose must be 0 or 1");
+  MRX_REQUIRE(ctx, ld_x >= (size_t)T && (!d_flags || ld_f >= (size_t)T), "ld_x or ld_f smaller than T");
+  const long long n_items = (long long)D * S;
+#define MRX_SEGMENT_PROJECT(k) \
+  case k:                      \
+    launch_project<k>(ctx, d_x, ld_x, d_flags, ld_f, T, d_bound, S, d_A, d_ok, transpose, d_a, n_items); \
+    break
+  switch (K) {
+    MRX_SEGMENT_PROJECT(1);
+    MRX_SEGMENT_PROJECT(2);
+    MRX_SEGMENT_PROJECT(3);
+    MRX_SEGMENT_PROJECT(4);
+    MRX_SEGMENT_PROJECT(5);
+    MRX_SEGMENT_PROJECT(6);
+    MRX_SEGMENT_PROJECT(7);
+    default:
+      MRX_SEGMENT_PROJECT(8);
+  }
+#undef MRX_SEGMENT_PROJECT
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;
 }

@@ -86,9 +86,33 @@ def bin_map(ctx, sky, inp, msum, mwgt, bucketed=None):
         ctx.call("mrx_bin_map", *args)
 
 
+class _AfterSubscans:
+    """F = F_pre F' of one TOD: the subscan projector F' (``subscans.Projector``), then the recorded pre-processing steps
+    (``tod_processing.PreprocessOperator``); the transpose in the reverse order.  In place, like its two parts."""
+
+    def __init__(self, projector, pre):
+        self.projector, self.pre = projector, pre
+
+    def apply(self, buf):
+        self.projector.apply(buf)
+        return self.pre.apply(buf)
+
+    def apply_transpose(self, buf):
+        self.pre.apply_transpose(buf)
+        return self.projector.apply_transpose(buf)
+
+    def product(self):
+        out = self.pre.product()
+        return {**out, "steps": ["filter_subscans"] + out["steps"], "subscans": self.projector.product()}
+
+
 class _GridMapper:
     """What the mappers share: the tangent-plane grid (mappers/base.py:295-301), the frame, the units, the map channels
     and, per TOD, the device inputs of the binning's pointing."""
+
+    def _subscan_spec(self, tod):
+        """The subscan filter a mapper solves through for this TOD (MaximumLikelihoodMapper's ``subscan_filter``), or None."""
+        return None
 
     def _init_grid(self, tods, center, width, height, resolution, stokes, nu, frame, units, degrees, bilinear, tod_preprocessing,
                    device):
@@ -137,7 +161,18 @@ class _GridMapper:
             from .tod_processing import preprocess_operator, process_tod
 
             config = {k: dict(v) for k, v in self.tod_preprocessing.items()}
-            if with_operator:
+            spec = self._subscan_spec(tod) if with_operator else None
+            if spec is not None:  # F = F_pre F': the subscan projector first, the recorded steps on its result
+                from . import subscans
+
+                rows = field_sum(tod.data.values(), dev)
+                flags = None if getattr(tod, "flags", None) is None else torch.as_tensor(tod.flags).to(dev, torch.uint8).contiguous()
+                projector = subscans.Projector(rows, spec["bounds"], spec["order"] + 1, flags=flags, min_hits=spec["min_hits"],
+                                               rcond=spec["rcond"], ctx=ctx)
+                projector.apply(rows)
+                done, operator = preprocess_operator(tod._derived(data={"total": rows}), config=config, ctx=ctx, device=dev)
+                operator = _AfterSubscans(projector, operator)
+            elif with_operator:
                 done, operator = preprocess_operator(tod, config=config, ctx=ctx, device=dev)
             else:
                 done = process_tod(tod, config=config, ctx=ctx, device=dev)
@@ -433,21 +468,85 @@ class MaximumLikelihoodMapper(_GlsMapper):
     row norms the data gave) and W as above.  Conjugate gradients with nearest and bilinear pointing alike (F couples
     pixels), preconditioned by the blocks of P^T W P, from the block solve.  ``products["filter_aware"]`` is True and
     ``products["preprocessing"]`` holds per TOD the ``steps`` applied and, for remove_modes, ``modes`` (U [D, m]) and
-    ``row_norms``.  An empty ``tod_preprocessing`` is F = I, the plain map.  Not with ``noise_model`` or ``noise_modes``."""
+    ``row_norms``.  An empty ``tod_preprocessing`` is F = I, the plain map.  Not with ``noise_model`` or ``noise_modes``.
+
+    ``subscan_filter`` (only with ``filter_aware=True``) puts the subscan polynomial filter in front of those
+    steps, F = F_pre F':  F' = I - T A T^t M per (detector, segment), the projector ``subscans.Projector`` rebuilds from
+    the TOD's own flags (M = (flags == 0), the mask W uses; turnarounds count only if the TOD flagged them) and applies to
+    the data once more.  F' T = 0 under any mask, so F' F = F' for the filter F that ``TOD.filter_subscans`` applied
+    on the same segments and order, whatever was flagged then: nothing of that filter's state is needed, and a TOD handed
+    over unfiltered gives the same map.  A pair that cannot be fitted is the identity in data and model alike.  This
+    marginalises a polynomial baseline per (detector, subscan) inside the solve.  ``"recorded"``: ``order``, ``bounds``,
+    ``min_hits`` and ``rcond`` of each TOD's ``metadata["subscans"]`` (ValueError where a TOD has none); a dict of
+    ``order`` (3), ``bounds`` (None: ``subscans.find_subscans`` of the boresight azimuth with ``turn_frac``, 0.9),
+    ``min_hits`` (8) and ``rcond`` (1e-10); or a list of such entries, one per TOD.  ``products["preprocessing"][i]``
+    then has ``steps`` starting with "filter_subscans" and ``subscans``: ``order``, ``bounds`` and the ``unfitted``
+    (detector, segment) pairs."""
 
     def __init__(self, tods, center, width=None, height=None, resolution=None, stokes="IQU", nu=None, frame="ra/dec", units="K_RJ",
                  degrees=True, bilinear=False, tod_preprocessing=None, noise_weights="inverse_variance", max_iter=100, tol=1e-6, rcond=1e-3,
-                 device="cuda:0", noise_fit=None, noise_model=None, noise_filter_length=None, noise_modes=None, filter_aware=False):
+                 device="cuda:0", noise_fit=None, noise_model=None, noise_filter_length=None, noise_modes=None, filter_aware=False,
+                 subscan_filter=None):
         if not isinstance(filter_aware, (bool, np.bool_)):
             raise ValueError(f"filter_aware {filter_aware!r}: True or False")
         if filter_aware and (noise_model is not None or noise_modes is not None):
             raise ValueError("filter_aware cannot be set with noise_model or noise_modes: F^T N^-1 F is not built")
+        if subscan_filter is not None and not filter_aware:
+            raise ValueError("subscan_filter is used only with filter_aware=True: the map is solved through the filter")
         self.filter_aware = bool(filter_aware)
         self._init_grid(tods, center, width, height, resolution, stokes, nu, frame, units, degrees, bilinear, tod_preprocessing, device)
         self._init_gls(stokes, noise_weights, max_iter, tol, rcond, noise_fit)
         self._init_noise_model(noise_model, noise_filter_length)
         self._init_noise_modes(noise_modes)
         self._check_noise_fit_used()
+        self._init_subscan_filter(subscan_filter)
+
+    SUBSCAN_KEYS = {"order": 3, "bounds": None, "turn_frac": 0.9, "min_hits": 8, "rcond": 1e-10}  # TOD.filter_subscans' defaults
+
+    def _init_subscan_filter(self, value):
+        """``self.subscan_filter``: None, or per TOD the resolved ``order``, ``bounds`` (int32, ascending, clamped to the
+        TOD), ``min_hits`` and ``rcond``.  Everything is checked here, on the host."""
+        from . import subscans
+        from .tod import check_bounds_array
+
+        self.subscan_filter = None
+        if value is None:
+            return
+        entries = list(value) if isinstance(value, (list, tuple)) else [value] * len(self.tods)
+        if len(entries) != len(self.tods):
+            raise ValueError(f"subscan_filter has {len(entries)} entries; there are {len(self.tods)} TODs")
+        specs = []
+        for entry, tod in zip(entries, self.tods):
+            if isinstance(entry, str):
+                if entry != "recorded":
+                    raise ValueError(f"subscan_filter '{entry}': 'recorded', a dict of {sorted(self.SUBSCAN_KEYS)} or a list of them")
+                meta = (getattr(tod, "metadata", None) or {}).get("subscans")
+                if meta is None:
+                    raise ValueError("subscan_filter='recorded': a TOD has no metadata['subscans'] (TOD.filter_subscans records it)")
+                entry = {k: meta[k] for k in ("order", "bounds", "min_hits", "rcond")}
+            elif not isinstance(entry, dict) or set(entry) - set(self.SUBSCAN_KEYS):
+                raise ValueError(f"subscan_filter {entry!r}: 'recorded', a dict of {sorted(self.SUBSCAN_KEYS)} or a list of them")
+            spec = {**self.SUBSCAN_KEYS, **entry}
+            order = spec["order"]
+            if isinstance(order, bool) or int(order) != order or not 0 <= int(order) < subscans.MAX_ORDER:
+                raise ValueError(f"subscan_filter order {order}: an integer in 0 .. {subscans.MAX_ORDER - 1}")
+            min_hits = spec["min_hits"]
+            if int(min_hits) != min_hits or int(min_hits) < 0:
+                raise ValueError(f"subscan_filter min_hits {min_hits}: an integer >= 0")
+            if not 0.0 <= float(spec["rcond"]) < 1.0:
+                raise ValueError(f"subscan_filter rcond {spec['rcond']}: in [0, 1)")
+            T = int(np.asarray(tod.coords.t).size)
+            if spec["bounds"] is None:
+                bounds, _ = subscans.find_subscans(tod.coords._baz, spec["turn_frac"])
+            else:
+                bounds = check_bounds_array(spec["bounds"], T)
+            specs.append({"order": int(order), "bounds": np.asarray(bounds, np.int32), "min_hits": int(min_hits), "rcond": float(spec["rcond"])})
+        self.subscan_filter = specs
+
+    def _subscan_spec(self, tod):
+        if self.subscan_filter is None:
+            return None
+        return next(spec for spec, t in zip(self.subscan_filter, self.tods) if t is tod)
 
     def _init_noise_model(self, model, length):
         self.noise_model, self.noise_filter_length = model, length

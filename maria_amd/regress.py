@@ -155,7 +155,20 @@ def solve(N, r, hits, min_hits=8, rcond=1e-10):
     if not isinstance(N, torch.Tensor) or not isinstance(r, torch.Tensor) or N.dim() != 3 or N.shape[1] != N.shape[2] or r.dim() != 2 \
             or N.shape[:2] != r.shape or N.dtype != torch.float64 or r.dtype != torch.float64:
         raise ValueError("N must be a [D, K, K] and r a [D, K] float64 tensor")
-    D, K = r.shape
+    L, s, ok = scaled_factor(N, hits, min_hits, rcond)
+    a = torch.cholesky_solve((r * s)[:, :, None], L)[:, :, 0] * s
+    return torch.where(ok[:, None], a, torch.zeros_like(a)), ok
+
+
+def scaled_factor(N, hits, min_hits=8, rcond=1e-10):
+    """``(L [D, K, K], s [D, K], ok [D] bool)`` of ``solve``: the Cholesky factor of M = (N * s_i) * s_j (the identity where
+    the row is not ok), s = 1 / sqrt(diag N) and the verdict, for ``solve`` and for what freezes N^-1
+    (``subscans.freeze``)."""
+    import torch
+
+    if not isinstance(N, torch.Tensor) or N.dim() != 3 or N.shape[1] != N.shape[2] or N.dtype != torch.float64:
+        raise ValueError("N must be a [D, K, K] float64 tensor")
+    D, K = N.shape[:2]
     check_count(K, "K", MAX_TEMPLATES)
     if not isinstance(hits, torch.Tensor) or tuple(hits.shape) != (D,) or hits.dtype.is_floating_point:
         raise ValueError(f"hits must be {D} integers, one per row")
@@ -170,9 +183,7 @@ def solve(N, r, hits, min_hits=8, rcond=1e-10):
     L, info = torch.linalg.cholesky_ex(M)
     pivot = torch.diagonal(L, dim1=1, dim2=2).square().amin(dim=1)
     ok = good & (info == 0) & (pivot >= float(rcond))  # a NaN pivot compares false
-    L = torch.where(ok[:, None, None], L, eye)
-    a = torch.cholesky_solve((r * s)[:, :, None], L)[:, :, 0] * s
-    return torch.where(ok[:, None], a, torch.zeros_like(a)), ok
+    return torch.where(ok[:, None, None], L, eye), s, ok
 
 
 def legendre_templates(T, order):

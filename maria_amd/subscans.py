@@ -14,7 +14,12 @@ of L samples:
 
 The polynomials are evaluated in the kernels, in float64, and never stored.  Every sum is added in a fixed order (a
 function of the segment's ends alone), without atomics: the same inputs give the same bits on every call.  The order of
-the operations is written out in include/mrx.h, and tests/subscans_ref.py restates it in numpy."""
+the operations is written out in include/mrx.h, and tests/subscans_ref.py restates it in numpy.
+
+With the flags fixed the filter is a linear operator, F = I - T A T^t M (M = (flags == 0), T the basis, A = N^-1 where the
+pair can be fitted and 0 otherwise): ``freeze`` gives A, ``project`` applies F or F^t in one fused pass
+(``mrx_tod_segment_project``), and ``Projector`` holds both for one TOD, for ``MaximumLikelihoodMapper(subscan_filter=...)``
+(tests/subscan_project_ref.py restates it in numpy)."""
 
 from __future__ import annotations
 
@@ -169,3 +174,89 @@ def inject_drifts(x, bounds, coeffs, ctx=None):
     """A new tensor: ``x`` plus the polynomial drifts ``coeffs`` [D, S, K] float64, ``apply`` with sign +1 (for tests and
     demonstrations)."""
     return apply(x, bounds, coeffs, sign=+1, ctx=ctx)
+
+
+def freeze(N, hits, min_hits=8, rcond=1e-10):
+    """``(A [D, S, K, K] float64, ok [D, S] uint8)``: the inverse of every (row, segment)'s normal matrix, for ``project``.
+    ``ok`` is ``regress.solve``'s verdict on the same N, hits, ``min_hits`` and ``rcond``; with its scaled Cholesky factor
+    L of M = (N * s_i) * s_j, s = 1 / sqrt(diag N):  B = (cholesky_solve(I, L) * s_i) * s_j,  A = (B + B^T) / 2 (the same
+    bits on both sides of the diagonal, a + b being b + a), and zero where the pair is not ok.  N does not depend on the
+    data: ``normal_equations`` of any [D, T] buffer under the flags gives it.  On the tensors' device, no host
+    synchronisation."""
+    import torch
+
+    from .regress import scaled_factor
+
+    if not isinstance(N, torch.Tensor) or N.dim() != 4 or N.shape[2] != N.shape[3] or N.dtype != torch.float64:
+        raise ValueError("N must be a [D, S, K, K] float64 tensor")
+    D, S, K = N.shape[:3]
+    if not isinstance(hits, torch.Tensor) or tuple(hits.shape) != (D, S) or hits.dtype.is_floating_point or hits.device != N.device:
+        raise ValueError(f"hits must be a [{D}, {S}] integer tensor on N's device")
+    L, s, ok = scaled_factor(N.reshape(D * S, K, K), hits.reshape(D * S), min_hits, rcond)
+    eye = torch.eye(K, dtype=torch.float64, device=N.device).expand(D * S, K, K)
+    B = (torch.cholesky_solve(eye, L) * s[:, :, None]) * s[:, None, :]
+    A = (B + B.transpose(1, 2)) * 0.5
+    A = torch.where(ok[:, None, None], A, torch.zeros_like(A))
+    return A.view(D, S, K, K).contiguous(), ok.view(D, S).to(torch.uint8)
+
+
+def project(x, bounds, A, ok, flags=None, transpose=False, coefficients=False, ctx=None):
+    """The frozen subscan filter on ``x`` ([D, T] float32 device tensor, any row pitch), in place: with M = (flags == 0),
+    T the segment's basis and ``A``, ``ok`` of ``freeze``,  x <- F x = x - T A T^t M x,  or with ``transpose``
+    x <- F^t x = x - M T A T^t x  (``mrx_tod_segment_project``; the order of every sum is in include/mrx.h).  A pair that
+    is not ok and samples in no segment keep their bits.  Returns ``x``, or with ``coefficients`` ``(x, a [D, S, K]
+    float64)``, a = A T^t M x (A T^t x transposed).  Everything the entry refuses, and bounds that do not ascend, raise
+    ValueError before any device call."""
+    import torch
+
+    from ._lib import ptr
+
+    D, T, ld_x = check_x(x)
+    d_bounds, S = _check_bounds(bounds, x)
+    if not isinstance(A, torch.Tensor) or A.dtype != torch.float64 or A.dim() != 4 or tuple(A.shape[:2]) != (D, S) or A.shape[2] != A.shape[3] \
+            or A.device != x.device:
+        raise ValueError(f"A must be a [{D}, {S}, K, K] float64 tensor on x's device")
+    K = check_count(A.shape[2], "K", MAX_ORDER)
+    if not isinstance(ok, torch.Tensor) or ok.dtype not in (torch.uint8, torch.bool) or tuple(ok.shape) != (D, S) or ok.device != x.device:
+        raise ValueError(f"ok must be a [{D}, {S}] uint8 tensor on x's device")
+    ld_f = check_like(flags, "flags", x, D, T, "uint8") if flags is not None else 0
+    if not isinstance(transpose, (bool, np.bool_)):
+        raise ValueError(f"transpose {transpose!r}: True or False")
+    if not x.is_cuda:  # the last refusal: a host tensor gets every other one first
+        raise ValueError("x must be a device tensor")
+    A, ok = A.contiguous(), ok.to(torch.uint8).contiguous()
+    a = torch.empty((D, S, K), dtype=torch.float64, device=x.device) if coefficients else None
+    context(ctx, x).call("mrx_tod_segment_project", ptr(x), ld_x, ptr(flags), ld_f, D, T, ptr(d_bounds), S, K, ptr(A), ptr(ok), int(bool(transpose)),
+                         ptr(a))
+    return (x, a) if coefficients else x
+
+
+class Projector:
+    """The subscan filter of one TOD as a fixed linear operator F' on float32 [D, T] device tensors, in place:
+    ``bounds`` [S + 1], ``K`` polynomials, ``flags`` ([D, T] uint8 device tensor or None) and, frozen from them alone,
+    ``A`` and ``ok`` (``freeze`` of ``normal_equations`` of ``like``, any [D, T] float32 device tensor: N does not depend
+    on the data).  F' T = 0 under its own mask, so F' F = F' for any earlier subscan filter F on these segments and this
+    order: a mapper needs nothing of that filter's state."""
+
+    def __init__(self, like, bounds, K, flags=None, min_hits=8, rcond=1e-10, ctx=None):
+        min_hits = check_min_hits(min_hits)
+        if not 0.0 <= float(rcond) < 1.0:
+            raise ValueError(f"rcond {rcond}: in [0, 1)")
+        N, _, hits = normal_equations(like, bounds, K, flags=flags, ctx=ctx)
+        self.bounds, self.K, self.flags, self.ctx, self.T = _check_bounds(bounds, like)[0], int(K), flags, ctx, int(like.shape[1])
+        self.A, self.ok = freeze(N, hits, min_hits=min_hits, rcond=rcond)
+
+    def apply(self, buf):
+        """buf <- F' buf."""
+        return project(buf, self.bounds, self.A, self.ok, flags=self.flags, ctx=self.ctx)
+
+    def apply_transpose(self, buf):
+        """buf <- F'^t buf."""
+        return project(buf, self.bounds, self.A, self.ok, flags=self.flags, transpose=True, ctx=self.ctx)
+
+    def product(self):
+        """What a mapper reports: ``order``, ``bounds`` and ``unfitted``, the [n, 2] (detector, segment) pairs of the
+        segments with samples on which F' is the identity (numpy)."""
+        bounds = self.bounds.cpu().numpy()
+        nonempty = np.diff(np.clip(bounds.astype(np.int64), 0, self.T)) > 0
+        return {"order": self.K - 1, "bounds": bounds, "unfitted": np.argwhere((self.ok.cpu().numpy() == 0) & nonempty[None, :])}

@@ -6,7 +6,14 @@ passes after a warm-up, each beside the bytes the entry has to move (4 D T of x,
 read + 4 D T written; the outputs of the reduction left out) and the time they take at the rate a device-to-device copy
 of the TOD reaches in the same run, which is measured first.  The lines go to stdout and to `out` (default
 profiles/subscans_bench.txt).
-Usage: python scripts/subscans_bench.py [n_det] [n_samples] [n_segments] [reps] [out]"""
+Usage: python scripts/subscans_bench.py [n_det] [n_samples] [n_segments] [reps] [out]
+
+With `project` as the first argument: the frozen projector of DESIGN 3.35 instead.  mrx_tod_segment_project forward and
+transposed beside the three-call form it replaces (mrx_tod_segment_normal, regress.solve of the D S systems,
+mrx_tod_segment_apply in place) and a copy of the TOD, at K = 4 and K = 8, without and with flags (3 % set); medians of
+`reps` (default 5) passes, to profiles/subscan_project_bench.txt.  The fused call has to move 4 D T read (+ D T of flags) and
+4 D T written; its second read of a segment is counted only if it misses the caches.
+Usage: python scripts/subscans_bench.py project [n_det] [n_samples] [n_segments] [reps] [out]"""
 import os
 import sys
 
@@ -32,7 +39,63 @@ def median_ms(fn, reps):
     return float(np.median([a.elapsed_time(b) for a, b in evs]))
 
 
+def project_main(argv):
+    from maria_amd.regress import solve
+
+    D = int(argv[0]) if len(argv) > 0 else 10000
+    T = int(argv[1]) if len(argv) > 1 else 240000
+    S = int(argv[2]) if len(argv) > 2 else 60
+    reps = int(argv[3]) if len(argv) > 3 else 5
+    out = argv[4] if len(argv) > 4 else os.path.join(ROOT, "profiles", "subscan_project_bench.txt")
+    dev = torch.device("cuda:0")
+    ctx = Context(0)
+    ctx.set_stream(torch.cuda.current_stream(dev))
+    x = torch.randn((D, T), dtype=torch.float32, device=dev)
+    flags = (torch.rand((D, T), device=dev) < 0.03).to(torch.uint8)
+    y = torch.empty_like(x)
+    bounds = torch.as_tensor(np.linspace(0, T, S + 1).round().astype(np.int32)).to(dev)
+    copy_ms = median_ms(lambda: y.copy_(x), reps)
+    del y
+    rate = 8.0 * D * T / copy_ms * 1e3
+    lines = [f"# frozen subscan projector of {D} x {T} float32 ({D * T * 4 / 1e9:.1f} GB) in {S} segments of {T // S} samples, medians of {reps} "
+             f"passes; a copy of the TOD takes {copy_ms:.3f} ms: {rate / 1e12:.2f} TB/s, the rate of every 'floor'"]
+    print(lines[0], flush=True)
+
+    def report(name, ms, nbytes):
+        floor = nbytes / rate * 1e3
+        lines.append(f"{name:58s} {ms:9.3f} ms   {nbytes / 1e9:6.2f} GB  {nbytes / ms / 1e6:7.0f} GB/s   floor {floor:6.3f} ms ({ms / floor:6.1f} x)")
+        print(lines[-1], flush=True)
+
+    for K in (4, 8):
+        for name, f in (("", None), (" + flags", flags)):
+            ld_f = T if f is not None else 0
+            nbytes = (8.0 + (1.0 if f is not None else 0.0)) * D * T
+            N, _, hits = subscans.normal_equations(x, bounds, K, flags=f, ctx=ctx)
+            A, ok = subscans.freeze(N, hits)
+            r = torch.empty((D, S, K), dtype=torch.float64, device=dev)
+            h32 = torch.empty((D, S), dtype=torch.int32, device=dev)
+            for word, transpose in (("forward", 0), ("transposed", 1)):
+                ms = median_ms(lambda: ctx.call("mrx_tod_segment_project", ptr(x), T, ptr(f), ld_f, D, T, ptr(bounds), S, K, ptr(A), ptr(ok),  # noqa: B023
+                                                transpose, None), reps)  # noqa: B023
+                report(f"mrx_tod_segment_project K = {K}{name} {word}", ms, nbytes)
+                x.normal_()  # the in-place passes drifted it
+
+            def three_calls():
+                ctx.call("mrx_tod_segment_normal", ptr(x), T, None, 0, ptr(f), ld_f, D, T, ptr(bounds), S, K, ptr(N), ptr(r), ptr(h32))  # noqa: B023
+                a, _ = solve(N.view(D * S, K, K), r.view(D * S, K), h32.view(D * S))  # noqa: B023
+                ctx.call("mrx_tod_segment_apply", ptr(x), T, D, T, ptr(bounds), S, K, ptr(a), -1, ptr(x), T)  # noqa: B023
+
+            ms = median_ms(three_calls, reps)
+            report(f"segment_normal + solve + segment_apply K = {K}{name}", ms, nbytes + 4.0 * D * T)  # x is read twice
+            x.normal_()
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "project":
+        return project_main(sys.argv[2:])
     D = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
     T = int(sys.argv[2]) if len(sys.argv) > 2 else 240000
     S = int(sys.argv[3]) if len(sys.argv) > 3 else 60
