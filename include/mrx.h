@@ -1111,6 +1111,58 @@ int mrx_tod_regress_normal(mrx_ctx* ctx, const float* d_x, size_t ld_x, const fl
 int mrx_tod_regress_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, const int32_t* d_group, int G,
                           const float* d_B, size_t ld_b, int K, const double* d_a, int sign, float* d_y, size_t ld_y);
 
+/* ---- planar and quadratic sky subtraction: a fit ACROSS the rows, sample by sample (maria_amd/sky_polynomial.py,
+ * DESIGN 3.36) ------------------------------------------------------------------------------------------------------- */
+
+/* Common to the two entries below.  The groups (1 <= G <= 16, a row whose entry is outside 0 .. G - 1 takes part in
+ * nothing), d_flags, d_model, their pitches, term(d, t), the single float64 roundings (no fused multiply-add), the
+ * absence of atomics, the alignment (none beyond the element size), "nothing is written past T" and "inputs are never
+ * modified" are those of the block above mrx_tod_column_mean.  d_P [D][K] float64, 1 <= K <= 6: the value of each of
+ * the K basis functions at the row (its detector's focal-plane position; maria_amd.sky_polynomial.basis). */
+
+/* The least-squares fit of the K basis functions across the rows of each group, at every sample: the transpose of
+ * mrx_tod_regress_normal.  A row takes part iff it is in a group and v[d] > 0; other rows are not read at all.  For
+ * group g and sample t, over the participating rows d with flags[d][t] == 0, in ascending d:
+ *   r[i]    = sum of (u[d] * P[d][i]) * (term(d, t) - off[d])
+ *   N[i][j] = sum of (v[d] * P[d][i]) * P[d][j]                      for i <= j
+ *   hits    = their number
+ * The order of the additions is the ascending row order of the group; it does not depend on the other rows or the other
+ * samples of the call, on alignment or on K (at K = 1 with P = 1, N and r are the bits of mrx_tod_column_mean's W and S).
+ * Then, in float64, every operation one rounding, the solve of N c = r:
+ *   s_i  = 1.0 / sqrt(N_ii);   M_ij = (N_ij * s_i) * s_j  (i <= j);   b_i = r_i * s_i
+ *   for j = 0 .. K - 1:   p_j = M_jj;  for k = 0 .. j - 1: p_j = p_j - L_jk * L_jk;   L_jj = sqrt(p_j);  q_j = 1.0 / L_jj
+ *                         for i = j + 1 .. K - 1:  w = M_ji;  for k = 0 .. j - 1: w = w - L_ik * L_jk;   L_ij = w * q_j
+ *   for i = 0 .. K - 1:   w = b_i;  for k = 0 .. i - 1: w = w - L_ik * z_k;   z_i = w * q_i
+ *   for i = K - 1 .. 0:   w = z_i;  for k = i + 1 .. K - 1: w = w - L_ki * a_k;   a_i = w * q_i
+ *   c_i  = a_i * s_i
+ * The sample is fitted iff hits >= max(min_hits, K), every N_ii > 0 and every pivot p_j >= rcond (a NaN compares
+ * false): the verdict of maria_amd.regress.solve.  A sample that is not fitted gets c = 0 and ok = 0.
+ *  d_x     [D][ld_x] float32
+ *  d_u, d_v [D] float64;  d_off [D] float64 or NULL (zeros)
+ *  d_c     [G][K][ld_c] float64, OVERWRITTEN in [0, T) of each row
+ *  d_ok    [G][T] uint8, OVERWRITTEN (1: fitted)
+ *  d_hits  [G][T] uint32, OVERWRITTEN, or NULL
+ *  d_N     [G][K (K + 1) / 2][T] float64, the upper triangle row after row, OVERWRITTEN, or NULL
+ *  d_r     [G][K][T] float64, OVERWRITTEN, or NULL
+ * D < 1, T < 1, G outside 1 .. 16, K outside 1 .. 6, a pitch (of an array that is given) < T, rcond outside [0, 1),
+ * min_hits < 1, or a null d_x, d_P, d_u, d_v, d_c or d_ok -> MRX_ERR_INVALID with the outputs untouched */
+int mrx_tod_column_fit(mrx_ctx* ctx, const float* d_x, size_t ld_x, const float* d_model, size_t ld_m,
+                       const uint8_t* d_flags, size_t ld_f, int D, int T, const int32_t* d_group, int G,
+                       const double* d_P, int K, const double* d_u, const double* d_v, const double* d_off,
+                       int min_hits, double rcond, double* d_c, size_t ld_c, uint8_t* d_ok, uint32_t* d_hits,
+                       double* d_N, double* d_r);
+
+/* Subtract (sign -1) or add (sign +1) each row's share of its group's fitted surface.  For a row d of group g:
+ *   s = 0.0; for i = 0 .. K - 1: s = s + c[g][i][t] * P[d][i]                  (two roundings a step, in this order)
+ *   y[d][t] = x[d][t] + sign * (float)(e[d] + h[d] * s)                        (one float32 operation)
+ * d_e [D] float64 or NULL (zeros), d_h [D] float64.  A row outside every group is copied.  d_y == d_x with
+ * ld_y == ld_x works in place.
+ * D < 1, T < 1, G outside 1 .. 16, K outside 1 .. 6, sign not -1 or +1, ld_x, ld_y or ld_c < T, a null d_x, d_P, d_c,
+ * d_h or d_y, or d_y == d_x with ld_y != ld_x -> MRX_ERR_INVALID with d_y untouched */
+int mrx_tod_column_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, const int32_t* d_group, int G,
+                         const double* d_P, int K, const double* d_c, size_t ld_c, const double* d_e,
+                         const double* d_h, int sign, float* d_y, size_t ld_y);
+
 /* ---- the subscan polynomial filter: a Legendre fit per (row, segment) (maria_amd/subscans.py) ---------- */
 
 /* Common to the two entries below.  d_flags, d_model, their pitches, term(d, t), the single float64 roundings (no fused

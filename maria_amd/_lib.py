@@ -239,6 +239,8 @@ SIGNATURES = {
     "mrx_tod_column_mean": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz]),
     "mrx_tod_regress_normal": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp, _i, _vp, _sz, _i, _vp, _vp, _vp]),
     "mrx_tod_regress_apply": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _vp, _sz, _i, _vp, _i, _vp, _sz]),
+    "mrx_tod_column_fit": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _d, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "mrx_tod_column_apply": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _vp, _i, _vp, _sz, _vp, _vp, _i, _vp, _sz]),
     "mrx_tod_segment_normal": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "mrx_tod_segment_apply": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _i, _vp, _i, _vp, _sz]),
     "mrx_tod_segment_project": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),

@@ -582,6 +582,66 @@ class TOD:
                   "common_mode": c.cpu().numpy(), "failed_rows": np.flatnonzero(~ok.cpu().numpy() & grouped)}
         return self._derived(data=data, record={"common_mode": record})
 
+    def remove_sky_polynomial(self, order=1, groups="band", n_iter=3, min_hits=8, min_dets=None, rcond=1e-10, flag_failed=True, model=None,
+                              into=None, ctx=None, device="cuda:0"):
+        """A new TOD with a planar (``order`` 1) or quadratic (2) sky surface removed sample by sample
+        (maria_amd.sky_polynomial; Sayers et al. 2010); in ``remove_common_mode``'s place in the chain, which
+        is its ``order`` 0.  Per group of detectors (``groups`` as in :meth:`remove_common_mode`) and at every sample a
+        polynomial in the detectors' focal-plane offsets (``sky_polynomial.basis`` of ``dets.offsets``: K = 1, 3 or 6
+        terms) is fitted by gain-weighted least squares to the signal (the sum of the fields, less ``model``) of the
+        detectors whose flag is 0 there, and y = x - (o_d + g_d sum_k c_k(t) P_dk) is taken from the field ``into``
+        (default: the first).  The gains g and offsets o are those of ``regress.fit_common_mode`` (``n_iter``,
+        ``min_hits`` samples a detector, ``rcond``); a detector whose fit failed there is left as it is and takes no part.
+        A sample with fewer than ``min_dets`` (None: 2 K) detectors left, or whose terms are degenerate on them
+        (``regress.solve``'s verdict with ``rcond``), has only the offset removed and, with ``flag_failed``, is flagged
+        in the group's rows.  Flagged samples take part in no sum and are subtracted from like the rest.  Every field of
+        the result is a float32 device copy; ``dets``, ``coords``, ``units`` and the pW <-> K_RJ calibrator are carried
+        over; ``metadata["sky_polynomial"]`` records ``order``, ``n_terms``, ``n_groups``, ``n_iter``, ``min_hits``,
+        ``min_dets``, ``rcond``, ``flag_failed``, the [D] ``gains`` and ``offsets``, the [G, K, T] float64
+        ``coefficients``, ``failed_rows`` and the [n, 2] (group, sample) ``failed_samples``.  This TOD is left as it is."""
+        import torch
+
+        from . import sky_polynomial
+
+        K = sky_polynomial.n_terms(order)
+        min_hits = _tod_args.check_min_hits(min_hits)
+        n_iter = _tod_args.check_count(n_iter, "n_iter", 64)
+        if not 0.0 <= float(rcond) < 1.0:
+            raise ValueError(f"rcond {rcond}: in [0, 1)")
+        groups = self._groups(groups, np.int32)
+        G = 1 if groups is None or not groups.size else max(int(groups.max()) + 1, 1)
+        _tod_args.check_count(G, "the number of groups", sky_polynomial.MAX_GROUPS)
+        min_dets = 2 * K if min_dets is None else min_dets
+        if isinstance(min_dets, bool) or int(min_dets) != min_dets or int(min_dets) < 1:
+            raise ValueError(f"min_dets {min_dets}: None or an integer >= 1")
+        offsets = np.asarray(self.dets.offsets, np.float64)
+        if groups is not None and groups.shape[0] != offsets.shape[0]:
+            raise ValueError(f"groups must have one entry for each of the {offsets.shape[0]} detectors")
+        P_host = sky_polynomial.basis(offsets, int(order), groups=groups, n_groups=G)
+        data, signal, model, flags, into, ctx = self._device_fields(model, into, ctx, device)
+        D, T = signal.shape
+        if D != P_host.shape[0]:
+            raise ValueError(f"fields of {D} rows: the detector table has {P_host.shape[0]}")
+        dev = signal.device
+        P = torch.as_tensor(P_host).to(dev)
+        c, ok_t, gains, offs, ok_d = sky_polynomial.fit_sky(signal, P, groups=groups, n_groups=G, flags=flags, model=model, n_iter=n_iter,
+                                                            min_hits=min_hits, min_dets=int(min_dets), rcond=rcond, ctx=ctx)
+        del signal
+        d_groups = torch.zeros(D, dtype=torch.int32, device=dev) if groups is None else torch.as_tensor(groups).to(dev)
+        fitted = torch.where(ok_d, d_groups, torch.full_like(d_groups, -1))  # a detector without gain and offset is copied
+        sky_polynomial.apply(data[into], P, c, gains, e=offs, groups=fitted, sign=-1, out=data[into], ctx=ctx)
+        new_flags = flags
+        if flag_failed:
+            inside = (d_groups >= 0) & (d_groups < G)
+            failed = ~ok_t[torch.where(inside, d_groups, torch.zeros_like(d_groups)).to(torch.int64)] & inside[:, None]  # [D, T]
+            new_flags = failed.to(torch.uint8) if flags is None else flags | failed.to(torch.uint8)
+        grouped = np.ones(D, bool) if groups is None else groups >= 0  # a detector left out has not failed
+        record = {"order": int(order), "n_terms": K, "n_groups": G, "n_iter": int(n_iter), "min_hits": min_hits, "min_dets": int(min_dets),
+                  "rcond": float(rcond), "flag_failed": bool(flag_failed), "gains": gains.cpu().numpy(), "offsets": offs.cpu().numpy(),
+                  "coefficients": c.cpu().numpy(), "failed_rows": np.flatnonzero(~ok_d.cpu().numpy() & grouped),
+                  "failed_samples": np.argwhere(~ok_t.cpu().numpy())}
+        return self._derived(data=data, flags=new_flags, record={"sky_polynomial": record})
+
     def _covariance_groups(self, groups, D):
         """(groups as [D] int32 or None, their number) for the covariance methods: at most 16 groups."""
         from . import covariance
