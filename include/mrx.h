@@ -1228,6 +1228,54 @@ int mrx_tod_segment_project(mrx_ctx* ctx, float* d_x, size_t ld_x, const uint8_t
                             const int32_t* d_bound, int S, int K, const double* d_A, const uint8_t* d_ok, int transpose,
                             double* d_a);
 
+/* ---- narrow spectral lines: an amplitude and a phase per (row, segment) (maria_amd/lines.py) ----------- */
+
+/* Common to the two entries below.  d_flags, d_model, their pitches, term(d, t), the single float64 roundings (no fused
+ * multiply-add), the absence of atomics, the alignment (none beyond the element size), "nothing is written past T" and
+ * "inputs are never modified" are those of the block above mrx_tod_column_mean; d_bound [S + 1], its clamping to 0 .. T
+ * in the kernels and the empty segment are those of the block above mrx_tod_segment_normal.
+ * The basis of a segment [lo, hi) of n = hi - lo samples for row d: n_poly in 0 .. 2 baseline functions and the two
+ * carriers of each of L lines, 1 <= L <= 3; K = n_poly + 2 L <= 8.  d_nu [D][L] float64 on the device: the frequency of
+ * line l in row d in cycles a sample, read as given (no range is enforced; a non-finite entry makes the sums of its own
+ * row NaN and nothing else).
+ *   B_0 = P_0 = 1.0,  B_1 = P_1 = u(t)          (the first n_poly of them: u and P of the block above
+ *                                                mrx_tod_segment_normal, a local baseline that keeps a drift out of the line)
+ *   theta = nu[d][l] * (double)t                (t the sample's index from the START OF THE ROW, not of the segment: the
+ *                                                phase is continuous across segments; the product one rounding)
+ *   q     = theta - rint(theta)                 (exact: |q| <= 1/2 lies on theta's own grid)
+ *   B_{n_poly + 2 l}     = cospi(2.0 * q)       (2.0 * q exact; cospi and sinpi the device library's float64 functions,
+ *   B_{n_poly + 2 l + 1} = sinpi(2.0 * q)        exactly 0 and +-1 at the quarter cycles)
+ * Every carrier is evaluated at its own sample; nothing is carried from one sample to the next. */
+
+/* The normal equations of every (row, segment).  For row d, segment s and kept = { t in the segment : flags[d][t] == 0 }:
+ *   N[d][s][i][j] = sum over kept of B_i * B_j                       (the product one rounding; the full symmetric matrix)
+ *   r[d][s][i]    = sum over kept of B_i * term(d, t)
+ *   hits[d][s]    = |kept|
+ * A flagged sample is selected away, never multiplied: what it holds (1e30 and NaN included) changes no bit.  An unflagged
+ * NaN stays in the r of its own (row, segment).  An empty segment gets zeros.  The sums of a (row, segment) are added in an
+ * order that is a function of lo and hi alone (mrx_tod_segment_normal's; not of L, n_poly, D, S, the flags, the pitches,
+ * the pointers' alignment or what else is in the call): the same inputs give the same bits on every call, and for a row
+ * or a segment computed alone.
+ *  d_x     [D][ld_x] float32
+ *  d_N     [D][S][K][K] float64, OVERWRITTEN
+ *  d_r     [D][S][K] float64, OVERWRITTEN
+ *  d_hits  [D][S] uint32, OVERWRITTEN, or NULL
+ * D < 1, T < 1, S < 1, L outside 1 .. 3, n_poly outside 0 .. 2, a pitch (of an array that is given) < T, or a null d_x,
+ * d_bound, d_nu, d_N or d_r -> MRX_ERR_INVALID with the outputs untouched */
+int mrx_tod_line_normal(mrx_ctx* ctx, const float* d_x, size_t ld_x, const float* d_model, size_t ld_m,
+                        const uint8_t* d_flags, size_t ld_f, int D, int T, const int32_t* d_bound, int S,
+                        const double* d_nu, int L, int n_poly, double* d_N, double* d_r, uint32_t* d_hits);
+
+/* Subtract (sign -1) or add (sign +1) each segment's lines, d_a [D][S][K] float64.  Only the carriers are applied: the
+ * baseline coefficients a[..][0 .. n_poly - 1] are nuisance parameters and are not read.
+ *   s = 0.0; for i = n_poly .. K - 1: s = s + a[d][seg][i] * B_i               (two roundings a step, in this order)
+ *   y[d][t] = x[d][t] + sign * (float)s                                        (one float32 operation)
+ * Samples in no segment are copied.  d_y == d_x with ld_y == ld_x works in place.
+ * D < 1, T < 1, S < 1, L outside 1 .. 3, n_poly outside 0 .. 2, sign not -1 or +1, ld_x or ld_y < T, a null d_x, d_bound,
+ * d_nu, d_a or d_y, or d_y == d_x with ld_y != ld_x -> MRX_ERR_INVALID with d_y untouched */
+int mrx_tod_line_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, const int32_t* d_bound, int S,
+                       const double* d_nu, int L, int n_poly, const double* d_a, int sign, float* d_y, size_t ld_y);
+
 /* ---- statistics per (row, segment) and the flagging of whole segments (maria_amd/cuts.py) ------------- */
 
 /* Common to the two entries below.  d_flags, d_model, their pitches, term(d, t), the single float64 roundings (no fused

@@ -244,6 +244,8 @@ SIGNATURES = {
     "mrx_tod_segment_normal": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "mrx_tod_segment_apply": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _i, _vp, _i, _vp, _sz]),
     "mrx_tod_segment_project": (_i, [_vp, _vp, _sz, _vp, _sz, _i, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    "mrx_tod_line_normal": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "mrx_tod_line_apply": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _sz]),
     "mrx_tod_segment_moments": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp, _i, _vp, _vp]),
     "mrx_tod_segment_flag": (_i, [_vp, _vp, _sz, _i, _i, _vp, _i, _vp, _i]),
     "mrx_tod_gram": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _vp, _i, _vp, _vp, _vp]),

@@ -1,5 +1,5 @@
 """The argument checks shared by the operators on a [D, T] TOD (flagging, downsample, ground, regress, jumps, subscans,
-time_constants, cuts, hwp, beamfit, covariance, sky_polynomial).  Every check raises ValueError and touches no device, so the operators
+time_constants, cuts, hwp, beamfit, covariance, sky_polynomial, lines).  Every check raises ValueError and touches no device, so the operators
 refuse on host tensors what they refuse on device tensors.  torch and ``_lib`` are imported inside the functions, and no
 operator module is imported at all: this module loads where no device and no library is."""
 

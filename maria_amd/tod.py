@@ -476,6 +476,118 @@ class TOD:
                   "unfixed": int((~ok).sum()), "flagged_fraction": float((jump_flags != 0).sum()) / jump_flags.numel()}
         return self._derived(data=data, flags=jump_flags, record={"jumps": record})
 
+    def remove_lines(self, lines=None, chunk=None, n_poly=2, n_sigma=6.0, nperseg=None, n_refine=2, per_detector=True, groups="band",
+                     model=None, into=None, min_hits=None, rcond=1e-10, ctx=None, device="cuda:0"):
+        """A new TOD with narrow spectral lines (pulse-tube lines and their harmonics, aliased mains, microphonic
+        resonances) found, tracked per detector and subtracted (maria_amd.lines).  The lines are those of
+        ``lines``, frequencies in Hz ([L], or [D, L] per detector), or with None the ones ``lines.find_lines`` reports
+        above ``n_sigma`` robust sigmas in the Welch spectrum (:meth:`psd`'s, ``nperseg`` samples a segment) of the signal
+        (the sum of the fields, less ``model``) of every group of detectors (``groups``: "band", None for one group, or an
+        integer array, -1: a detector left as it is).  In ascending frequency, three neighbours at a time (each set on the
+        signal the earlier sets are already gone from): every detector's frequencies are tracked by ``n_refine`` rounds of
+        the phase slope between consecutive chunks (``lines.refine``; ``per_detector`` False: one correction a group),
+        then each chunk of ``chunk`` seconds (None: ``nperseg`` samples) gets an amplitude and a phase per line beside
+        ``n_poly`` (0 .. 2) Legendre baseline terms, and the carriers alone are subtracted from the field ``into``
+        (default: the first; the mappers bin the sum).  With lines from the finder the chunks must not be longer than
+        ``nperseg`` samples: a frequency known to half a Welch bin must not slip half a cycle from one chunk to the next.
+        Samples with nonzero ``flags`` take no part in the fits, and are subtracted from like the rest.  A (detector,
+        chunk) pair with fewer than max(min_hits, K) samples left (``min_hits`` None: 4 K, K = n_poly + 2 lines of the
+        set), or whose basis is degenerate on them, is left as it is and counted.  Run it after ``flag_glitches`` and
+        ``fix_jumps`` (a spike or a step is broadband and leaks into every line) and before ``cut_uncorrelated``,
+        ``remove_ground`` and ``remove_common_mode`` (a line common to the array would otherwise enter their templates).
+        Every field of the result is a float32 device copy; ``flags``, ``dets``, ``coords``, ``units`` and the pW <-> K_RJ
+        calibrator are carried over; ``metadata["lines"]`` records the parameters, ``bounds``, the ``found`` and ``refined``
+        frequencies ([D, L] in Hz, strongest first, NaN where a detector's group has fewer lines), the per-chunk
+        ``amplitude`` and ``phase`` ([D, S, L]) and the ``unfitted`` count.  A TOD without lines comes back with every bit
+        of its fields.  This TOD is left as it is."""
+        import torch
+
+        from . import lines as mlines
+        from .cuts import chunk_bounds
+        from .noise_estimate import check_nperseg, default_nperseg, welch
+
+        n_poly = mlines._check_n_poly(n_poly)
+        if min_hits is not None:
+            min_hits = _tod_args.check_min_hits(min_hits)
+        if not 0.0 <= float(rcond) < 1.0:
+            raise ValueError(f"rcond {rcond}: in [0, 1)")
+        if isinstance(n_refine, bool) or int(n_refine) != n_refine or int(n_refine) < 0:
+            raise ValueError(f"n_refine {n_refine}: an integer >= 0")
+        if not (np.isfinite(float(n_sigma)) and float(n_sigma) > 0):
+            raise ValueError(f"n_sigma {n_sigma}: finite and > 0")
+        T = self._T
+        if T < 2:
+            raise ValueError("a TOD of fewer than two samples has no sample rate")
+        fs = float(self._sample_rate())
+        nperseg = default_nperseg(T) if nperseg is None else check_nperseg(nperseg, T)
+        if chunk is not None and not (np.isfinite(float(chunk)) and round(float(chunk) * fs) >= 1):
+            raise ValueError(f"chunk {chunk}: a finite number of seconds, at least one sample")
+        length = nperseg if chunk is None else int(round(float(chunk) * fs))
+        if lines is None and length > nperseg:
+            raise ValueError(f"chunks of {length} samples with lines from the finder: at most nperseg = {nperseg}")
+        group = self._groups(groups, np.int64)
+        data, signal, model, flags, into, ctx = self._device_fields(model, into, ctx, device)
+        D = int(signal.shape[0])
+        group = np.zeros(D, np.int64) if group is None else group
+        if group.shape != (D,):
+            raise ValueError(f"groups must be {D} integers, one per detector")
+        G = int(group.max()) + 1 if group.size and group.max() >= 0 else 0
+        if model is not None:
+            signal.sub_(model)
+        if lines is None:
+            f, p = welch(signal, fs, nperseg=nperseg, ctx=ctx)
+            found = mlines.find_lines(f.cpu().numpy(), p.cpu().numpy(), groups=group, n_sigma=n_sigma)
+            per_row = None
+        else:
+            hz = np.asarray(_tod_args.to_numpy(lines), np.float64)
+            if hz.ndim not in (1, 2) or hz.shape[-1] < 1 or (hz.ndim == 2 and hz.shape[0] != D) or not np.all(np.isfinite(hz)) \
+                    or not (np.all(hz > 0) and np.all(hz <= 0.5 * fs)):
+                raise ValueError(f"lines must be [L] or [{D}, L] frequencies in (0, {0.5 * fs}] Hz, L >= 1")
+            per_row = hz if hz.ndim == 2 else None
+            found = [hz.mean(axis=0) if hz.ndim == 2 else hz] * G
+        bounds = chunk_bounds(T, length)
+        S = bounds.size - 1
+        d_bounds = torch.as_tensor(bounds).to(signal.device)
+        Lmax = max([v.size for v in found] + [0])
+        rec_found, rec_refined = np.full((D, Lmax), np.nan), np.full((D, Lmax), np.nan)
+        amplitude, phase = np.full((D, S, Lmax), np.nan), np.full((D, S, Lmax), np.nan)
+        unfitted = 0
+        nonempty = torch.as_tensor(np.diff(bounds.astype(np.int64)) > 0).to(signal.device)
+        for k, freqs in enumerate(found):
+            rows = np.flatnonzero(group == k)
+            if rows.size == 0 or freqs.size == 0:
+                continue
+            whole = rows.size == D
+            d_rows = torch.as_tensor(rows).to(signal.device)
+            work = signal if whole else signal.index_select(0, d_rows)
+            target = data[into] if whole else data[into].index_select(0, d_rows)
+            fl = flags if flags is None or whole else flags.index_select(0, d_rows)
+            start = np.broadcast_to(freqs[None, :], (rows.size, freqs.size)) if per_row is None else per_row[rows]
+            rec_found[np.ix_(rows, np.arange(freqs.size))] = start
+            order = np.argsort(freqs)
+            for members in mlines.line_groups(freqs.size):
+                cols = order[list(members)]
+                K = n_poly + 2 * cols.size
+                mh = 4 * K if min_hits is None else min_hits
+                nu = mlines.refine(work, d_bounds, start[:, cols] / fs, n_iter=int(n_refine), per_detector=per_detector, n_poly=n_poly, flags=fl,
+                                   min_hits=mh, rcond=rcond, ctx=ctx)
+                a, ok = mlines.fit(work, d_bounds, nu, n_poly=n_poly, flags=fl, min_hits=mh, rcond=rcond, ctx=ctx)
+                mlines.apply(work, d_bounds, nu, a, n_poly, sign=-1, out=work, ctx=ctx)
+                mlines.apply(target, d_bounds, nu, a, n_poly, sign=-1, out=target, ctx=ctx)
+                amp, phi = mlines.amplitude_phase(a, n_poly)
+                rec_refined[np.ix_(rows, cols)] = nu * fs
+                amplitude[np.ix_(rows, np.arange(S), cols)] = amp.cpu().numpy()
+                phase[np.ix_(rows, np.arange(S), cols)] = phi.cpu().numpy()
+                unfitted += int((~ok & nonempty[None, :]).sum())
+            if not whole:
+                data[into].index_copy_(0, d_rows, target)
+        del signal
+        record = {"n_poly": n_poly, "n_sigma": float(n_sigma), "nperseg": nperseg, "chunk": None if chunk is None else float(chunk),
+                  "n_refine": int(n_refine), "per_detector": bool(per_detector), "min_hits": min_hits, "rcond": float(rcond), "into": into,
+                  "bounds": bounds, "lines": [np.array(v, np.float64) for v in found], "found": rec_found, "refined": rec_refined,
+                  "amplitude": amplitude, "phase": phase, "unfitted": unfitted}
+        return self._derived(data=data, record={"lines": record})
+
     def remove_ground(self, n_bins=64, bins=None, model=None, shared=False, min_hits=8, into=None, ctx=None, device="cuda:0"):
         """A new TOD with the scan-synchronous ground pickup removed (maria_amd.ground): per detector, the mean
         of the signal (the sum of the fields) in each of ``n_bins`` uniform bins of the boresight azimuth
