@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """One-off robustness run of the follow-on rows at the size of a config-5 detector shard
-(6250 detectors x 1.44 M samples = 9e9 samples, 36 GB per field): indices beyond 2^32."""
+(6250 detectors x 1.44 M samples = 9e9 samples, 36 GB per field): indices beyond 2^32.
+
+Superseded for the TOD entries by tests/test_gpu_wide_rows.py, which holds every pitched TOD entry on rows that
+start past 2^31 and 2^32 elements to its float64 reference, bit for bit against the contiguous call."""
 import ctypes as C
 import os
 import sys
