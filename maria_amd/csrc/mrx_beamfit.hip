@@ -13,18 +13,19 @@
 // tile a thread first reads its four flags of every row; a wave none of whose samples is kept in any row goes on to the
 // next tile (no pointing, no float64).  Otherwise, per row with a kept sample in the wave, it forms the sums of the lane's
 // kept samples with the sample's rotation G (SampleConst::G, made once per call for all rows by sample_const in a kernel of
-// its own: [T][6] float32 in d_work) (a flagged sample's value is never read), which the 64 lanes add in a butterfly
-// (xor 32 .. 1); lane 0 then adds them to the wave's own LDS slot of the row.  At the chunk's end the four waves' slots
+// its own: [T][6] float32 in d_work) (a flagged sample's value is never read), which the 64 lanes add in
+// wave_sum_all (mrx_tod_dev.h); lane 0 then adds them to the wave's own LDS slot of the row.  At the chunk's end the four waves' slots
 // are added in wave order and stored to d_work[row][chunk]; a second kernel adds a row's chunks in ascending order.  A
 // skipped wave or row would have added +0.0 to every sum: the order is a function of (D, T) alone, there are no atomics,
 // and the same inputs give the same bits on every call.
 #include "mrx_map_pointing.h"
+#include "mrx_tod_dev.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int kWave = 64;
+using mrx_tod::kWave;
 constexpr int kWaves = kBlock / kWave;
 constexpr int kChunkTiles = 16;  // 16384 samples a chunk: 15 chunks a row at T = 240 000, 44 MB of partial sums at D = 10 000, K = 7
 
@@ -284,12 +285,7 @@ __global__ __launch_bounds__(kBlock) void beam_normal_kernel(MapArgs g, BeamArgs
           n += 1u;
         }
       }
-#pragma unroll
-      for (int o = kWave / 2; o >= 1; o >>= 1) {  // every lane ends with the same sums: a + b is b + a
-#pragma unroll
-        for (int j = 0; j < kNs; ++j) s[j] = s[j] + __shfl_xor(s[j], o, kWave);
-        n += __shfl_xor(n, o, kWave);
-      }
+      mrx_tod::wave_sum_all(s, n);
       if (lane == 0) {  // (a select per lane and sum would hold 37 lane masks in scalar registers across the loops)
         double* const mine = part[dl][wave];
 #pragma unroll
@@ -372,7 +368,7 @@ int mrx_tod_source_flag(mrx_ctx* ctx, const float* d_az, const float* d_el, int 
   if (ctx->options[MRX_OPT_POINTING_CHAIN])
     return mrx_fail(ctx, MRX_ERR_UNSUPPORTED, "%s: composed pointing only (MRX_OPT_POINTING_CHAIN is set)", __func__);
   const MapArgs g = frame_args(center_phi, center_theta, d_az, d_el, T, d_transform, d_dx, d_dy, D);
-  const int wide = (((uintptr_t)d_flags | (uintptr_t)ld_f) & 3u) == 0;
+  const int wide = mrx_aligned(d_flags, ld_f, 4);
   hipLaunchKernelGGL(source_flag_kernel, dim3(mrx_ceil_div(T, kTileSamples), mrx_ceil_div(D, kTileDet)), dim3(kBlock), 0, ctx->stream, g, d_src,
                      radius * radius, inside, (unsigned)value, d_flags, ld_f, wide);
   MRX_CHECK_LAUNCH(ctx);
@@ -400,7 +396,7 @@ int mrx_tod_beam_normal(mrx_ctx* ctx, const float* d_x, size_t ld_x, const float
               "the centre must be finite");
   MRX_REQUIRE(ctx, mrx_ceil_div(D, kTileDet) <= 65535, "D too large for one launch");
   MRX_REQUIRE(ctx, T <= 0x7fffffff - 2 * kTileSamples, "T too large: sample indices are 32-bit");
-  MRX_REQUIRE(ctx, ((uintptr_t)d_work & 7u) == 0, "d_work must be 8-byte aligned");
+  MRX_REQUIRE(ctx, mrx_aligned(d_work, 0, 8), "d_work must be 8-byte aligned");
   size_t need = 0;
   (void)mrx_tod_beam_normal_work_bytes(D, T, K, &need);
   MRX_REQUIRE(ctx, work_bytes >= need, "work buffer smaller than mrx_tod_beam_normal_work_bytes");
@@ -416,7 +412,7 @@ int mrx_tod_beam_normal(mrx_ctx* ctx, const float* d_x, size_t ld_x, const float
   hipLaunchKernelGGL(beam_rotation_kernel, dim3(mrx_ceil_div(T, kBlock)), dim3(kBlock), 0, ctx->stream, g, rot);
   MRX_CHECK_LAUNCH(ctx);
   const int n_chunks = n_chunks_of(T);
-  const BeamArgs a{d_x, ld_x, d_model, ld_m, d_flags, ld_f, d_flags && (((uintptr_t)d_flags | (uintptr_t)ld_f) & 3u) == 0,
+  const BeamArgs a{d_x, ld_x, d_model, ld_m, d_flags, ld_f, d_flags && mrx_aligned(d_flags, ld_f, 4),
                    d_src, rot, d_param, work, n_chunks};
   const dim3 grid(n_chunks, mrx_ceil_div(D, kTileDet));
   if (K == 5 && d_model)

@@ -205,24 +205,6 @@ __global__ __launch_bounds__(kThreads) void gap_fill_kernel(float* __restrict__ 
   }
 }
 
-struct Grid {
-  int tiles_per_row;
-  long long n_tiles;
-  unsigned blocks;
-};
-
-// workgroups stride over the tiles: as many as stay resident (8 a CU), neighbours in the grid neighbouring tiles of a row
-Grid tile_grid(const mrx_ctx* ctx, int D, int T) {
-  Grid g;
-  g.tiles_per_row = (T + kTileSamples - 1) / kTileSamples;
-  g.n_tiles = (long long)D * g.tiles_per_row;
-  g.blocks = mrx_resident_blocks(ctx, g.n_tiles);
-  return g;
-}
-
-// may a row's flags be moved as 4-byte words?
-int word_aligned(const void* p, size_t ld) { return (((uintptr_t)p | (uintptr_t)ld) & 3u) == 0 ? 1 : 0; }
-
 }  // namespace
 
 extern "C" {
@@ -235,7 +217,7 @@ int mrx_tod_median_residual(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, 
   MRX_REQUIRE(ctx, ld_x >= (size_t)T && ld_r >= (size_t)T, "ld_x or ld_r smaller than T");
   MRX_REQUIRE(ctx, half_window >= 1 && half_window <= kMaxHalf, "half_window must be in 1 .. 15");
   MRX_REQUIRE(ctx, (const void*)d_r != (const void*)d_x, "d_r must not be d_x");
-  const Grid g = tile_grid(ctx, D, T);
+  const mrx_tile_grid_t g = mrx_tile_grid(ctx, D, T, kTileSamples);
   hipLaunchKernelGGL(median_residual_kernel, dim3(g.blocks), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, half_window, d_r, ld_r,
                      g.tiles_per_row, g.n_tiles);
   MRX_CHECK_LAUNCH(ctx);
@@ -253,9 +235,9 @@ int mrx_tod_glitch_flag(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int 
   MRX_REQUIRE(ctx, grow_before >= 0 && grow_before <= kMaxGrow && grow_after >= 0 && grow_after <= kMaxGrow,
               "grow_before and grow_after must be in 0 .. 64");
   if (d_count) MRX_HIP(ctx, hipMemsetAsync(d_count, 0, (size_t)D * sizeof(uint32_t), ctx->stream));
-  const Grid g = tile_grid(ctx, D, T);
+  const mrx_tile_grid_t g = mrx_tile_grid(ctx, D, T, kTileSamples);
   hipLaunchKernelGGL(glitch_flag_kernel, dim3(g.blocks), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, half_window, d_thresh,
-                     grow_before, grow_after, d_flags, ld_f, word_aligned(d_flags, ld_f), d_count, g.tiles_per_row, g.n_tiles);
+                     grow_before, grow_after, d_flags, ld_f, (int)mrx_aligned(d_flags, ld_f, 4), d_count, g.tiles_per_row, g.n_tiles);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;
 }
@@ -269,9 +251,9 @@ int mrx_tod_gap_fill(mrx_ctx* ctx, float* d_x, size_t ld_x, int D, int T, const 
   MRX_REQUIRE(ctx, ld_x >= (size_t)T && ld_f >= (size_t)T, "ld_x or ld_f smaller than T");
   MRX_REQUIRE(ctx, n_fit >= 1 && n_fit <= kMaxFit, "n_fit must be in 1 .. 16");
   if (d_filled) MRX_HIP(ctx, hipMemsetAsync(d_filled, 0, (size_t)D * sizeof(uint32_t), ctx->stream));
-  const Grid g = tile_grid(ctx, D, T);
+  const mrx_tile_grid_t g = mrx_tile_grid(ctx, D, T, kTileSamples);
   hipLaunchKernelGGL(gap_fill_kernel, dim3(g.blocks), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, d_flags, ld_f,
-                     word_aligned(d_flags, ld_f), n_fit, d_filled, g.tiles_per_row, g.n_tiles);
+                     (int)mrx_aligned(d_flags, ld_f, 4), n_fit, d_filled, g.tiles_per_row, g.n_tiles);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;
 }

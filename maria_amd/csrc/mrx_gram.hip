@@ -62,6 +62,7 @@ __device__ __forceinline__ f32x16 mfma_32x32x2(float a, float b, f32x16 c) {
 // may the thread's four samples q .. q + 3 be one access?
 __device__ __forceinline__ bool whole(long long q, int T, int wide, int bit) { return (wide & bit) && q + kOwn <= T; }
 
+// (not mrx_tod_dev.h's load_own, which gives a sample past T the default 0: see above)
 __device__ __forceinline__ void load4(const float* row, long long q, int T, bool one, float (&v)[kOwn]) {
   if (one) {
     const float4 w = *reinterpret_cast<const float4*>(row + q);
@@ -266,8 +267,6 @@ __global__ __launch_bounds__(kThreads) void gram_count_fill_kernel(int D, int T,
   }
 }
 
-bool aligned(const void* p, size_t ld_bytes, unsigned to) { return (((uintptr_t)p | (uintptr_t)ld_bytes) & (to - 1u)) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -279,8 +278,8 @@ int mrx_tod_gram(mrx_ctx* ctx, const float* d_x, size_t ld_x, const float* d_mod
   MRX_REQUIRE(ctx, d_x && d_G, "null pointer");
   MRX_REQUIRE(ctx, D >= 1 && T >= 1 && R >= 1, "need D >= 1 rows of T >= 1 samples and R >= 1 rows in the list");
   MRX_REQUIRE(ctx, ld_x >= (size_t)T && (!d_model || ld_m >= (size_t)T) && (!d_flags || ld_f >= (size_t)T), "ld_x, ld_m or ld_f smaller than T");
-  const int wide = (aligned(d_x, ld_x * 4, 16) ? kWideX : 0) | (d_model && aligned(d_model, ld_m * 4, 16) ? kWideM : 0) |
-                   (d_flags && aligned(d_flags, ld_f, 4) ? kWideF : 0);
+  const int wide = (mrx_aligned(d_x, ld_x * 4, 16) ? kWideX : 0) | (d_model && mrx_aligned(d_model, ld_m * 4, 16) ? kWideM : 0) |
+                   (d_flags && mrx_aligned(d_flags, ld_f, 4) ? kWideF : 0);
   const unsigned nb = (unsigned)(((long long)R + kTile - 1) / kTile);
   hipLaunchKernelGGL(gram_kernel<false>, dim3(nb, nb), dim3(kThreads), 0, ctx->stream, d_x, ld_x, d_model, ld_m, d_flags, ld_f, D, T, d_rows, R,
                      d_center, d_G, wide);

@@ -8,8 +8,8 @@
 //
 // Reduction.  One wave takes one (row, bin); the four waves of a workgroup take four neighbouring bins of one row, so
 // that the short runs of consecutive samples neighbouring bins own meet in the same cache lines.  Lane l adds the list
-// entries l, l + 64, .. of its bin, in that order, into a float64 accumulator of its own; the 64 accumulators meet in a
-// butterfly of fixed shape (xor 32, 16, .. 1).  The order of every addition is a function of the bin's list alone: the
+// entries l, l + 64, .. of its bin, in that order, into a float64 accumulator of its own; the 64 accumulators meet in
+// wave_sum_all (mrx_tod_dev.h).  The order of every addition is a function of the bin's list alone: the
 // result is the same on every call and does not depend on the other rows of the launch.  No atomics.
 // A list entry outside [0, T) is skipped by an unsigned comparison before any address is formed from it, and the list
 // bounds read from d_start are clamped into [0, n_order]: bad lists give wrong sums, never a read outside the arrays.
@@ -21,20 +21,16 @@
 // template row (<= 16 KB) is read through the cache; the bin varies slowly along a scan.  A bin outside [0, K) is found
 // by an unsigned comparison and no template entry is read for it.
 #include "mrx_internal.h"
+#include "mrx_tod_dev.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
-constexpr int kWaves = kThreads / kWave;  // neighbouring bins of one row a workgroup reduces
-constexpr int kUnroll = 4;                // list entries a lane has in flight
-constexpr int kMaxBins = 4096;            // maria_amd.ground.MAX_BINS
-constexpr int kTileSamples = 1024;
-constexpr int kOwn = kTileSamples / kThreads;
+using namespace mrx_tod;  // the 256-thread, four-sample tile, kWave; kWaves neighbouring bins of one row a workgroup reduces
 
-static_assert(kOwn == 4, "a thread of the application moves one 16-byte word");
+constexpr int kUnroll = 4;      // list entries a lane has in flight
+constexpr int kMaxBins = 4096;  // maria_amd.ground.MAX_BINS
 
 __global__ __launch_bounds__(kThreads) void bin_reduce_kernel(const float* __restrict__ x, size_t ld_x, const float* __restrict__ model,
                                                               size_t ld_m, const unsigned char* __restrict__ flags, size_t ld_f, int T,
@@ -80,11 +76,7 @@ __global__ __launch_bounds__(kThreads) void bin_reduce_kernel(const float* __res
         }
       }
     }
-#pragma unroll
-    for (int off = kWave / 2; off >= 1; off >>= 1) {  // every lane ends with the same sum: a + b is b + a
-      acc += __shfl_xor(acc, off, kWave);
-      n += __shfl_xor(n, off, kWave);
-    }
+    wave_sum_all(acc, n);
     if (lane == 0) {
       const size_t o = (size_t)row * K + k;
       if (sum) sum[o] = acc;
@@ -169,11 +161,10 @@ int mrx_tod_bin_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T,
   MRX_REQUIRE(ctx, K >= 1 && K <= kMaxBins, "K must be in 1 .. 4096");
   MRX_REQUIRE(ctx, sign == 1 || sign == -1, "sign must be -1 or +1");
   MRX_REQUIRE(ctx, ld_x >= (size_t)T && ld_y >= (size_t)T, "ld_x or ld_y smaller than T");
-  const int tiles_per_row = (T + kTileSamples - 1) / kTileSamples;
-  const long long n_tiles = (long long)D * tiles_per_row;
-  const int wide = mrx_aligned16(d_x, ld_x * sizeof(float)) && mrx_aligned16(d_y, ld_y * sizeof(float)) && mrx_aligned16(d_bin, 0) ? 1 : 0;
-  hipLaunchKernelGGL(bin_apply_kernel, dim3(mrx_resident_blocks(ctx, n_tiles)), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, d_bin, d_template,
-                     K, sign, d_y, ld_y, wide, tiles_per_row, n_tiles);
+  const mrx_tile_grid_t g = mrx_tile_grid(ctx, D, T, kTileSamples);
+  const int wide = mrx_aligned(d_x, ld_x * 4, 16) && mrx_aligned(d_y, ld_y * 4, 16) && mrx_aligned(d_bin, 0, 16) ? 1 : 0;
+  hipLaunchKernelGGL(bin_apply_kernel, dim3(g.blocks), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, d_bin, d_template, K, sign, d_y, ld_y, wide,
+                     g.tiles_per_row, g.n_tiles);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;
 }

@@ -19,9 +19,9 @@
 // sums + 20 q P bytes: 47.3 KB at q = 8 with 523 taps (3 workgroups a CU), 119.5 KB at the worst shape (1 a CU).
 //
 // mrx_tod_hwp_modulate: out = float32( i + c cos 4 chi + s sin 4 chi ) as fma(s, sin, fma(c, cos, i)) in float64, one
-// rounding to float32; a streaming pass, a thread four consecutive samples (one 16-byte access where pointer and pitch
-// allow, four otherwise), in place where d_out == d_i.
+// rounding to float32; a streaming pass, a thread its own four samples (mrx_tod_dev.h), in place where d_out == d_i.
 #include "mrx_internal.h"
+#include "mrx_tod_dev.h"
 
 #include <algorithm>
 
@@ -145,21 +145,14 @@ __global__ __launch_bounds__(kThreads) void tod_demodulate_kernel(const float* _
   }
 }
 
-constexpr int kModThreads = 256;
-constexpr int kOwn = 4;  // consecutive samples of a thread
-constexpr int kModTile = kModThreads * kOwn;
+// the modulation's tile is mrx_tod_dev.h's.  This file is built WITH contraction: it takes the loads and stores only
+constexpr int kModThreads = mrx_tod::kThreads;
+constexpr int kOwn = mrx_tod::kOwn;
+constexpr int kModTile = mrx_tod::kTileSamples;
+using mrx_tod::load_own;
+using mrx_tod::store_own;
 
 enum : int { kWideI = 1, kWideC = 2, kWideS = 4, kWideOut = 8, kWideCarrier = 16 };
-
-__device__ __forceinline__ void load4(const float* row, int t, int T, bool wide, float (&v)[kOwn]) {
-  if (wide && t + kOwn <= T) {
-    const float4 w = *reinterpret_cast<const float4*>(row + t);
-    v[0] = w.x, v[1] = w.y, v[2] = w.z, v[3] = w.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < kOwn; ++k) v[k] = t + k < T ? row[t + k] : 0.0f;
-  }
-}
 
 // out and vi may be the same buffer: a thread reads its samples before it writes them, and no other thread touches them
 __global__ __launch_bounds__(kModThreads) void tod_hwp_modulate_kernel(const float* vi, const float* __restrict__ vc,
@@ -171,9 +164,9 @@ __global__ __launch_bounds__(kModThreads) void tod_hwp_modulate_kernel(const flo
     const int t = (int)(tile - row * tiles_per_row) * kModTile + kOwn * (int)threadIdx.x;
     if (t >= T) continue;
     float a[kOwn], b[kOwn], c[kOwn];
-    load4(vi + (size_t)row * ld_in, t, T, wide & kWideI, a);
-    load4(vc + (size_t)row * ld_in, t, T, wide & kWideC, b);
-    load4(vs + (size_t)row * ld_in, t, T, wide & kWideS, c);
+    load_own<kOwn>(vi + (size_t)row * ld_in, t, T, wide & kWideI, a);
+    load_own<kOwn>(vc + (size_t)row * ld_in, t, T, wide & kWideC, b);
+    load_own<kOwn>(vs + (size_t)row * ld_in, t, T, wide & kWideS, c);
     double cs[2 * kOwn];
     if ((wide & kWideCarrier) && t + kOwn <= T) {
 #pragma unroll
@@ -188,14 +181,7 @@ __global__ __launch_bounds__(kModThreads) void tod_hwp_modulate_kernel(const flo
     float r[kOwn];
 #pragma unroll
     for (int k = 0; k < kOwn; ++k) r[k] = (float)fma((double)c[k], cs[2 * k + 1], fma((double)b[k], cs[2 * k], (double)a[k]));
-    float* const yr = out + (size_t)row * ld_out;
-    if ((wide & kWideOut) && t + kOwn <= T) {
-      *reinterpret_cast<float4*>(yr + t) = make_float4(r[0], r[1], r[2], r[3]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < kOwn; ++k)
-        if (t + k < T) yr[t + k] = r[k];
-    }
+    store_own<kOwn>(out + (size_t)row * ld_out, t, T, wide & kWideOut, r);
   }
 }
 
@@ -247,13 +233,12 @@ int mrx_tod_hwp_modulate(mrx_ctx* ctx, const float* d_i, const float* d_c, const
   MRX_REQUIRE(ctx, ld_in >= (size_t)T && ld_out >= (size_t)T, "ld_in or ld_out smaller than T");
   MRX_REQUIRE(ctx, (const void*)d_out != (const void*)d_c && (const void*)d_out != (const void*)d_s, "d_out must not be d_c or d_s");
   MRX_REQUIRE(ctx, d_out != d_i || ld_out == ld_in, "in place (d_out == d_i) needs ld_out == ld_in");
-  const int wide = (mrx_aligned16(d_i, ld_in * 4) ? kWideI : 0) | (mrx_aligned16(d_c, ld_in * 4) ? kWideC : 0) | (mrx_aligned16(d_s, ld_in * 4) ? kWideS : 0) |
-                   (mrx_aligned16(d_out, ld_out * 4) ? kWideOut : 0) | (mrx_aligned16(d_carrier, 0) ? kWideCarrier : 0);
-  const int tiles_per_row = (T + kModTile - 1) / kModTile;
-  const long long n_tiles = (long long)D * tiles_per_row;
-  const unsigned blocks = mrx_resident_blocks(ctx, n_tiles);
-  hipLaunchKernelGGL(tod_hwp_modulate_kernel, dim3(blocks), dim3(kModThreads), 0, ctx->stream, d_i, d_c, d_s, ld_in, T, d_carrier, d_out, ld_out,
-                     wide, tiles_per_row, n_tiles);
+  const int wide = (mrx_aligned(d_i, ld_in * 4, 16) ? kWideI : 0) | (mrx_aligned(d_c, ld_in * 4, 16) ? kWideC : 0) |
+                   (mrx_aligned(d_s, ld_in * 4, 16) ? kWideS : 0) | (mrx_aligned(d_out, ld_out * 4, 16) ? kWideOut : 0) |
+                   (mrx_aligned(d_carrier, 0, 16) ? kWideCarrier : 0);
+  const mrx_tile_grid_t g = mrx_tile_grid(ctx, D, T, kModTile);
+  hipLaunchKernelGGL(tod_hwp_modulate_kernel, dim3(g.blocks), dim3(kModThreads), 0, ctx->stream, d_i, d_c, d_s, ld_in, T, d_carrier, d_out, ld_out,
+                     wide, g.tiles_per_row, g.n_tiles);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;
 }

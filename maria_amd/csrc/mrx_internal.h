@@ -230,7 +230,22 @@ static inline unsigned mrx_resident_blocks(const mrx_ctx* ctx, long long items, 
   return (unsigned)std::min(items, (long long)std::max(1, ctx->n_cu) * per_cu);
 }
 
-// may rows that start at `p`, `ld_bytes` BYTES apart (0: a single row), be moved in 16-byte pieces?
-static inline bool mrx_aligned16(const void* p, size_t ld_bytes) {
-  return (((uintptr_t)p | (uintptr_t)ld_bytes) & 15u) == 0;
+// may rows that start at `p`, `ld_bytes` BYTES apart (0: a single row), be moved in pieces of `to` bytes (a power of two)?
+static inline bool mrx_aligned(const void* p, size_t ld_bytes, unsigned to) {
+  return (((uintptr_t)p | (uintptr_t)ld_bytes) & (uintptr_t)(to - 1u)) == 0;
+}
+
+// the resident grid of a kernel whose workgroups stride over the tiles of `tile_samples` samples of D rows of T: neighbours
+// in the grid take neighbouring tiles of a row
+struct mrx_tile_grid_t {
+  int tiles_per_row;
+  long long n_tiles;
+  unsigned blocks;
+};
+static inline mrx_tile_grid_t mrx_tile_grid(const mrx_ctx* ctx, int D, int T, int tile_samples, int per_cu = 8) {
+  mrx_tile_grid_t g;
+  g.tiles_per_row = (int)(((long long)T + tile_samples - 1) / tile_samples);
+  g.n_tiles = (long long)D * g.tiles_per_row;
+  g.blocks = mrx_resident_blocks(ctx, g.n_tiles, per_cu);
+  return g;
 }

@@ -22,18 +22,17 @@
 // place of 2 sep reads a sample.  The peaks are kept as a bit mask in LDS and grown as mrx_glitch.hip grows detections.
 //
 // Height: one wave a row walks the row's jumps; the lanes stride over a window and the wave adds their float64 partial
-// sums up in a butterfly, an order that depends on the list alone.  Fix: a thread owns four consecutive samples, finds
+// sums up (mrx_tod_dev.h: wave_sum_all), an order that depends on the list alone.  Fix: a thread owns four consecutive samples, finds
 // the number of jumps at or before its first by bisection of the row's list and walks on from there.
 #include "mrx_internal.h"
+#include "mrx_tod_dev.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int kTileSamples = 1024;  // maria_amd.jumps.TILE_SAMPLES
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kOwn = kTileSamples / kThreads;  // consecutive samples a thread stores
+using namespace mrx_tod;  // the 256-thread, four-sample tile (kTileSamples is maria_amd.jumps.TILE_SAMPLES), kWave
+
 constexpr int kMaxWindow = 256;                // maria_amd.jumps.MAX_WINDOW
 constexpr int kMaxGap = 64;                    // maria_amd.jumps.MAX_GAP
 constexpr int kMaxSep = 512;                   // maria_amd.jumps.MAX_SEP
@@ -50,7 +49,7 @@ constexpr int kMaxDet = kTileSamples + 2 * kMaxGrow;                            
 constexpr int kDetRounds = (kMaxDet + kThreads - 1) / kThreads;                 // positions a thread tests
 constexpr int kDetWords = kDetRounds * kThreads / 64;
 
-static_assert(kOwn == 4, "a thread stores four consecutive samples");
+static_assert(kTileSamples == 1024, "maria_amd.jumps.TILE_SAMPLES");
 static_assert(kTileSamples <= kStatStage, "the statistic's results reuse the staging array");
 static_assert((kTileSamples - 1) / 64 + 2 < kDetWords, "any_bit reads three words from a sample's own");
 
@@ -273,8 +272,7 @@ __device__ __forceinline__ void wave_window(const float* __restrict__ xr, const 
   for (int u = a + (int)(threadIdx.x & 63); u < b; u += 64) {
     if (!fr || fr[u] == 0) acc += (double)xr[u], ++cnt;
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d), cnt += __shfl_xor(cnt, d);
+  wave_sum_all(acc, cnt);
   *sum = acc, *n = cnt;
 }
 
@@ -320,50 +318,15 @@ __global__ __launch_bounds__(kThreads) void jump_fix_kernel(const float* x, size
       if (pos[js + mid] <= t0) a = mid + 1; else b = mid;
     }
     int k = a;
-    const float* const xr = x + (size_t)row * ld_x + t0;
-    float* const yr = y + (size_t)row * ld_y + t0;
-    const bool whole = wide && t0 + kOwn <= T;
     float v[kOwn];
-    if (whole) {
-      const float4 q = *reinterpret_cast<const float4*>(xr);
-      v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-    } else {
-#pragma unroll
-      for (int u = 0; u < kOwn; ++u) v[u] = t0 + u < T ? xr[u] : 0.0f;
-    }
+    load_own<kOwn>(x + (size_t)row * ld_x, t0, T, wide, v);
 #pragma unroll
     for (int u = 0; u < kOwn; ++u) {
       while (js + k < je && pos[js + k] <= t0 + u) ++k;
       if (k > 0) v[u] = (float)((double)v[u] - cum[js + k - 1]);
     }
-    if (whole) {
-      *reinterpret_cast<float4*>(yr) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-      for (int u = 0; u < kOwn; ++u)
-        if (t0 + u < T) yr[u] = v[u];
-    }
+    store_own<kOwn>(y + (size_t)row * ld_y, t0, T, wide, v);
   }
-}
-
-struct Grid {
-  int tiles_per_row;
-  long long n_tiles;
-  unsigned blocks;
-};
-
-// workgroups stride over the tiles: as many as stay resident, neighbours in the grid neighbouring tiles of a row
-Grid tile_grid(const mrx_ctx* ctx, int D, int T, int per_cu) {
-  Grid g;
-  g.tiles_per_row = (T + kTileSamples - 1) / kTileSamples;
-  g.n_tiles = (long long)D * g.tiles_per_row;
-  g.blocks = mrx_resident_blocks(ctx, g.n_tiles, per_cu);
-  return g;
-}
-
-// may the rows be moved in pieces of `bytes` bytes?  (pitch in elements of `elem` bytes)
-int aligned_rows(const void* p, size_t ld, size_t elem, unsigned bytes) {
-  return (((uintptr_t)p | (uintptr_t)(ld * elem)) & (bytes - 1u)) == 0 ? 1 : 0;
 }
 
 const char* bad_window(int window, int gap, int min_count) {
@@ -387,10 +350,10 @@ int mrx_tod_step_stat(mrx_ctx* ctx, const float* d_x, size_t ld_x, const uint8_t
   const char* const bad = bad_window(window, gap, min_count);
   MRX_REQUIRE(ctx, !bad, bad);
   MRX_REQUIRE(ctx, (const void*)d_s != (const void*)d_x, "d_s must not be d_x");
-  const Grid g = tile_grid(ctx, D, T, 5);
+  const mrx_tile_grid_t g = mrx_tile_grid(ctx, D, T, kTileSamples, 5);
   hipLaunchKernelGGL(step_stat_kernel, dim3(g.blocks), dim3(kThreads), 0, ctx->stream, d_x, ld_x, d_flags, ld_f, T, window, gap, min_count,
-                     d_s, ld_s, aligned_rows(d_x, ld_x, 4, 16), d_flags ? aligned_rows(d_flags, ld_f, 1, 4) : 0,
-                     aligned_rows(d_s, ld_s, 4, 16), g.tiles_per_row, g.n_tiles);
+                     d_s, ld_s, (int)mrx_aligned(d_x, ld_x * 4, 16), (int)(d_flags && mrx_aligned(d_flags, ld_f, 4)),
+                     (int)mrx_aligned(d_s, ld_s * 4, 16), g.tiles_per_row, g.n_tiles);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;
 }
@@ -406,9 +369,10 @@ int mrx_tod_jump_find(mrx_ctx* ctx, const float* d_s, size_t ld_s, int D, int T,
   MRX_REQUIRE(ctx, grow_before >= 0 && grow_before <= kMaxGrow && grow_after >= 0 && grow_after <= kMaxGrow,
               "grow_before and grow_after must be in 0 .. 64");
   if (d_count) MRX_HIP(ctx, hipMemsetAsync(d_count, 0, (size_t)D * sizeof(uint32_t), ctx->stream));
-  const Grid g = tile_grid(ctx, D, T, 8);
+  const mrx_tile_grid_t g = mrx_tile_grid(ctx, D, T, kTileSamples);
   hipLaunchKernelGGL(jump_find_kernel, dim3(g.blocks), dim3(kThreads), 0, ctx->stream, d_s, ld_s, T, d_thresh, sep, grow_before, grow_after,
-                     d_flags, ld_f, aligned_rows(d_s, ld_s, 4, 16), aligned_rows(d_flags, ld_f, 1, 4), d_count, g.tiles_per_row, g.n_tiles);
+                     d_flags, ld_f, (int)mrx_aligned(d_s, ld_s * 4, 16), (int)mrx_aligned(d_flags, ld_f, 4), d_count, g.tiles_per_row,
+                     g.n_tiles);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;
 }
@@ -442,9 +406,9 @@ int mrx_tod_jump_fix(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, 
   MRX_REQUIRE(ctx, n == 0 || (d_pos && d_cum), "null pointer");
   MRX_REQUIRE(ctx, ld_x >= (size_t)T && ld_y >= (size_t)T, "ld_x or ld_y smaller than T");
   MRX_REQUIRE(ctx, (const void*)d_y != (const void*)d_x || ld_y == ld_x, "in place (d_y == d_x) needs ld_y == ld_x");
-  const Grid g = tile_grid(ctx, D, T, 8);
+  const mrx_tile_grid_t g = mrx_tile_grid(ctx, D, T, kTileSamples);
   hipLaunchKernelGGL(jump_fix_kernel, dim3(g.blocks), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, d_row_start, d_pos, d_cum, n, d_y, ld_y,
-                     aligned_rows(d_x, ld_x, 4, 16) & aligned_rows(d_y, ld_y, 4, 16), g.tiles_per_row, g.n_tiles);
+                     (int)(mrx_aligned(d_x, ld_x * 4, 16) && mrx_aligned(d_y, ld_y * 4, 16)), g.tiles_per_row, g.n_tiles);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;
 }

@@ -14,31 +14,26 @@
 //
 // mrx_tod_line_normal.  mrx_tod_segment_normal's shape: one wave takes one (row, segment) and owns all of its sums; lane o
 // adds the samples lo + o, lo + o + 64, .. in ascending order into K (K + 1) / 2 + K float64 accumulators in registers,
-// then the 64 lanes meet in a butterfly (xor 32 .. 1); lane i K + j stores N[i][j], lane i stores r[i].  The order is a
-// function of lo and hi alone.  A flagged sample enters as a row of zeros (selected, never multiplied).  The four waves
-// of a workgroup take four consecutive (row, segment) pairs and share nothing.  Compiled for every (n_poly, L).
+// then the 64 lanes meet and store (mrx_tod_dev.h: rhs_add, wave_sum_all, store_normal_by_lane).  The order is a function of lo and hi alone.  A flagged sample enters as a row of zeros (selected, never
+// multiplied).  The four waves of a workgroup take four consecutive (row, segment) pairs and share nothing.  Compiled
+// for every (n_poly, L).
 //
-// mrx_tod_line_apply.  mrx_tod_segment_apply's streaming pass over (row, tile of 1024 samples), thread o the four samples
-// 4 o .. 4 o + 3, the segment of a sample found by bisection over the clamped bounds: every index is inside the arrays
-// whatever d_bound holds.
+// mrx_tod_line_apply.  mrx_tod_segment_apply's streaming pass over (row, tile), a thread its own four samples, the
+// segment of a sample by find_segment (mrx_tod_dev.h).
 #include "mrx_internal.h"
+#include "mrx_tod_dev.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
-constexpr int kWaves = kThreads / kWave;
-constexpr int kOwn = 4;  // consecutive samples of a thread of the application
-constexpr int kTileSamples = kThreads * kOwn;
+using namespace mrx_tod;  // the 256-thread, four-sample tile, kWave
+
 constexpr int kMaxLines = 3;
 constexpr int kMaxPoly = 2;
 constexpr int kFlight = 2;  // samples of a lane whose loads go out together
 
 enum : int { kWideX = 1, kWideY = 2 };
-
-__device__ __forceinline__ int clamp_bound(int b, int T) { return min(max(b, 0), T); }
 
 // the two carriers of a line of nu cycles a sample at sample t of the row
 __device__ __forceinline__ void carrier(double nu, int t, double& c, double& s) {
@@ -99,55 +94,20 @@ __global__ __launch_bounds__(kThreads) void line_normal_kernel(const float* __re
         for (int i = 0; i < K; ++i) b[i] = keep ? B[i] : 0.0;
         const double term = keep ? (mr ? (double)xv[e] - (double)mv[e] : (double)xv[e]) : 0.0;
         cnt += keep ? 1u : 0u;
+        // (written out, on a row selected here: mrx_tod_dev.h says why)
         int a = 0;
 #pragma unroll
         for (int i = 0; i < K; ++i) {
 #pragma unroll
           for (int j = i; j < K; ++j, ++a) acc[a] = acc[a] + b[i] * b[j];
         }
-#pragma unroll
-        for (int i = 0; i < K; ++i) acc[NP + i] = acc[NP + i] + b[i] * term;
+        rhs_add<K>(acc + NP, B, keep, term);
       }
     }
-#pragma unroll
-    for (int o = kWave / 2; o >= 1; o >>= 1) {  // every lane ends with the same sums: a + b is b + a
-#pragma unroll
-      for (int a = 0; a < NA; ++a) acc[a] = acc[a] + __shfl_xor(acc[a], o, kWave);
-      cnt += __shfl_xor(cnt, o, kWave);
-    }
-    // lane i K + j picks N[i][j] and lane i picks r[i] by selects: the accumulators are never indexed by a lane's number
-    int me = lane;
-    asm volatile("" : "+v"(me));
-    double vN = 0.0, vr = 0.0;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-#pragma unroll
-      for (int j = 0; j < K; ++j) {
-        const int p = i < j ? i : j, q = i < j ? j : i;
-        vN = me == i * K + j ? acc[p * K - p * (p - 1) / 2 + (q - p)] : vN;
-      }
-      vr = me == i ? acc[NP + i] : vr;
-    }
-    if (lane < K * K) N[(size_t)item * (K * K) + lane] = vN;
-    if (lane < K) r[(size_t)item * K + lane] = vr;
+    wave_sum_all(acc, cnt);
+    store_normal_by_lane<K>(acc, lane, N + (size_t)item * (K * K), r + (size_t)item * K);
     if (lane == 0 && hits) hits[item] = cnt;
   }
-}
-
-// the segment of sample t: s, and its clamped [lo, hi); -1 with lo = hi = 0 when t is in none
-__device__ __forceinline__ int find_segment(const int* __restrict__ bound, int S, int T, int t, int& lo, int& hi) {
-  int a = 0, b = S;  // the largest a in 0 .. S - 1 with bound[a] <= t, or 0
-  while (b - a > 1) {
-    const int m = (a + b) >> 1;
-    if (clamp_bound(bound[m], T) <= t)
-      a = m;
-    else
-      b = m;
-  }
-  lo = clamp_bound(bound[a], T), hi = clamp_bound(bound[a + 1], T);
-  if (t >= lo && t < hi) return a;
-  lo = hi = 0;
-  return -1;
 }
 
 // x and y may be the same buffer: a thread reads its samples before it writes them, and no other thread touches them
@@ -160,15 +120,8 @@ __global__ __launch_bounds__(kThreads) void line_apply_kernel(const float* x, si
     const long long row = tile / tiles_per_row;
     const int q = (int)(tile - row * tiles_per_row) * kTileSamples + kOwn * (int)threadIdx.x;
     if (q >= T) continue;
-    const float* const xr = x + (size_t)row * ld_x;
     float v[kOwn];
-    if ((wide & kWideX) && q + kOwn <= T) {
-      const float4 w = *reinterpret_cast<const float4*>(xr + q);
-      v[0] = w.x, v[1] = w.y, v[2] = w.z, v[3] = w.w;
-    } else {
-#pragma unroll
-      for (int k = 0; k < kOwn; ++k) v[k] = q + k < T ? xr[q + k] : 0.0f;
-    }
+    load_own<kOwn>(x + (size_t)row * ld_x, q, T, wide & kWideX, v);
     double f[NL];
 #pragma unroll
     for (int l = 0; l < NL; ++l) f[l] = nu[(size_t)row * NL + l];
@@ -191,18 +144,9 @@ __global__ __launch_bounds__(kThreads) void line_apply_kernel(const float* x, si
       const float g = (float)sum;
       v[k] = sign < 0 ? v[k] - g : v[k] + g;
     }
-    float* const yr = y + (size_t)row * ld_y;
-    if ((wide & kWideY) && q + kOwn <= T) {
-      *reinterpret_cast<float4*>(yr + q) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < kOwn; ++k)
-        if (q + k < T) yr[q + k] = v[k];
-    }
+    store_own<kOwn>(y + (size_t)row * ld_y, q, T, wide & kWideY, v);
   }
 }
-
-bool aligned(const void* p, size_t ld_bytes, unsigned to) { return (((uintptr_t)p | (uintptr_t)ld_bytes) & (to - 1u)) == 0; }
 
 template <int NPOLY, int NL>
 void launch_normal(mrx_ctx* ctx, const float* x, size_t ld_x, const float* model, size_t ld_m, const uint8_t* flags, size_t ld_f, int T,
@@ -213,9 +157,9 @@ void launch_normal(mrx_ctx* ctx, const float* x, size_t ld_x, const float* model
 
 template <int NL>
 void launch_apply(mrx_ctx* ctx, const float* x, size_t ld_x, int T, const int32_t* bound, int S, const double* nu, int n_poly, const double* a,
-                  int sign, float* y, size_t ld_y, int wide, int tiles_per_row, long long n_tiles) {
-  hipLaunchKernelGGL(line_apply_kernel<NL>, dim3(mrx_resident_blocks(ctx, n_tiles)), dim3(kThreads), 0, ctx->stream, x, ld_x, T, bound, S, nu, n_poly,
-                     a, sign, y, ld_y, wide, tiles_per_row, n_tiles);
+                  int sign, float* y, size_t ld_y, int wide, const mrx_tile_grid_t& g) {
+  hipLaunchKernelGGL(line_apply_kernel<NL>, dim3(g.blocks), dim3(kThreads), 0, ctx->stream, x, ld_x, T, bound, S, nu, n_poly, a, sign, y, ld_y, wide,
+                     g.tiles_per_row, g.n_tiles);
 }
 
 }  // namespace
@@ -266,18 +210,17 @@ int mrx_tod_line_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T
   MRX_REQUIRE(ctx, sign == 1 || sign == -1, "sign must be -1 or +1");
   MRX_REQUIRE(ctx, ld_x >= (size_t)T && ld_y >= (size_t)T, "ld_x or ld_y smaller than T");
   MRX_REQUIRE(ctx, d_y != d_x || ld_y == ld_x, "in place (d_y == d_x) needs ld_y == ld_x");
-  const int tiles_per_row = (T + kTileSamples - 1) / kTileSamples;
-  const long long n_tiles = (long long)D * tiles_per_row;
-  const int wide = (aligned(d_x, ld_x * 4, 16) ? kWideX : 0) | (aligned(d_y, ld_y * 4, 16) ? kWideY : 0);
+  const mrx_tile_grid_t g = mrx_tile_grid(ctx, D, T, kTileSamples);
+  const int wide = (mrx_aligned(d_x, ld_x * 4, 16) ? kWideX : 0) | (mrx_aligned(d_y, ld_y * 4, 16) ? kWideY : 0);
   switch (L) {
     case 1:
-      launch_apply<1>(ctx, d_x, ld_x, T, d_bound, S, d_nu, n_poly, d_a, sign, d_y, ld_y, wide, tiles_per_row, n_tiles);
+      launch_apply<1>(ctx, d_x, ld_x, T, d_bound, S, d_nu, n_poly, d_a, sign, d_y, ld_y, wide, g);
       break;
     case 2:
-      launch_apply<2>(ctx, d_x, ld_x, T, d_bound, S, d_nu, n_poly, d_a, sign, d_y, ld_y, wide, tiles_per_row, n_tiles);
+      launch_apply<2>(ctx, d_x, ld_x, T, d_bound, S, d_nu, n_poly, d_a, sign, d_y, ld_y, wide, g);
       break;
     default:
-      launch_apply<3>(ctx, d_x, ld_x, T, d_bound, S, d_nu, n_poly, d_a, sign, d_y, ld_y, wide, tiles_per_row, n_tiles);
+      launch_apply<3>(ctx, d_x, ld_x, T, d_bound, S, d_nu, n_poly, d_a, sign, d_y, ld_y, wide, g);
   }
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;

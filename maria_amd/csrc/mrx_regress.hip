@@ -7,9 +7,7 @@
 //   y[d][t]     = x[d][t] + sign * (float)(sum over i, in order, of a[d][i] * (double)B[g][i][t])
 // The file is built without FMA contraction: every operation above is one float64 rounding.
 //
-// Sample ownership is the same in all three kernels and does not depend on alignment: a workgroup of 256 threads takes
-// 1024 consecutive samples, thread o the four samples 4 o .. 4 o + 3 of them.  Where a pointer and its pitch are multiples
-// of 16 bytes (flags: of 4) the four samples are one load or store, otherwise four.  Nothing is read or written past T.
+// Sample ownership is the same in all three kernels: the tile and a thread's own four samples of mrx_tod_dev.h.
 //
 // mrx_tod_column_mean.  A workgroup takes (group g, tile of 1024 samples) and walks ALL rows 0 .. D - 1 in ascending
 // order; a row of another group is skipped before any of its samples is read (the group is uniform: a scalar branch),
@@ -18,49 +16,24 @@
 //
 // mrx_tod_regress_normal.  A workgroup takes one row and walks its tiles in ascending order; a thread adds its samples
 // into K (K + 1) / 2 + K float64 accumulators in registers (the upper triangle of N, and r), the 64 lanes of a wave meet
-// in a butterfly (xor 32 .. 1), the four waves in LDS, wave 0 first.  The order is a function of T alone.  The kernel is
+// (mrx_tod_dev.h: wave_sum_all), the four waves in LDS, wave 0 first.  The order is a function of T alone.  The kernel is
 // compiled for K classes 2, 4 and 8; a flagged sample enters as a row of zeros (selected, never multiplied by x).
 //
 // mrx_tod_regress_apply.  A streaming pass over (row, tile); the row's K coefficients are uniform.
 #include "mrx_internal.h"
+#include "mrx_tod_dev.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
-constexpr int kWaves = kThreads / kWave;
-constexpr int kOwn = 4;  // consecutive samples of a thread
-constexpr int kTileSamples = kThreads * kOwn;
+using namespace mrx_tod;  // the 256-thread, four-sample tile, kWave
+
 constexpr int kRows = 4;  // rows of a group a thread of the column mean has in flight
 constexpr int kMaxGroups = 16;
 constexpr int kMaxTemplates = 8;
 
 enum : int { kWideX = 1, kWideM = 2, kWideF = 4, kWideB = 8, kWideY = 16 };
-
-// the thread's four samples q .. q + 3 of a row; beyond T: zero
-__device__ __forceinline__ void load4(const float* row, int q, int T, bool wide, float (&v)[kOwn]) {
-  if (wide && q + kOwn <= T) {
-    const float4 w = *reinterpret_cast<const float4*>(row + q);
-    v[0] = w.x, v[1] = w.y, v[2] = w.z, v[3] = w.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < kOwn; ++k) v[k] = q + k < T ? row[q + k] : 0.0f;
-  }
-}
-
-// their flags; beyond T, flagged.  row == nullptr: no flags
-__device__ __forceinline__ void load4(const unsigned char* row, int q, int T, bool wide, unsigned char (&f)[kOwn]) {
-  if (row && wide && q + kOwn <= T) {
-    const unsigned w = *reinterpret_cast<const unsigned*>(row + q);
-#pragma unroll
-    for (int k = 0; k < kOwn; ++k) f[k] = (unsigned char)((w >> (8 * k)) & 255u);
-  } else {
-#pragma unroll
-    for (int k = 0; k < kOwn; ++k) f[k] = q + k < T ? (row ? row[q + k] : (unsigned char)0) : (unsigned char)1;
-  }
-}
 
 __global__ __launch_bounds__(kThreads) void column_mean_kernel(const float* __restrict__ x, size_t ld_x, const float* __restrict__ model,
                                                                size_t ld_m, const unsigned char* __restrict__ flags, size_t ld_f, int D, int T,
@@ -84,9 +57,9 @@ __global__ __launch_bounds__(kThreads) void column_mean_kernel(const float* __re
         const int d = d0 + r;
         in[r] = d < D && (unsigned)(group ? group[d] : 0) == (unsigned)g;
         if (in[r]) {
-          load4(x + (size_t)d * ld_x, q, T, wide & kWideX, xv[r]);
-          if (model) load4(model + (size_t)d * ld_m, q, T, wide & kWideM, mv[r]);
-          load4(flags ? flags + (size_t)d * ld_f : nullptr, q, T, wide & kWideF, fv[r]);
+          load_own<kOwn>(x + (size_t)d * ld_x, q, T, wide & kWideX, xv[r]);
+          if (model) load_own<kOwn>(model + (size_t)d * ld_m, q, T, wide & kWideM, mv[r]);
+          load_own_or_none<kOwn>(flags ? flags + (size_t)d * ld_f : nullptr, q, T, wide & kWideF, fv[r]);
         }
       }
 #pragma unroll
@@ -147,13 +120,13 @@ __global__ __launch_bounds__(kThreads) void regress_normal_kernel(const float* _
   for (int q = kOwn * tid; q < T; q += kTileSamples) {
     float xv[kOwn], mv[kOwn], bv[KC][kOwn];
     unsigned char fv[kOwn];
-    load4(xr, q, T, wide & kWideX, xv);
-    if (mr) load4(mr, q, T, wide & kWideM, mv);
-    load4(fr, q, T, wide & kWideF, fv);
+    load_own<kOwn>(xr, q, T, wide & kWideX, xv);
+    if (mr) load_own<kOwn>(mr, q, T, wide & kWideM, mv);
+    load_own_or_none<kOwn>(fr, q, T, wide & kWideF, fv);
 #pragma unroll
     for (int i = 0; i < KC; ++i) {
       if (i < K) {
-        load4(Bg + (size_t)i * ld_b, q, T, wide & kWideB, bv[i]);
+        load_own<kOwn>(Bg + (size_t)i * ld_b, q, T, wide & kWideB, bv[i]);
       } else {
 #pragma unroll
         for (int k = 0; k < kOwn; ++k) bv[i][k] = 0.0f;
@@ -177,12 +150,7 @@ __global__ __launch_bounds__(kThreads) void regress_normal_kernel(const float* _
       for (int i = 0; i < KC; ++i) acc[NP + i] = acc[NP + i] + b[i] * term;
     }
   }
-#pragma unroll
-  for (int o = kWave / 2; o >= 1; o >>= 1) {  // every lane ends with the same sums: a + b is b + a
-#pragma unroll
-    for (int a = 0; a < NA; ++a) acc[a] = acc[a] + __shfl_xor(acc[a], o, kWave);
-    n += __shfl_xor(n, o, kWave);
-  }
+  wave_sum_all(acc, n);
   const int wave = tid / kWave;
   if ((tid & (kWave - 1)) == 0) {
 #pragma unroll
@@ -215,7 +183,7 @@ __global__ __launch_bounds__(kThreads) void regress_apply_kernel(const float* x,
     if (q >= T) continue;
     const int gd = group ? group[row] : 0;
     float v[kOwn];
-    load4(x + (size_t)row * ld_x, q, T, wide & kWideX, v);
+    load_own<kOwn>(x + (size_t)row * ld_x, q, T, wide & kWideX, v);
     if ((unsigned)gd < (unsigned)G) {
       const float* const Bg = B + (size_t)gd * K * ld_b;
       const double* const ar = a + (size_t)row * K;
@@ -226,7 +194,7 @@ __global__ __launch_bounds__(kThreads) void regress_apply_kernel(const float* x,
       for (int i = 0; i < kMaxTemplates; ++i) {
         if (i < K) {
           float bv[kOwn];
-          load4(Bg + (size_t)i * ld_b, q, T, wide & kWideB, bv);
+          load_own<kOwn>(Bg + (size_t)i * ld_b, q, T, wide & kWideB, bv);
           const double ai = ar[i];
 #pragma unroll
           for (int k = 0; k < kOwn; ++k) s[k] = s[k] + ai * (double)bv[k];
@@ -238,22 +206,13 @@ __global__ __launch_bounds__(kThreads) void regress_apply_kernel(const float* x,
         v[k] = sign < 0 ? v[k] - f : v[k] + f;
       }
     }
-    float* const yr = y + (size_t)row * ld_y;
-    if ((wide & kWideY) && q + kOwn <= T) {
-      *reinterpret_cast<float4*>(yr + q) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < kOwn; ++k)
-        if (q + k < T) yr[q + k] = v[k];
-    }
+    store_own<kOwn>(y + (size_t)row * ld_y, q, T, wide & kWideY, v);
   }
 }
 
-bool aligned(const void* p, size_t ld_bytes, unsigned to) { return (((uintptr_t)p | (uintptr_t)ld_bytes) & (to - 1u)) == 0; }
-
 int wide_inputs(const float* x, size_t ld_x, const float* model, size_t ld_m, const uint8_t* flags, size_t ld_f) {
-  return (aligned(x, ld_x * 4, 16) ? kWideX : 0) | (model && aligned(model, ld_m * 4, 16) ? kWideM : 0) |
-         (flags && aligned(flags, ld_f, 4) ? kWideF : 0);
+  return (mrx_aligned(x, ld_x * 4, 16) ? kWideX : 0) | (model && mrx_aligned(model, ld_m * 4, 16) ? kWideM : 0) |
+         (flags && mrx_aligned(flags, ld_f, 4) ? kWideF : 0);
 }
 
 template <int KC>
@@ -278,11 +237,9 @@ int mrx_tod_column_mean(mrx_ctx* ctx, const float* d_x, size_t ld_x, const float
   MRX_REQUIRE(ctx, G >= 1 && G <= kMaxGroups, "G must be in 1 .. 16");
   MRX_REQUIRE(ctx, ld_x >= (size_t)T && (!d_model || ld_m >= (size_t)T) && (!d_flags || ld_f >= (size_t)T) && (!d_mean || ld_c >= (size_t)T),
               "ld_x, ld_m, ld_f or ld_c smaller than T");
-  const int tiles = (T + kTileSamples - 1) / kTileSamples;
-  const long long n_items = (long long)G * tiles;
-  hipLaunchKernelGGL(column_mean_kernel, dim3(mrx_resident_blocks(ctx, n_items)), dim3(kThreads), 0, ctx->stream, d_x, ld_x, d_model, ld_m, d_flags,
-                     ld_f, D, T, d_group, d_u, d_v, d_off, d_S, d_W, d_mean, ld_c, wide_inputs(d_x, ld_x, d_model, ld_m, d_flags, ld_f), tiles,
-                     n_items);
+  const mrx_tile_grid_t g = mrx_tile_grid(ctx, G, T, kTileSamples);  // items: (group, tile)
+  hipLaunchKernelGGL(column_mean_kernel, dim3(g.blocks), dim3(kThreads), 0, ctx->stream, d_x, ld_x, d_model, ld_m, d_flags, ld_f, D, T, d_group, d_u,
+                     d_v, d_off, d_S, d_W, d_mean, ld_c, wide_inputs(d_x, ld_x, d_model, ld_m, d_flags, ld_f), g.tiles_per_row, g.n_tiles);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;
 }
@@ -298,7 +255,7 @@ int mrx_tod_regress_normal(mrx_ctx* ctx, const float* d_x, size_t ld_x, const fl
   MRX_REQUIRE(ctx, K >= 1 && K <= kMaxTemplates, "K must be in 1 .. 8");
   MRX_REQUIRE(ctx, ld_x >= (size_t)T && (!d_model || ld_m >= (size_t)T) && (!d_flags || ld_f >= (size_t)T) && ld_b >= (size_t)T,
               "ld_x, ld_m, ld_f or ld_b smaller than T");
-  const int wide = wide_inputs(d_x, ld_x, d_model, ld_m, d_flags, ld_f) | (aligned(d_B, ld_b * 4, 16) ? kWideB : 0);
+  const int wide = wide_inputs(d_x, ld_x, d_model, ld_m, d_flags, ld_f) | (mrx_aligned(d_B, ld_b * 4, 16) ? kWideB : 0);
   if (K <= 2)
     launch_normal<2>(ctx, d_x, ld_x, d_model, ld_m, d_flags, ld_f, D, T, d_group, G, d_B, ld_b, K, d_N, d_r, d_hits, wide);
   else if (K <= 4)
@@ -320,11 +277,11 @@ int mrx_tod_regress_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, in
   MRX_REQUIRE(ctx, sign == 1 || sign == -1, "sign must be -1 or +1");
   MRX_REQUIRE(ctx, ld_x >= (size_t)T && ld_y >= (size_t)T && ld_b >= (size_t)T, "ld_x, ld_y or ld_b smaller than T");
   MRX_REQUIRE(ctx, d_y != d_x || ld_y == ld_x, "in place (d_y == d_x) needs ld_y == ld_x");
-  const int tiles_per_row = (T + kTileSamples - 1) / kTileSamples;
-  const long long n_tiles = (long long)D * tiles_per_row;
-  const int wide = (aligned(d_x, ld_x * 4, 16) ? kWideX : 0) | (aligned(d_B, ld_b * 4, 16) ? kWideB : 0) | (aligned(d_y, ld_y * 4, 16) ? kWideY : 0);
-  hipLaunchKernelGGL(regress_apply_kernel, dim3(mrx_resident_blocks(ctx, n_tiles)), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, d_group, G, d_B,
-                     ld_b, K, d_a, sign, d_y, ld_y, wide, tiles_per_row, n_tiles);
+  const mrx_tile_grid_t g = mrx_tile_grid(ctx, D, T, kTileSamples);
+  const int wide = (mrx_aligned(d_x, ld_x * 4, 16) ? kWideX : 0) | (mrx_aligned(d_B, ld_b * 4, 16) ? kWideB : 0) |
+                   (mrx_aligned(d_y, ld_y * 4, 16) ? kWideY : 0);
+  hipLaunchKernelGGL(regress_apply_kernel, dim3(g.blocks), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, d_group, G, d_B, ld_b, K, d_a, sign, d_y,
+                     ld_y, wide, g.tiles_per_row, g.n_tiles);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;
 }

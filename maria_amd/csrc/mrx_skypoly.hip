@@ -17,15 +17,18 @@
 // The fit is compiled per K, so the triangle and the Cholesky factor unroll into registers, and per "flags given": without
 // flags N and hits are the same for every sample, and a thread keeps ONE copy of them (the same additions in the same
 // order: the bits of the per-sample sum).  A thread owns OWN consecutive samples: 4, but 2 at K = 5 and 6 with flags (27
-// float64 accumulators a sample at K = 6).  Where a pointer and its pitch are multiples of 4 OWN bytes (flags: of OWN) the
-// OWN samples are one load or store, otherwise OWN.  Nothing is read or written past T.
+// float64 accumulators a sample at K = 6), read and written by load_own<OWN> and store_own<OWN> (mrx_tod_dev.h).
 #include "mrx_internal.h"
+#include "mrx_tod_dev.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int kThreads = 256;
+using mrx_tod::kThreads;
+using mrx_tod::load_own;
+using mrx_tod::store_own;
+
 constexpr int kRows = 4;  // rows of a group a thread has in flight
 constexpr int kMaxGroups = 16;
 constexpr int kMaxTerms = 6;
@@ -33,54 +36,6 @@ constexpr int kMaxTerms = 6;
 enum : int { kWideX = 1, kWideM = 2, kWideF = 4, kWideY = 8 };
 
 constexpr int own_of(int K, bool flags) { return K <= 4 || !flags ? 4 : 2; }
-
-// the thread's samples q .. q + OWN - 1 of a row; beyond T: zero
-template <int OWN>
-__device__ __forceinline__ void load_own(const float* row, int q, int T, bool wide, float (&v)[OWN]) {
-  if (wide && q + OWN <= T) {
-    if constexpr (OWN == 4) {
-      const float4 w = *reinterpret_cast<const float4*>(row + q);
-      v[0] = w.x, v[1] = w.y, v[2] = w.z, v[3] = w.w;
-    } else {
-      const float2 w = *reinterpret_cast<const float2*>(row + q);
-      v[0] = w.x, v[1] = w.y;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < OWN; ++k) v[k] = q + k < T ? row[q + k] : 0.0f;
-  }
-}
-
-// their flags; beyond T, flagged
-template <int OWN>
-__device__ __forceinline__ void load_own(const unsigned char* row, int q, int T, bool wide, unsigned char (&f)[OWN]) {
-  if (wide && q + OWN <= T) {
-    unsigned w;
-    if constexpr (OWN == 4)
-      w = *reinterpret_cast<const unsigned*>(row + q);
-    else
-      w = *reinterpret_cast<const unsigned short*>(row + q);
-#pragma unroll
-    for (int k = 0; k < OWN; ++k) f[k] = (unsigned char)((w >> (8 * k)) & 255u);
-  } else {
-#pragma unroll
-    for (int k = 0; k < OWN; ++k) f[k] = q + k < T ? row[q + k] : (unsigned char)1;
-  }
-}
-
-template <int OWN>
-__device__ __forceinline__ void store_own(float* row, int q, int T, bool wide, const float (&v)[OWN]) {
-  if (wide && q + OWN <= T) {
-    if constexpr (OWN == 4)
-      *reinterpret_cast<float4*>(row + q) = make_float4(v[0], v[1], v[2], v[3]);
-    else
-      *reinterpret_cast<float2*>(row + q) = make_float2(v[0], v[1]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < OWN; ++k)
-      if (q + k < T) row[q + k] = v[k];
-  }
-}
 
 struct FitShape {
   size_t ld_x, ld_m, ld_f, ld_c;
@@ -264,8 +219,8 @@ __global__ __launch_bounds__(kThreads) void column_apply_kernel(const float* x, 
                                                                 const double* __restrict__ P, int K, const double* __restrict__ c, size_t ld_c,
                                                                 const double* __restrict__ e, const double* __restrict__ h, int sign, float* y,
                                                                 size_t ld_y, int wide, int tiles, long long n_items) {
-  constexpr int OWN = 4;
-  constexpr int kTile = kThreads * OWN;
+  constexpr int OWN = mrx_tod::kOwn;
+  constexpr int kTile = mrx_tod::kTileSamples;
   for (long long item = blockIdx.x; item < n_items; item += gridDim.x) {
     const int g = (int)(item / tiles);
     const int q = (int)(item - (long long)g * tiles) * kTile + OWN * (int)threadIdx.x;
@@ -317,18 +272,17 @@ __global__ __launch_bounds__(kThreads) void column_apply_kernel(const float* x, 
   }
 }
 
-bool aligned(const void* p, size_t ld_bytes, unsigned to) { return (((uintptr_t)p | (uintptr_t)ld_bytes) & (to - 1u)) == 0; }
-
 template <int K, bool FLAGS>
 void launch_fit(mrx_ctx* ctx, const float* x, const float* model, const uint8_t* flags, const int32_t* group, int G, const double* P,
                 const double* u, const double* v, const double* off, double* c, uint8_t* ok, uint32_t* hits, double* N, double* r, FitShape A) {
   constexpr int OWN = own_of(K, FLAGS);
-  A.wide = (aligned(x, A.ld_x * 4, 4 * OWN) ? kWideX : 0) | (model && aligned(model, A.ld_m * 4, 4 * OWN) ? kWideM : 0) |
-           (FLAGS && aligned(flags, A.ld_f, OWN) ? kWideF : 0);
-  A.tiles = (A.T + kThreads * OWN - 1) / (kThreads * OWN);
-  A.n_items = (long long)G * A.tiles;
-  hipLaunchKernelGGL((column_fit_kernel<K, FLAGS>), dim3(mrx_resident_blocks(ctx, A.n_items)), dim3(kThreads), 0, ctx->stream, x, model, flags,
-                     group, P, u, v, off, c, ok, hits, N, r, A);
+  A.wide = (mrx_aligned(x, A.ld_x * 4, 4 * OWN) ? kWideX : 0) | (model && mrx_aligned(model, A.ld_m * 4, 4 * OWN) ? kWideM : 0) |
+           (FLAGS && mrx_aligned(flags, A.ld_f, OWN) ? kWideF : 0);
+  const mrx_tile_grid_t g = mrx_tile_grid(ctx, G, A.T, kThreads * OWN);  // items: (group, tile)
+  A.tiles = g.tiles_per_row;
+  A.n_items = g.n_tiles;
+  hipLaunchKernelGGL((column_fit_kernel<K, FLAGS>), dim3(g.blocks), dim3(kThreads), 0, ctx->stream, x, model, flags, group, P, u, v, off, c, ok,
+                     hits, N, r, A);
 }
 
 }  // namespace
@@ -377,12 +331,11 @@ int mrx_tod_column_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int
   MRX_REQUIRE(ctx, sign == 1 || sign == -1, "sign must be -1 or +1");
   MRX_REQUIRE(ctx, ld_x >= (size_t)T && ld_y >= (size_t)T && ld_c >= (size_t)T, "ld_x, ld_y or ld_c smaller than T");
   MRX_REQUIRE(ctx, d_y != d_x || ld_y == ld_x, "in place (d_y == d_x) needs ld_y == ld_x");
-  const int tiles = (T + kThreads * 4 - 1) / (kThreads * 4);
   const bool copies = d_y != d_x && d_group;  // the rows of no group: there are none without d_group, and in place they stay
-  const long long n_items = (long long)(G + (copies ? 1 : 0)) * tiles;
-  const int wide = (aligned(d_x, ld_x * 4, 16) ? kWideX : 0) | (aligned(d_y, ld_y * 4, 16) ? kWideY : 0);
-  hipLaunchKernelGGL(column_apply_kernel, dim3(mrx_resident_blocks(ctx, n_items)), dim3(kThreads), 0, ctx->stream, d_x, ld_x, D, T, d_group, G,
-                     d_P, K, d_c, ld_c, d_e, d_h, sign, d_y, ld_y, wide, tiles, n_items);
+  const mrx_tile_grid_t g = mrx_tile_grid(ctx, G + (copies ? 1 : 0), T, mrx_tod::kTileSamples);  // items: (group, tile)
+  const int wide = (mrx_aligned(d_x, ld_x * 4, 16) ? kWideX : 0) | (mrx_aligned(d_y, ld_y * 4, 16) ? kWideY : 0);
+  hipLaunchKernelGGL(column_apply_kernel, dim3(g.blocks), dim3(kThreads), 0, ctx->stream, d_x, ld_x, D, T, d_group, G, d_P, K, d_c, ld_c, d_e, d_h,
+                     sign, d_y, ld_y, wide, g.tiles_per_row, g.n_tiles);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;
 }

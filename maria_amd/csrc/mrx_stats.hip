@@ -11,7 +11,7 @@
 // one 16-byte copy (x, the model) and one 4-byte copy (the flags) of no alignment beyond the element's, which the
 // compiler turns into the widest loads the target allows at that alignment; the last, partial chunk is read sample by
 // sample.  Either way a sample goes to the same lane and the same place in that lane's order: chunk after chunk, the
-// four samples ascending, then the 64 lanes meet in a butterfly (xor 32 .. 1), after which every lane holds every sum.
+// four samples ascending, then the 64 lanes meet (mrx_tod_dev.h: wave_sum_all), after which every lane holds every sum.
 // The order is a function of L alone.  The segment is read twice: the first pass gives n, p, the sum, min, max and D2,
 // the second, with mu = sum / n known to every lane, the central sums (its reads come from cache: a segment of a scan is
 // a few tens of KiB).  Three of a lane's four pairs lie inside the lane; the pair across the seam takes the last sample
@@ -20,40 +20,27 @@
 //
 // mrx_tod_segment_flag.  A streaming pass over (row, tile of 4096 flags), thread o the sixteen bytes 16 o .. 16 o + 15 (one
 // 16-byte access where pointer and pitch allow it, bytes otherwise).  A thread finds its sample's segment as
-// mrx_tod_segment_apply does (bisection over the clamped bounds, kept while the following samples stay inside) and
+// mrx_tod_segment_apply does (find_segment, kept while the following samples stay inside) and
 // writes only where it has set something: a thread with no masked segment reads and leaves.
 #include "mrx_internal.h"
+#include "mrx_tod_dev.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
-constexpr int kWaves = kThreads / kWave;
+using mrx_tod::clamp_bound;
+using mrx_tod::find_segment;
+using mrx_tod::kThreads;
+using mrx_tod::kWave;
+using mrx_tod::kWaves;
+using mrx_tod::wave_sum_all;
+
 constexpr int kOwn = 4;                 // consecutive samples of a lane in a chunk
 constexpr int kChunk = kWave * kOwn;    // 256 samples
 constexpr int kFlight = 2;              // chunks whose loads go out together
 constexpr int kFlagOwn = 16;            // consecutive flags of a thread of the flagging pass
 constexpr int kFlagTile = kThreads * kFlagOwn;
-
-__device__ __forceinline__ int clamp_bound(int b, int T) { return min(max(b, 0), T); }
-
-// the segment of sample t, as in mrx_subscan.hip: s, and its clamped [lo, hi); -1 with lo = hi = 0 when t is in none
-__device__ __forceinline__ int find_segment(const int* __restrict__ bound, int S, int T, int t, int& lo, int& hi) {
-  int a = 0, b = S;  // the largest a in 0 .. S - 1 with bound[a] <= t, or 0
-  while (b - a > 1) {
-    const int m = (a + b) >> 1;
-    if (clamp_bound(bound[m], T) <= t)
-      a = m;
-    else
-      b = m;
-  }
-  lo = clamp_bound(bound[a], T), hi = clamp_bound(bound[a + 1], T);
-  if (t >= lo && t < hi) return a;
-  lo = hi = 0;
-  return -1;
-}
 
 // A lane's four samples of the chunk that starts `rem` samples before the segment's end: term, selected to 0.0
 // where the sample is flagged or past the end, and keep.  xs, ms, fs point at the chunk's first sample.  A chunk past the
@@ -143,14 +130,14 @@ __global__ __launch_bounds__(kThreads) void segment_moments_kernel(const float* 
         }
       }
     }
+    wave_sum_all(sum);
+    wave_sum_all(d2);
+    wave_sum_all(n);
+    wave_sum_all(p);
 #pragma unroll
-    for (int o = kWave / 2; o >= 1; o >>= 1) {  // every lane ends with the same sums: a + b is b + a
-      sum = sum + __shfl_xor(sum, o, kWave);
-      d2 = d2 + __shfl_xor(d2, o, kWave);
+    for (int o = kWave / 2; o >= 1; o >>= 1) {  // the same butterfly: every lane ends with the same minimum and maximum
       mn = nan_min(mn, __shfl_xor(mn, o, kWave));
       mx = nan_max(mx, __shfl_xor(mx, o, kWave));
-      n += __shfl_xor(n, o, kWave);
-      p += __shfl_xor(p, o, kWave);
     }
     const double mu = n ? sum / (double)n : 0.0;
     double m2 = 0.0, m3 = 0.0, m4 = 0.0;
@@ -176,12 +163,9 @@ __global__ __launch_bounds__(kThreads) void segment_moments_kernel(const float* 
           }
         }
       }
-#pragma unroll
-      for (int o = kWave / 2; o >= 1; o >>= 1) {
-        m2 = m2 + __shfl_xor(m2, o, kWave);
-        m3 = m3 + __shfl_xor(m3, o, kWave);
-        m4 = m4 + __shfl_xor(m4, o, kWave);
-      }
+      wave_sum_all(m2);
+      wave_sum_all(m3);
+      wave_sum_all(m4);
     }
     // lane j stores value j, picked by selects
     double v = 0.0;
@@ -279,11 +263,10 @@ int mrx_tod_segment_flag(mrx_ctx* ctx, uint8_t* d_flags, size_t ld_f, int D, int
   MRX_REQUIRE(ctx, S >= 1, "need S >= 1 segments");
   MRX_REQUIRE(ctx, value >= 1 && value <= 255, "value must be in 1 .. 255");
   MRX_REQUIRE(ctx, ld_f >= (size_t)T, "ld_f smaller than T");
-  const int tiles_per_row = (T + kFlagTile - 1) / kFlagTile;
-  const long long n_tiles = (long long)D * tiles_per_row;
-  const int wide = mrx_aligned16(d_flags, ld_f);
-  hipLaunchKernelGGL(segment_flag_kernel, dim3(mrx_resident_blocks(ctx, n_tiles)), dim3(kThreads), 0, ctx->stream, d_flags, ld_f, T, d_bound, S,
-                     d_mask, (unsigned)value, wide, tiles_per_row, n_tiles);
+  const mrx_tile_grid_t g = mrx_tile_grid(ctx, D, T, kFlagTile);
+  const int wide = mrx_aligned(d_flags, ld_f, 16);
+  hipLaunchKernelGGL(segment_flag_kernel, dim3(g.blocks), dim3(kThreads), 0, ctx->stream, d_flags, ld_f, T, d_bound, S, d_mask, (unsigned)value,
+                     wide, g.tiles_per_row, g.n_tiles);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;
 }

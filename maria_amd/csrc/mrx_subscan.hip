@@ -9,38 +9,30 @@
 // in float64 from the int32 offset: every value involved is an integer below 2^32, so it is the integer numerator exactly.
 //
 // mrx_tod_segment_normal.  One wave takes one (row, segment) and owns all of its sums: lane o adds the samples lo + o,
-// lo + o + 64, .. in ascending order into K (K + 1) / 2 + K float64 accumulators in registers (the upper triangle of N,
-// and r), then the 64 lanes meet in a butterfly (xor 32 .. 1), after which every lane holds every sum; lane i K + j
-// stores N[i][j], lane i stores r[i].  The order is a function of L alone.  A flagged sample enters as a row of zeros
-// (selected, never multiplied by x).  The four waves of a workgroup take four consecutive (row, segment) pairs and share
-// nothing: no LDS, no barrier.  The kernel is compiled for every K = 1 .. 8.
+// lo + o + 64, .. in ascending order into K (K + 1) / 2 + K float64 accumulators in registers, then the 64 lanes meet and
+// store (mrx_tod_dev.h: rhs_add, wave_sum_all, store_normal_by_lane).  The order is a function of L alone.  A flagged
+// sample enters as a row of zeros (selected, never multiplied by x).  The four waves of a workgroup take four consecutive
+// (row, segment) pairs and share nothing: no LDS, no barrier.  The kernel is compiled for every K = 1 .. 8.
 //
-// mrx_tod_segment_apply.  A streaming pass over (row, tile of 1024 samples), thread o the four samples 4 o .. 4 o + 3 as in
-// mrx_regress.hip (one 16-byte access where pointer and pitch allow it).  A thread finds its sample's segment by bisection
-// over the clamped bounds (the largest s with bound[s] <= t), keeps it while the following samples stay inside, and
-// checks lo <= t < hi: with bounds that do not ascend a sample may take another segment than the caller meant, but every
-// index is inside the arrays whatever d_bound holds.
+// mrx_tod_segment_apply.  A streaming pass over (row, tile), a thread its own four samples (mrx_tod_dev.h).  A thread
+// finds its sample's segment by find_segment and keeps it while the following samples stay inside.
 //
 // mrx_tod_segment_project.  The filter with its flags fixed, F = I - T A T^t M or its transpose, in place: the sums of the
 // first entry, a K x K product with the caller's frozen A = N^-1, and the subtraction of the second, one wave a (row,
 // segment) for all three.  Its comment is above its kernel.
 #include "mrx_internal.h"
+#include "mrx_tod_dev.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
-constexpr int kWaves = kThreads / kWave;
-constexpr int kOwn = 4;  // consecutive samples of a thread of the application
-constexpr int kTileSamples = kThreads * kOwn;
+using namespace mrx_tod;  // the 256-thread, four-sample tile, kWave
+
 constexpr int kMaxOrder = 8;  // K: the polynomials P_0 .. P_{K - 1}
 constexpr int kFlight = 2;    // samples of a lane whose loads go out together
 
 enum : int { kWideX = 1, kWideY = 2 };
-
-__device__ __forceinline__ int clamp_bound(int b, int T) { return min(max(b, 0), T); }
 
 // P_0 .. P_{K - 1} at u; the loop unrolls, so that c_n is a constant rounded once
 template <int K>
@@ -95,56 +87,20 @@ __global__ __launch_bounds__(kThreads) void segment_normal_kernel(const float* _
         for (int i = 0; i < K; ++i) b[i] = keep ? P[i] : 0.0;
         const double term = keep ? (mr ? (double)xv[e] - (double)mv[e] : (double)xv[e]) : 0.0;
         n += keep ? 1u : 0u;
+        // (written out, on a row selected here: mrx_tod_dev.h says why)
         int a = 0;
 #pragma unroll
         for (int i = 0; i < K; ++i) {
 #pragma unroll
           for (int j = i; j < K; ++j, ++a) acc[a] = acc[a] + b[i] * b[j];
         }
-#pragma unroll
-        for (int i = 0; i < K; ++i) acc[NP + i] = acc[NP + i] + b[i] * term;
+        rhs_add<K>(acc + NP, P, keep, term);
       }
     }
-#pragma unroll
-    for (int o = kWave / 2; o >= 1; o >>= 1) {  // every lane ends with the same sums: a + b is b + a
-#pragma unroll
-      for (int a = 0; a < NA; ++a) acc[a] = acc[a] + __shfl_xor(acc[a], o, kWave);
-      n += __shfl_xor(n, o, kWave);
-    }
-    // lane i K + j picks N[i][j] and lane i picks r[i] by selects: the accumulators are never indexed by a lane's number
-    // (the comparisons are made here, item by item: hoisted out of the item loop their K K masks would not fit the SGPRs)
-    int me = lane;
-    asm volatile("" : "+v"(me));
-    double vN = 0.0, vr = 0.0;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-#pragma unroll
-      for (int j = 0; j < K; ++j) {
-        const int p = i < j ? i : j, q = i < j ? j : i;
-        vN = me == i * K + j ? acc[p * K - p * (p - 1) / 2 + (q - p)] : vN;
-      }
-      vr = me == i ? acc[NP + i] : vr;
-    }
-    if (lane < K * K) N[(size_t)item * (K * K) + lane] = vN;
-    if (lane < K) r[(size_t)item * K + lane] = vr;
+    wave_sum_all(acc, n);
+    store_normal_by_lane<K>(acc, lane, N + (size_t)item * (K * K), r + (size_t)item * K);
     if (lane == 0 && hits) hits[item] = n;
   }
-}
-
-// the segment of sample t: s, and its clamped [lo, hi); -1 with lo = hi = 0 when t is in none
-__device__ __forceinline__ int find_segment(const int* __restrict__ bound, int S, int T, int t, int& lo, int& hi) {
-  int a = 0, b = S;  // the largest a in 0 .. S - 1 with bound[a] <= t, or 0
-  while (b - a > 1) {
-    const int m = (a + b) >> 1;
-    if (clamp_bound(bound[m], T) <= t)
-      a = m;
-    else
-      b = m;
-  }
-  lo = clamp_bound(bound[a], T), hi = clamp_bound(bound[a + 1], T);
-  if (t >= lo && t < hi) return a;
-  lo = hi = 0;
-  return -1;
 }
 
 // x and y may be the same buffer: a thread reads its samples before it writes them, and no other thread touches them
@@ -155,15 +111,8 @@ __global__ __launch_bounds__(kThreads) void segment_apply_kernel(const float* x,
     const long long row = tile / tiles_per_row;
     const int q = (int)(tile - row * tiles_per_row) * kTileSamples + kOwn * (int)threadIdx.x;
     if (q >= T) continue;
-    const float* const xr = x + (size_t)row * ld_x;
     float v[kOwn];
-    if ((wide & kWideX) && q + kOwn <= T) {
-      const float4 w = *reinterpret_cast<const float4*>(xr + q);
-      v[0] = w.x, v[1] = w.y, v[2] = w.z, v[3] = w.w;
-    } else {
-#pragma unroll
-      for (int k = 0; k < kOwn; ++k) v[k] = q + k < T ? xr[q + k] : 0.0f;
-    }
+    load_own<kOwn>(x + (size_t)row * ld_x, q, T, wide & kWideX, v);
     int s = -1, lo = 0, hi = 0;
 #pragma unroll
     for (int k = 0; k < kOwn; ++k) {
@@ -187,20 +136,13 @@ __global__ __launch_bounds__(kThreads) void segment_apply_kernel(const float* x,
       const float f = (float)sum;
       v[k] = sign < 0 ? v[k] - f : v[k] + f;
     }
-    float* const yr = y + (size_t)row * ld_y;
-    if ((wide & kWideY) && q + kOwn <= T) {
-      *reinterpret_cast<float4*>(yr + q) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < kOwn; ++k)
-        if (q + k < T) yr[q + k] = v[k];
-    }
+    store_own<kOwn>(y + (size_t)row * ld_y, q, T, wide & kWideY, v);
   }
 }
 
 // The frozen projector of a (row, segment), in place: r = sum P x (pass 1), a = A r, x -= (float)(sum a_i P_i) (pass 2).
-// Pass 1 is segment_normal_kernel's r, operation for operation (its kFlight loop, its selects, its butterfly), over the
-// unflagged samples (forward) or over all of them (transposed); pass 2 is segment_apply_kernel's expression on every
+// Pass 1 is segment_normal_kernel's r, operation for operation (its kFlight loop, its selects, the same rhs_add and
+// wave_sum_all), over the unflagged samples (forward) or over all of them (transposed); pass 2 is segment_apply_kernel's expression on every
 // sample (forward) or on the unflagged ones (transposed), each lane on the samples it read in pass 1: lo + lane,
 // lo + lane + 64, ..  Pass 2 reads its samples from global memory a second time: a segment is a few KiB that one wave
 // has just streamed, and nobody else writes it.  A pair that is not ok, or is empty, touches no sample.
@@ -243,20 +185,13 @@ __global__ __launch_bounds__(kThreads) void segment_project_kernel(float* x, siz
         const int k = k0 + e * kWave;
         const bool keep = fv[e] == 0;
         const double u = L > 1 ? (2.0 * (double)k - span) / span : 0.0;
-        double P[K], b[K];
+        double P[K];
         legendre<K>(u, P);
-#pragma unroll
-        for (int i = 0; i < K; ++i) b[i] = keep ? P[i] : 0.0;
         const double term = keep ? (double)xv[e] : 0.0;
-#pragma unroll
-        for (int i = 0; i < K; ++i) acc[i] = acc[i] + b[i] * term;
+        rhs_add<K>(acc, P, keep, term);
       }
     }
-#pragma unroll
-    for (int o = kWave / 2; o >= 1; o >>= 1) {
-#pragma unroll
-      for (int i = 0; i < K; ++i) acc[i] = acc[i] + __shfl_xor(acc[i], o, kWave);
-    }
+    wave_sum_all(acc);
     // every lane holds every r_i and forms every a_i: the same bits in all of them
     const double* const As = A + (size_t)item * (K * K);
     double a[K];
@@ -305,8 +240,6 @@ void launch_project(mrx_ctx* ctx, float* x, size_t ld_x, const uint8_t* flags, s
   hipLaunchKernelGGL(segment_project_kernel<K>, dim3(mrx_resident_blocks(ctx, (n_items + kWaves - 1) / kWaves)), dim3(kThreads), 0, ctx->stream, x, ld_x,
                      flags, ld_f, T, bound, S, A, ok, transpose, a, n_items);
 }
-
-bool aligned(const void* p, size_t ld_bytes, unsigned to) { return (((uintptr_t)p | (uintptr_t)ld_bytes) & (to - 1u)) == 0; }
 
 template <int K>
 void launch_normal(mrx_ctx* ctx, const float* x, size_t ld_x, const float* model, size_t ld_m, const uint8_t* flags, size_t ld_f, int T,
@@ -360,11 +293,10 @@ int mrx_tod_segment_apply(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, in
   MRX_REQUIRE(ctx, sign == 1 || sign == -1, "sign must be -1 or +1");
   MRX_REQUIRE(ctx, ld_x >= (size_t)T && ld_y >= (size_t)T, "ld_x or ld_y smaller than T");
   MRX_REQUIRE(ctx, d_y != d_x || ld_y == ld_x, "in place (d_y == d_x) needs ld_y == ld_x");
-  const int tiles_per_row = (T + kTileSamples - 1) / kTileSamples;
-  const long long n_tiles = (long long)D * tiles_per_row;
-  const int wide = (aligned(d_x, ld_x * 4, 16) ? kWideX : 0) | (aligned(d_y, ld_y * 4, 16) ? kWideY : 0);
-  hipLaunchKernelGGL(segment_apply_kernel, dim3(mrx_resident_blocks(ctx, n_tiles)), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, d_bound, S, K,
-                     d_a, sign, d_y, ld_y, wide, tiles_per_row, n_tiles);
+  const mrx_tile_grid_t g = mrx_tile_grid(ctx, D, T, kTileSamples);
+  const int wide = (mrx_aligned(d_x, ld_x * 4, 16) ? kWideX : 0) | (mrx_aligned(d_y, ld_y * 4, 16) ? kWideY : 0);
+  hipLaunchKernelGGL(segment_apply_kernel, dim3(g.blocks), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, d_bound, S, K, d_a, sign, d_y, ld_y, wide,
+                     g.tiles_per_row, g.n_tiles);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;
 }

@@ -5,8 +5,8 @@
 //             x[t] = (float)(((double)y[t] - a * (double)y[t - 1]) * r)
 // The file is built without FMA contraction: every operation above is one float64 rounding.
 //
-// The lag.  A workgroup owns a row and walks it in tiles of kTileSamples, thread o the four samples 4 o .. 4 o + 3 (one
-// 16-byte access where pointer and pitch allow it).  One step of the recurrence is the affine map s -> a s + g x; a run of
+// The lag.  A workgroup owns a row and walks it in the tiles of mrx_tod_dev.h, a thread its own four samples (q is 64 bits:
+// the last tile of a row may pass 2^31).  One step of the recurrence is the affine map s -> a s + g x; a run of
 // k steps is s -> a^k s + B with B the run's result from a zero state, so that with one pole a row the scan carries the
 // B alone and the powers a^4, a^8 .. a^256 are made once a row by squaring, in float64.  Per tile: the thread runs its
 // four samples from a zero state (B), the wave scans the 64 B by shuffles (step d: B += a^(4 d) B[lane - d]), the four
@@ -26,43 +26,20 @@
 // that tile; at the start of a chunk that is not the start of the row it is read from the input.  In place a chunk is
 // the whole row: a thread then reads nothing but its own samples, each before it writes it.
 #include "mrx_internal.h"
+#include "mrx_tod_dev.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
-constexpr int kWaves = kThreads / kWave;
-constexpr int kOwn = 4;  // consecutive samples of a thread
-constexpr int kTileSamples = kThreads * kOwn;
+using namespace mrx_tod;  // the 256-thread, four-sample tile, kWave
+
 constexpr int kScanSteps = 6;    // shuffle distances 1 .. 32
 constexpr int kChunkTiles = 16;  // tiles of a work item of the inverse out of place
 
 enum : int { kWideX = 1, kWideY = 2 };
 
 static_assert(kWave == 1 << kScanSteps && kOwn == 4, "64 lanes of four samples");
-
-// the thread's samples q .. q + 3 of a row; 0 past T
-__device__ __forceinline__ void load_own(const float* xr, long long q, int T, bool wide, float (&v)[kOwn]) {
-  if (wide && q + kOwn <= (long long)T) {
-    const float4 w = *reinterpret_cast<const float4*>(xr + q);
-    v[0] = w.x, v[1] = w.y, v[2] = w.z, v[3] = w.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < kOwn; ++k) v[k] = q + k < (long long)T ? xr[q + k] : 0.0f;
-  }
-}
-
-__device__ __forceinline__ void store_own(float* yr, long long q, int T, bool wide, const float (&v)[kOwn]) {
-  if (wide && q + kOwn <= (long long)T) {
-    *reinterpret_cast<float4*>(yr + q) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < kOwn; ++k)
-      if (q + k < (long long)T) yr[q + k] = v[k];
-  }
-}
 
 // x and y may be the same buffer (same pitch): a thread reads its samples before it writes them, and no other thread
 // touches them
@@ -81,8 +58,8 @@ __global__ __launch_bounds__(kThreads) void onepole_kernel(const float* x, size_
     if (x == y) return;
     for (int tile = 0; tile < n_tiles; ++tile) {
       const long long q = (long long)tile * kTileSamples + kOwn * o;
-      load_own(xr, q, T, wide_x, v);
-      store_own(yr, q, T, wide_y, v);
+      load_own<kOwn>(xr, q, T, wide_x, v);
+      store_own<kOwn>(yr, q, T, wide_y, v);
     }
     return;
   }
@@ -99,10 +76,10 @@ __global__ __launch_bounds__(kThreads) void onepole_kernel(const float* x, size_
 #pragma unroll
   for (int s = 0; s < kScanSteps; ++s) a_lane = ((lane >> s) & 1) ? a_lane * pw[s] : a_lane;
   double carry = 0.0;  // y64 of the last sample of the previous tile
-  load_own(xr, kOwn * o, T, wide_x, v);
+  load_own<kOwn>(xr, (long long)kOwn * o, T, wide_x, v);
   for (int tile = 0; tile < n_tiles; ++tile) {  // n_tiles follows from T: every thread of the workgroup makes every round
     const long long q = (long long)tile * kTileSamples + kOwn * o;
-    if (tile + 1 < n_tiles) load_own(xr, q + kTileSamples, T, wide_x, nv);  // in flight over this tile's scan
+    if (tile + 1 < n_tiles) load_own<kOwn>(xr, q + kTileSamples, T, wide_x, nv);  // in flight over this tile's scan
     const bool steady = init != 0 && q == 0;  // sample 0 has seen x[0] for ever: y64[0] = x[0]
     double gx[kOwn];
 #pragma unroll
@@ -136,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void onepole_kernel(const float* x, size_
       state = a * state + gx[k];
       out[k] = (float)state;
     }
-    store_own(yr, q, T, wide_y, out);
+    store_own<kOwn>(yr, q, T, wide_y, out);
 #pragma unroll
     for (int k = 0; k < kOwn; ++k) v[k] = nv[k];
   }
@@ -163,10 +140,10 @@ __global__ __launch_bounds__(kThreads) void onepole_inverse_kernel(const float* 
     // the sample in front of the chunk (tile_lo > 0: out of place, where nobody writes the input)
     float edge = tile_lo > 0 ? yr[(long long)tile_lo * kTileSamples - 1] : 0.0f;
     float v[kOwn], nv[kOwn] = {0.0f, 0.0f, 0.0f, 0.0f}, out[kOwn];
-    load_own(yr, (long long)tile_lo * kTileSamples + kOwn * o, T, wide_y, v);
+    load_own<kOwn>(yr, (long long)tile_lo * kTileSamples + kOwn * o, T, wide_y, v);
     for (int tile = tile_lo; tile < tile_hi; ++tile) {
       const long long q = (long long)tile * kTileSamples + kOwn * o;
-      if (tile + 1 < tile_hi) load_own(yr, q + kTileSamples, T, wide_y, nv);
+      if (tile + 1 < tile_hi) load_own<kOwn>(yr, q + kTileSamples, T, wide_y, nv);
       if (lagged) {
         float prev = __shfl_up(v[kOwn - 1], 1, kWave);
         if (lane == kWave - 1) wave_last[slot][wave] = v[kOwn - 1];
@@ -181,14 +158,12 @@ __global__ __launch_bounds__(kThreads) void onepole_inverse_kernel(const float* 
 #pragma unroll
         for (int k = 0; k < kOwn; ++k) out[k] = v[k];
       }
-      store_own(xr, q, T, wide_x, out);
+      store_own<kOwn>(xr, q, T, wide_x, out);
 #pragma unroll
       for (int k = 0; k < kOwn; ++k) v[k] = nv[k];
     }
   }
 }
-
-bool aligned(const void* p, size_t ld_bytes, unsigned to) { return (((uintptr_t)p | (uintptr_t)ld_bytes) & (to - 1u)) == 0; }
 
 // what both entries refuse; nullptr: nothing
 const char* refusal(const float* d_in, size_t ld_in, int D, int T, const double* d_a, int init, const float* d_out, size_t ld_out) {
@@ -209,7 +184,7 @@ int mrx_tod_onepole(mrx_ctx* ctx, const float* d_x, size_t ld_x, int D, int T, c
   if (!ctx) return MRX_ERR_INVALID;
   const char* const bad = refusal(d_x, ld_x, D, T, d_a, init, d_y, ld_y);
   MRX_REQUIRE(ctx, !bad, bad);
-  const int wide = (aligned(d_x, ld_x * 4, 16) ? kWideX : 0) | (aligned(d_y, ld_y * 4, 16) ? kWideY : 0);
+  const int wide = (mrx_aligned(d_x, ld_x * 4, 16) ? kWideX : 0) | (mrx_aligned(d_y, ld_y * 4, 16) ? kWideY : 0);
   hipLaunchKernelGGL(onepole_kernel, dim3((unsigned)D), dim3(kThreads), 0, ctx->stream, d_x, ld_x, T, d_a, init, d_y, ld_y, wide);
   MRX_CHECK_LAUNCH(ctx);
   return MRX_OK;
@@ -225,7 +200,7 @@ int mrx_tod_onepole_inverse(mrx_ctx* ctx, const float* d_y, size_t ld_y, int D, 
   const int chunks_per_row = (tiles_per_row + chunk_tiles - 1) / chunk_tiles;
   const long long n_items = (long long)D * chunks_per_row;
   const unsigned blocks = mrx_resident_blocks(ctx, n_items);  // as many as stay resident
-  const int wide = (aligned(d_y, ld_y * 4, 16) ? kWideY : 0) | (aligned(d_x, ld_x * 4, 16) ? kWideX : 0);
+  const int wide = (mrx_aligned(d_y, ld_y * 4, 16) ? kWideY : 0) | (mrx_aligned(d_x, ld_x * 4, 16) ? kWideX : 0);
   hipLaunchKernelGGL(onepole_inverse_kernel, dim3(blocks), dim3(kThreads), 0, ctx->stream, d_y, ld_y, T, d_a, init, d_x, ld_x, wide,
                      tiles_per_row, chunk_tiles, chunks_per_row, n_items);
   MRX_CHECK_LAUNCH(ctx);
