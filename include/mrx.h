@@ -1360,7 +1360,7 @@ int mrx_tod_gram(mrx_ctx* ctx, const float* d_x, size_t ld_x, const float* d_mod
 /* Common to the two entries below.  The pointing arguments are mrx_bin_map's, in its order (d_az, d_el [T] float32,
  * d_transform [T][9] float64 or NULL, d_dx, d_dy [D] float32), and the offsets (ox, oy) of detector d at sample t from the
  * frame's centre (center_phi, center_theta, radians) are the float32 numbers the binning computes for a map of that
- * centre: steps 1-3 of mrx_map.hip in the composed form, by the same code built with the same flags
+ * centre: steps 1-3 of mrx_map_sample.hip (mrx_map_pointing.h) in the composed form, by the same code built with the same flags
  * (mrx_map_pointing.h: sample_const, make_det_const, sample_offsets).  With MRX_OPT_POINTING_CHAIN set both return
  * MRX_ERR_UNSUPPORTED and launch nothing.
  *  d_src   [T][2] float32 or NULL: the source's offsets (src_x, src_y) from that centre at every sample (a planet that

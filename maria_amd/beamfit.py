@@ -2,7 +2,7 @@
 ``mrx_tod_beam_normal``).
 
 The offsets (ox, oy) of detector d at sample t from a frame's centre are the float32 numbers the binning computes
-(steps 1-3 of mrx_map.hip, composed form).  With the source at (src_x, src_y)(t) from that centre (None: at the centre)
+(steps 1-3 of the map operators, csrc/mrx_map_pointing.h, composed form).  With the source at (src_x, src_y)(t) from that centre (None: at the centre)
 and (u, v) = (ox - src_x, oy - src_y), the model of a row is
 
     K = 5 (circular):    (A, dx, dy, w, c)          q = w (u^2 + v^2)               w = 1 / sigma^2
@@ -354,7 +354,7 @@ def fit(x, pointing, center, init, flags, model=None, src=None, elliptical=False
 # ---- the reference pointing on the host, for tests and demonstrations -----------------------------------------------
 
 def reference_rotations(az, el, transform, center):
-    """G [T, 3, 2] float64 with dz = c @ G[t]: steps 1-3 of the map operators composed per sample (mrx_map.hip:
+    """G [T, 3, 2] float64 with dz = c @ G[t]: steps 1-3 of the map operators composed per sample (mrx_map_pointing.h:
     sample_const), in float64 numpy on the host.  ``transform`` [T, 3, 3] or None; ``center`` (phi, theta) radians."""
     az, el = np.asarray(az, np.float64), np.asarray(el, np.float64)
     a = el - np.pi / 2

@@ -1,7 +1,8 @@
-// The pointing of the map operators, steps 1-3 of mrx_map.hip (detector az/el, frame rotation, offsets from the map
-// centre), shared by the translation units that need a detector sample's offsets exactly as the binning computes them
-// (mrx_map.hip, mrx_beamfit.hip): the map's axes and arguments, the per-detector and per-sample constants and the offsets
-// themselves.  Both files are built with the same flags (no FMA contraction), so that the same inputs give the same bits.
+// The pointing of the map operators, steps 1-3 of mrx_map_sample.hip (detector az/el, frame rotation, offsets from the
+// map centre), shared by the translation units that need a detector sample's offsets exactly as the binning computes them
+// (mrx_map_sample.hip, mrx_map.hip, mrx_beamfit.hip): the map's axes and arguments (with the host's make_axis and
+// map_args), the per-detector and per-sample constants and the offsets themselves.  The three files are built with the
+// same flags (no FMA contraction), so that the same inputs give the same bits.
 #pragma once
 
 #include <cmath>
@@ -90,6 +91,38 @@ struct MapArgs {
   int coef_cap;        // coarse steps per row the table holds
 };
 
+// the map's grid and centre and the detectors' pointing, as every map kernel takes them (the callers check the sizes)
+inline MapArgs map_args(const mrx_sky_map* map, const float* d_az, const float* d_el, int T, const double* d_transform,
+                        const float* d_dx, const float* d_dy, const double* d_stokes_w, int D) {  // (host)
+  MapArgs g{};
+  g.eta = make_axis(map->n_eta, map->eta0, map->deta);
+  g.xi = make_axis(map->n_xi, map->xi0, map->dxi);
+  g.C = map->n_channels;
+  g.S = map->n_stokes;
+  g.n_eta = map->n_eta;
+  g.n_xi = map->n_xi;
+  g.cphi = (float)map->center_phi;
+  // exp(1j * (pi/2 - ctheta)) as jax evaluates it: the python float demoted to float32,
+  // then a complex64 exponential
+  const float ang = (float)(1.5707963267948966 - map->center_theta);
+  g.rot_re = (float)cos((double)ang);
+  g.rot_im = (float)sin((double)ang);
+  g.cos_cphi = cos(map->center_phi);
+  g.sin_cphi = sin(map->center_phi);
+  g.cos_ctheta = cos(map->center_theta);
+  g.sin_ctheta = sin(map->center_theta);
+  g.bilinear = map->bilinear;
+  g.az = d_az;
+  g.el = d_el;
+  g.transform = d_transform;
+  g.dx = d_dx;
+  g.dy = d_dy;
+  g.stokes_w = d_stokes_w;
+  g.D = D;
+  g.T = T;
+  return g;
+}
+
 // TOD.to("K_RJ") on the sampler's store (mrx_map_sample_krj): the arguments of mrx_tod_to_krj for the rows of this call
 struct MapKrj {
   const float* bore_el;     // [T]
@@ -123,21 +156,24 @@ struct SampleConst {
 
 __device__ __forceinline__ int sc_index(const MapArgs&, const SampleConst& sc) { return sc.s; }
 
+// The coarse step of the pwv series that time t falls in, 0 .. Ta - 2, and t's place u in it in float64 (below 0 or past
+// 1 where the series is extrapolated): linear interpolation of the coarse series (sim/atmosphere.py:30-37).  The one
+// statement of this arithmetic: the per-sample calibration (sample_const, the sampler's slot_record) and the interval form
+// (IntervalCal, mrx_map_sample.hip) must name the same step for the same time, and tests/test_gpu_map_cal.py restates it.
+__device__ __forceinline__ int coarse_step(const MapArgs& g, double t, double& u) {
+  int jj = (int)floor(fmin(fmax((t - g.ta0) * g.inv_dta, -1.0), 2.0e9));
+  jj = min(max(jj, 0), g.Ta - 2);
+  u = (t - (g.ta0 + (double)jj * g.dta)) * g.inv_dta;
+  return jj;
+}
+
 __device__ __forceinline__ void sample_const(const MapArgs& g, int s, bool chain, SampleConst& sc) {
   s = min(max(s, 0), g.T - 1);
   const float a = __fsub_rn(g.el[s], kHalfPiF);
   sc.ca = cosf(a);
   sc.sa = sinf(a);
   sc.az = g.az[s];
-  if (g.cal) {
-    // zenith-scaled pwv of the sample: linear interpolation of the coarse series
-    // (sim/atmosphere.py:30-37)
-    const double tt = g.t[s];
-    int jj = (int)floor(fmin(fmax((tt - g.ta0) * g.inv_dta, -1.0), 2.0e9));
-    jj = min(max(jj, 0), g.Ta - 2);
-    sc.jj = jj;
-    sc.u = (tt - (g.ta0 + (double)jj * g.dta)) * g.inv_dta;
-  }
+  if (g.cal) sc.jj = coarse_step(g, g.t[s], sc.u);  // zenith-scaled pwv of the sample
   if (!chain) {
     // Steps 1-3 are rotations of the unit vector c: xyz = c @ R(az, el), v = xyz @ M(t),
     // and phi_theta_to_offsets only needs two components of v in the frame of the map

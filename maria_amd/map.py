@@ -70,7 +70,7 @@ def collapse_temperature(table, axis_T, base_temperature):
 def steps_per_tile(t, dta, tile=1024):
     """``mrx_map_cal.steps_per_tile``: the most steps of a coarse series of step ``dta`` that ``tile`` consecutive samples
     (and the two either side) of the sample times ``t`` meet -- what sizes the LDS table of the map sampler's per-sample
-    calibration (csrc/mrx_map.hip, the interval form)."""
+    calibration (csrc/mrx_map_sample.hip, the interval form)."""
     t = np.asarray(t, float)
     if len(t) < 2:
         return 1

@@ -30,7 +30,7 @@ def det_vector_jac(dx, dy):
 
 
 def rotations(az, el, transform, center):
-    """G [T, 3, 2]: dz = c @ G[t], the rotation of steps 1-3 composed per sample in float64 (mrx_map.hip: sample_const).
+    """G [T, 3, 2]: dz = c @ G[t], the rotation of steps 1-3 composed per sample in float64 (mrx_map_pointing.h: sample_const).
     ``transform`` [T, 3, 3] or None; ``center`` (phi, theta) in radians."""
     az, el = np.asarray(az, np.float64), np.asarray(el, np.float64)
     a = el - HALF_PI

@@ -619,6 +619,43 @@ def test_map_entry_points_reject_bad_arguments(gpu_ctx):
                      None, 2, ptr(one64), ptr(one64))
 
 
+@pytest.mark.parametrize("D,groups", [(16384, 2), (32768, 4)])
+def test_several_row_groups_a_workgroup(gpu_ctx, D, groups):
+    """A workgroup of the sampler walks 2 or 4 groups of 16 rows on one tile's sample records once the grid is large enough
+    for it (4096 workgroups at that grouping: the launcher's rule, restated here).  T = 8192: rows from every group against
+    the oracle within test_map_sampling_matches_oracle's bound, and 2048 rows in the middle equal to a launch of those
+    rows alone (one group a workgroup) in every bit."""
+    from maria_amd import map as mmap
+    from maria_amd import synthetic
+    from oracle import hotpath, mapsample
+
+    T = 8192
+    g = 4
+    while g > 1 and -(-T // 1024) * -(-D // (16 * g)) < 16 * 256:
+        g //= 2
+    assert g == groups and -(-T // 1024) * -(-2048 // 32) < 16 * 256  # (and the 2048 rows alone: one group)
+    rng = np.random.default_rng(D)
+    t = 1.7e9 + np.arange(T) / 400.0
+    az, el = synthetic.daisy_scan(t)
+    az, el = az.astype(np.float32), el.astype(np.float32)
+    off = synthetic.hex_pack(D, np.radians(1.0))
+    centre = _centre(az, el, None)
+    eta, xi = np.linspace(0.03, -0.03, 9), np.linspace(-0.03, 0.03, 11)
+    values = _blob_map(1, 1, 9, 11, eta, xi, rng)
+    w = np.ones((D, 1)) * 0.5
+    scal = [2.1e10]
+    got = mmap.sample_map(gpu_ctx, values, eta, xi, centre, az, el, off, w, cal_scalars=scal)
+    lo = D // 2 - 1000  # (no multiple of a workgroup's rows)
+    part = mmap.sample_map(gpu_ctx, values, eta, xi, centre, az, el, off[lo : lo + 2048], w[:2048], cal_scalars=scal)
+    assert bool((got[lo : lo + 2048] == part).all())
+    rows = np.unique(np.r_[np.arange(0, D, 1021), np.arange(16 * groups), D - 1 - np.arange(16 * groups)])  # every group's place
+    az_d, el_d = hotpath.broadcast(off[rows], az, el)
+    ref = mapsample.sample_maps(az_d, el_d, t, None, None, eta, xi, centre, values, w[rows], cal_scalars=scal)
+    sub = got[rows].cpu().numpy()
+    bound = _rounding_bound(values, eta, xi, 0.5, 1e12 * mapsample.K_B * sum(scal))
+    assert np.abs(sub - ref).max() <= bound and bound <= 3e-4 * np.abs(ref).max()
+
+
 @pytest.mark.parametrize("D,T", [(1, 1), (1, 3), (3, 5), (17, 1025)])
 def test_tiny_and_ragged_sizes(gpu_ctx, D, T):
     """One detector, one sample, lengths below the 4-sample group and one past the tile:

@@ -1,5 +1,5 @@
 """GPU tests of the map sampler's per-sample calibration (mrx_map_sample with calibration tables) where its interval form
-(csrc/mrx_map.hip: one parabola record per row and coarse step of a tile) meets its edges: a tile whose end halo sits
+(csrc/mrx_map_sample.hip: one parabola record per row and coarse step of a tile) meets its edges: a tile whose end halo sits
 on a coarse-step boundary, the halos at the run's two ends, and a tile that meets more coarse steps than the form's
 table holds.  Every sample is compared with the oracle (oracle/mapsample.py) and with the kernel's own per-sample form."""
 
@@ -18,7 +18,7 @@ _D = 37  # the last 16-row group ragged
 def _interval_hits(t, ta0, dta, Ta):
     """The full tiles whose end halo (one sample after the tile's last; the run's last sample's successor when the
     index is clamped) picks record n_int of the interval form, one past the n_int records the tile builds: a numpy
-    restatement of step_of, v0, dvt, lim and the halo's choice in mrx_map.hip (float64 steps, float32 v through an
+    restatement of step_of, v0, dvt, lim and the halo's choice in mrx_map_sample.hip (float64 steps, float32 v through an
     fma) as they stood before the choice was clamped.  It shows that a case exercises the edge; it is not the reference."""
     t = np.asarray(t, np.float64)
     T, inv_dta, f32 = len(t), 1.0 / dta, np.float32
@@ -81,8 +81,9 @@ _CONTROLS = ["0.0/400/0.1", "12.5/400/0.1", "1.7e9/400/0.1", "12.5/1000/0.1", "1
 _SAME_FORM_BOUND = 2.5e-5
 
 
-def _sample(ctx, name, C, steps_per_tile=None, seed=0):
-    """The case's TOD through mrx_map_sample with calibration tables, and what the oracle needs to restate it."""
+def _sample(ctx, name, C, steps_per_tile=None, seed=0, off_tables=None):
+    """The case's TOD through mrx_map_sample with calibration tables, and what the oracle needs to restate it.
+    ``off_tables``: a (row, knot) of the coarse pwv put beyond the tables' pwv axis."""
     from maria_amd import map as mmap
     from maria_amd import synthetic
 
@@ -102,6 +103,8 @@ def _sample(ctx, name, C, steps_per_tile=None, seed=0):
     tabs = np.stack([(1.5e10 + 4e9 * c) * np.exp(-(0.05 + 0.03 * c + 0.04 * axis_pwv[:, None]) / np.sin(axis_el)[None, :])
                      for c in range(C)]).astype(np.float32)
     coarse = 1.2 + 0.3 * np.cumsum(rng.normal(0, 0.05, (_D, len(ta))), axis=1)  # a random walk per detector
+    if off_tables is not None:
+        coarse[off_tables] = 7.5
     got = mmap.sample_map(ctx, values, eta, xi, centre, az, el, off, w, cal_tables=tabs, cal_axis_pwv=axis_pwv, cal_axis_el=axis_el,
                           coarse_pwv=coarse.T, ta0=ta0, dta=dta, t=t, steps_per_tile=steps_per_tile).cpu().numpy()
     return got, dict(t=t, ta=ta, ta0=ta0, dta=dta, az=az, el=el, off=off, centre=centre, eta=eta, xi=xi, values=values, w=w,
@@ -162,6 +165,50 @@ def test_interval_calibration_on_unaligned_coarse_grids(gpu_ctx, name, C):
     assert e_b <= _SAME_FORM_BOUND, (e_b, np.unravel_index(np.argmax(np.abs(got - per_sample) / row), got.shape))
     assert np.abs(got - ref).max() <= bound_a, (float(np.abs(got - ref).max() / np.abs(ref).max()))
     assert np.abs(per_sample - ref).max() <= bound_a
+
+
+def test_a_row_with_a_knot_off_the_tables_takes_the_per_sample_form(gpu_ctx):
+    """One coarse pwv sample of one row lies beyond the tables (NaN: jax's fill).  In the tiles that meet that knot the
+    row takes the per-sample form -- its values there are the per-sample call's (steps_per_tile = 1) bit for bit, NaN for
+    NaN -- while the tile's other rows stay on the interval form (they differ from the per-sample call's in some bit).
+    The NaNs stand where the oracle has them; every other sample within the neighbouring test's bounds."""
+    from oracle import mapsample
+
+    name, C, row = "12.5/400/0.1", 2, 21
+    t, ta, ta0, dta = _case(name)
+    knot = int(round((t[3 * 1024 + 500] - ta0) / dta))  # in the middle of the fourth tile
+    got, k = _sample(gpu_ctx, name, C, off_tables=(row, knot))
+    per_sample, _ = _sample(gpu_ctx, name, C, steps_per_tile=1, off_tables=(row, knot))
+    ref = _oracle(k)
+    nan = np.isnan(ref)
+    assert nan[row].any() and not np.delete(nan, row, axis=0).any() and not nan[row, : 3 * 1024].any() and not nan[row, 4 * 1024 :].any()
+    assert np.array_equal(np.isnan(got), nan) and np.array_equal(np.isnan(per_sample), nan)
+    tile = slice(3 * 1024, 4 * 1024)
+    assert np.array_equal(got[row, tile], per_sample[row, tile], equal_nan=True), "the row took the per-sample form"
+    others = np.delete(np.arange(_D), row)
+    assert all(not np.array_equal(got[d, tile], per_sample[d, tile]) for d in others), "the tile's other rows: the interval form"
+    assert not np.array_equal(got[row, :1024], per_sample[row, :1024]), "the row in a tile without the knot: the interval form"
+    ok = ~nan
+    rowmax = np.abs(np.where(ok, per_sample, 0.0)).max(axis=1, keepdims=True)
+    bound = _rounding_bound(k["values"], k["eta"], k["xi"], 0.5, 1e12 * mapsample.K_B * sum(tab.max() for tab in k["tabs"]))
+    bound_a = bound + 2e-6 * np.abs(ref[ok]).max()
+    e_b = float((np.abs(got - per_sample) / rowmax)[ok].max())
+    assert e_b <= _SAME_FORM_BOUND, e_b
+    assert np.abs(got - ref)[ok].max() <= bound_a and np.abs(per_sample - ref)[ok].max() <= bound_a
+
+
+def test_more_channels_than_the_interval_table_holds_take_the_per_sample_form(gpu_ctx):
+    """Five channels with calibration tables under the composed pointing: the interval table is built for four, so the
+    launcher reserves none and every row takes the per-sample form -- the default call equals the steps_per_tile = 1 call
+    (which no table fits either) in every bit -- and the field is the oracle's within the neighbouring test's bound."""
+    from oracle import mapsample
+
+    got, per_sample, ref, k = _measure(gpu_ctx, "12.5/400/0.1", 5)
+    assert np.isfinite(ref).all() and np.isfinite(got).all()
+    assert np.array_equal(got, per_sample), "no interval table: the per-sample form ran"
+    bound = _rounding_bound(k["values"], k["eta"], k["xi"], 0.5, 1e12 * mapsample.K_B * sum(tab.max() for tab in k["tabs"]))
+    assert bound <= 3e-5 * np.abs(ref).max()
+    assert np.abs(got - ref).max() <= bound + 2e-6 * np.abs(ref).max(), float(np.abs(got - ref).max() / np.abs(ref).max())
 
 
 def test_krj_sampling_with_more_steps_a_tile_than_the_interval_table(gpu_ctx):

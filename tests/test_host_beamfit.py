@@ -300,3 +300,6 @@ def test_entries_are_declared_and_bound():
     assert "mrx_beamfit.hip" in makefile and "mrx_map_pointing.h" in makefile
     flags = dict(re.findall(r"^EXTRA_(\w+) := (.*)$", makefile, flags=re.M))
     assert flags["mrx_beamfit"] in ("$(EXTRA_mrx_map)", flags["mrx_map"])  # the binning's bits need the binning's flags
+    # ... and so does the sampler, a translation unit of its own on the same pointing code
+    assert "mrx_map_sample.hip" in makefile
+    assert flags["mrx_map_sample"] in ("$(EXTRA_mrx_map)", flags["mrx_map"])
