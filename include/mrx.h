@@ -543,6 +543,34 @@ int mrx_screen_generate_3d(mrx_ctx* ctx, uint64_t seed, uint32_t stream, int nh,
                            const mrx_screen_desc* planes, int n_planes, float* d_work,
                            size_t work_floats, const float* d_amp);
 
+/* A flat-sky CMB patch: T, Q, U on a periodic ny x nx domain (powers of two in [64, 8192]) of square pixels of
+ * `res` radians, Lx = nx res, Ly = ny res,
+ *     m_X(x_j) = sum_k a_X(k) exp(i k.x_j),   k = 2 pi (fx / Lx, fy / Ly), signed integer fx, fy,   l = |k|.
+ * Per cell of the half plane kx = 0 .. nx/2, with g1, g2, g3 independent unit complex Gaussians (E |g|^2 = 1):
+ *     T = cT(l) g1,   E = cTE(l) g1 + cE(l) g2,   B = cB(l) g3,
+ *     Q = E cos 2phi - B sin 2phi,   U = E sin 2phi + B cos 2phi,   phi = atan2(ky, kx)
+ * (y is the row axis of the output, x its column axis).  `table` is a HOST array [n_ell][4] float32, row = integer
+ * l from 0, columns cT = sqrt C_TT, cTE = C_TE / sqrt C_TT, cE = sqrt max(C_EE - C_TE^2 / C_TT, 0), cB = sqrt C_BB,
+ * each times 1 / sqrt(Lx Ly) so that <|a_T|^2> = C_TT / (Lx Ly) ...: the fields come out in the units of sqrt C_l
+ * (K_CMB).  The four coefficients are interpolated linearly in l (float64 l and weight, float32 coefficients);
+ * cells with l beyond the last row get zero, as does l = 0.
+ * Nyquist lines: the cells with |fx| = nx/2 or |fy| = ny/2 are zero in all three fields.  sin 2phi is odd there,
+ * so a Hermitian Q / U pair does not exist for them, and power left in them mixes E into B.
+ * The self-mirrored column kx = 0 holds independent cells for every ky and is made Hermitian by pass 1 as the 3-D
+ * generator's is, S' = (S[ky] + conj S[-ky]) / sqrt 2, alike in T, Q and U: there cos 2phi = -1 and sin 2phi = 0,
+ * so Q' = -E', U' = -B' and the T-E covariance is kept.
+ * Draws: cell pair (ky = iy, iy + ny/2), iy < ny/2, of column kx uses the three Philox counters
+ * (kx, iy, stream, 0x434d4200 | d), d = 0, 1, 2, key = seed: words (0,1) are the Box-Muller pair of g_{d+1} / sqrt 2
+ * for cell iy, words (2,3) that for cell iy + ny/2.  Counter word 3 is 0 for the 2-D screens, 0x33440000 for the
+ * 3-D ones and an ASCII tag for each noise series: no counter coincides.
+ * Then the two passes of mrx_screen_generate_batch per field (normalisation 1).  `fields[3]` gives the output block of
+ * T, Q and U as mrx_screen_generate_3d's `planes` do (d_out, out_ny, out_nx, ld_out: the top-left block of the domain;
+ * the other fields are ignored).  d_work: mrx_cmb_work_floats floats (the three half spectra, the normalisation, the
+ * table's device copy), 16-byte aligned. */
+int mrx_cmb_work_floats(int ny, int nx, int n_ell, size_t* floats);
+int mrx_cmb_generate(mrx_ctx* ctx, uint64_t seed, uint32_t stream, int ny, int nx, double res, const float* table,
+                     int n_ell, const mrx_screen_desc* fields, float* d_work, size_t work_floats);
+
 /* Covariance-matched amplitudes (circulant embedding) for the generators above.  The power law is
  * the continuous transform of the Matern covariance cut at the grid's Nyquist wavenumber; for rough
  * fields (nu = 1/3 in three dimensions, atmosphere/atmosphere.py:249) most of the one-pixel structure

@@ -956,6 +956,68 @@ int psd_sum_slot(mrx_ctx* ctx, int ny, int nx, double dy, double dx, double r0,
   return MRX_OK;
 }
 
+// ---- CMB patch (mrx_cmb_generate): correlated T, E, B modes from a C_ell table, Q / U in k space ----
+// Pass 0 in front of the two screen passes, as screen3d_fft_h is: one thread per cell pair (iy, iy + ny/2) of a
+// column kx = ix <= nx/2 draws three unit complex normals a cell, forms T = cT g1, E = cTE g1 + cE g2, B = cB g3
+// from the table's four coefficients at l = |k| (linear in l between the integer rows, zero beyond the last row and
+// on both Nyquist lines), rotates (E, B) by 2 phi = 2 atan2(ky, kx) into (Q, U), and writes the three half spectra
+// as plane[f][kx][ky], the layout pass 1 reads.  l, the interpolation weight and cos / sin 2 phi are float64 (a
+// set-up kernel: once per Simulation), the coefficients and the products float32.
+constexpr uint32_t kTagCmb = 0x434d4200u;  // 'CMB\0': counter word 3 of the CMB draws, | draw index 0 .. 2
+constexpr size_t kCmbHeader = 4;           // floats between the planes and the table: the float64 normalisation 1, padding
+
+struct CmbArgs {
+  float2* work[3];     // half spectra of T, Q, U: [nx/2 + 1][ny + kPitchPad] each
+  const float4* table; // [n_ell] rows (cT, cTE, cE, cB), row = integer l
+  int n_ell;
+  double res;          // pixel size (radians)
+  uint32_t stream;
+};
+
+__device__ __forceinline__ void cmb_cell(const CmbArgs& g, double kx, double ky, bool nyquist, float2 g1, float2 g2,
+                                         float2 g3, float2 (&tqu)[3]) {
+  const double k2 = kx * kx + ky * ky, ell = sqrt(k2);
+  tqu[0] = tqu[1] = tqu[2] = make_float2(0.0f, 0.0f);
+  if (nyquist || !(k2 > 0.0) || ell > (double)(g.n_ell - 1)) return;
+  const int l0 = min((int)ell, g.n_ell - 2);
+  const float w = (float)(ell - (double)l0);
+  const float4 a = g.table[l0], b = g.table[l0 + 1];
+  const float cT = fmaf(w, b.x - a.x, a.x), cTE = fmaf(w, b.y - a.y, a.y);
+  const float cE = fmaf(w, b.z - a.z, a.z), cB = fmaf(w, b.w - a.w, a.w);
+  const float c2 = (float)((kx * kx - ky * ky) / k2), s2 = (float)(2.0 * kx * ky / k2);
+  constexpr float kRoot = 0.70710678118654752f;  // unit complex normals: E |g|^2 = 1
+  g1.x *= kRoot; g1.y *= kRoot; g2.x *= kRoot; g2.y *= kRoot; g3.x *= kRoot; g3.y *= kRoot;
+  const float2 E = make_float2(cTE * g1.x + cE * g2.x, cTE * g1.y + cE * g2.y);
+  const float2 B = make_float2(cB * g3.x, cB * g3.y);
+  tqu[0] = make_float2(cT * g1.x, cT * g1.y);
+  tqu[1] = make_float2(E.x * c2 - B.x * s2, E.y * c2 - B.y * s2);
+  tqu[2] = make_float2(E.x * s2 + B.x * c2, E.y * s2 + B.y * c2);
+}
+
+__global__ __launch_bounds__(kBlock) void cmb_modes_kernel(const CmbArgs g, int ny, int nx, uint32_t key0, uint32_t key1) {
+  const int half = ny >> 1;
+  const int e = blockIdx.x * kBlock + threadIdx.x;  // (nx/2 + 1) ny/2 <= 4097 * 4096 pairs
+  if (e >= (nx / 2 + 1) * half) return;
+  const int ix = e / half, iy = e - ix * half;
+  U4 rnd[3];
+#pragma unroll
+  for (uint32_t d = 0; d < 3; ++d) rnd[d] = philox4x32_10(U4{(uint32_t)ix, (uint32_t)iy, g.stream, kTagCmb | d}, key0, key1);
+  const double kx = wavenumber(ix, nx, g.res);
+  const bool nyq_x = 2 * ix == nx;
+  float2 lo[3], hi[3];
+  // words (x, y) -> cell iy, (z, w) -> cell iy + ny/2 (iy = 0 there is the Nyquist line of ky)
+  cmb_cell(g, kx, wavenumber(iy, ny, g.res), nyq_x, box_muller(rnd[0].x, rnd[0].y), box_muller(rnd[1].x, rnd[1].y),
+           box_muller(rnd[2].x, rnd[2].y), lo);
+  cmb_cell(g, kx, wavenumber(iy + half, ny, g.res), nyq_x || iy == 0, box_muller(rnd[0].z, rnd[0].w),
+           box_muller(rnd[1].z, rnd[1].w), box_muller(rnd[2].z, rnd[2].w), hi);
+  const size_t at = (size_t)ix * (ny + kPitchPad) + iy;
+#pragma unroll
+  for (int f = 0; f < 3; ++f) {
+    g.work[f][at] = lo[f];
+    g.work[f][at + half] = hi[f];
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1224,6 +1286,59 @@ int mrx_screen_generate_3d(mrx_ctx* ctx, uint64_t seed, uint32_t stream, int nh,
                      (uint32_t)seed, (uint32_t)(seed >> 32));
   MRX_CHECK_LAUNCH(ctx);
   return run_screen_passes(ctx, seed, ny, nx, planes, n_planes, d_work, true, d_sum);
+}
+
+int mrx_cmb_work_floats(int ny, int nx, int n_ell, size_t* floats) {
+  if (!floats || ny <= 0 || nx <= 0 || n_ell < 0) return MRX_ERR_INVALID;
+  size_t planes = 0;
+  mrx_screen_work_floats(ny, nx, 3, &planes);
+  *floats = planes + kCmbHeader + 4 * (size_t)n_ell;  // + the normalisation, + the device copy of the table
+  return MRX_OK;
+}
+
+int mrx_cmb_generate(mrx_ctx* ctx, uint64_t seed, uint32_t stream, int ny, int nx, double res, const float* table,
+                     int n_ell, const mrx_screen_desc* fields, float* d_work, size_t work_floats) {
+  MRX_ENTER(ctx);
+  if (!ctx) return MRX_ERR_INVALID;
+  MRX_REQUIRE(ctx, table && fields && d_work, "null pointer");
+  MRX_REQUIRE(ctx, res > 0, "the pixel size must be positive");
+  MRX_REQUIRE(ctx, n_ell >= 2 && n_ell <= (1 << 24), "the coefficient table needs 2 .. 2^24 rows");
+  const int ly = ilog2_exact(ny), lx = ilog2_exact(nx);
+  if (ly < 0 || lx < 0 || ny < 64 || nx < 64 || ny > 8192 || nx > 8192)
+    return mrx_fail(ctx, MRX_ERR_UNSUPPORTED, "CMB domain sides must be powers of two in [64, 8192] (got %d x %d)", ny, nx);
+  size_t need = 0, plane_floats = 0;
+  mrx_cmb_work_floats(ny, nx, n_ell, &need);
+  mrx_screen_work_floats(ny, nx, 3, &plane_floats);
+  MRX_REQUIRE(ctx, work_floats >= need, "work buffer smaller than mrx_cmb_work_floats()");
+  MRX_REQUIRE(ctx, (reinterpret_cast<uintptr_t>(d_work) & 15u) == 0, "d_work must be 16-byte aligned");
+  // behind the three planes (a multiple of four floats): the passes' normalisation -- the table carries the
+  // absolute units, so 1 -- and the table
+  static const double kOne = 1.0;
+  double* d_one = reinterpret_cast<double*>(d_work + plane_floats);
+  float* d_table = d_work + plane_floats + kCmbHeader;
+  MRX_HIP(ctx, hipMemcpyAsync(d_one, &kOne, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  MRX_HIP(ctx, hipMemcpyAsync(d_table, table, 4 * sizeof(float) * (size_t)n_ell, hipMemcpyHostToDevice, ctx->stream));
+  MRX_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller's host table may go away
+  CmbArgs g{};
+  mrx_screen_desc blocks[3] = {};  // the output blocks alone: no beam, no spectrum of the screens'
+  for (int f = 0; f < 3; ++f) {
+    g.work[f] = reinterpret_cast<float2*>(d_work) + (size_t)f * (plane_floats / 6);
+    MRX_REQUIRE(ctx, fields[f].d_out != nullptr, "null output pointer");
+    MRX_REQUIRE(ctx, fields[f].out_ny <= ny && fields[f].out_nx <= nx, "written block larger than the FFT domain");
+    blocks[f].d_out = fields[f].d_out;
+    blocks[f].out_ny = fields[f].out_ny;
+    blocks[f].out_nx = fields[f].out_nx;
+    blocks[f].ld_out = fields[f].ld_out;
+  }
+  g.table = reinterpret_cast<const float4*>(d_table);
+  g.n_ell = n_ell;
+  g.res = res;
+  g.stream = stream;
+  const int pairs = (nx / 2 + 1) * (ny / 2);
+  hipLaunchKernelGGL(cmb_modes_kernel, dim3(mrx_ceil_div(pairs, kBlock)), dim3(kBlock), 0, ctx->stream, g, ny, nx,
+                     (uint32_t)seed, (uint32_t)(seed >> 32));
+  MRX_CHECK_LAUNCH(ctx);
+  return run_screen_passes(ctx, seed, ny, nx, blocks, 3, d_work, true, d_one);
 }
 
 int mrx_screen_amp_floats(int nh, int ny, int nx, int n_radial, size_t* table_floats, size_t* work_floats) {

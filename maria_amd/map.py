@@ -166,13 +166,14 @@ class ProjectionMap:
     ``resolution`` and ``center`` in degrees (``degrees=True``) or radians; ``frame`` "ra/dec"
     or "az/el".  Row i of the data sits at eta[i], eta ascending as given -- the reference then
     flips axis and data together (``apply_parity``), which changes nothing for sampling and is
-    mirrored here so that the device sees the same descending axis.  Units other than K_RJ, the
+    mirrored here so that the device sees the same descending axis.  ``units="K_CMB"``: thermodynamic
+    temperature, sampled through the Planck derivative in each band (``cmb.kcmb_weight``).  Other units, the
     time dimension, FITS/HDF input and plotting stay with maria's front end."""
 
     def __init__(self, data, nu=None, stokes=None, width=None, height=None, resolution=None, center=(0.0, 0.0),
                  frame="ra/dec", degrees=True, units="K_RJ"):
-        if units != "K_RJ":
-            raise NotImplementedError("maps are sampled in K_RJ; other map units go through maria's calibration graph")
+        if units not in ("K_RJ", "K_CMB"):
+            raise NotImplementedError("maps are sampled in K_RJ or K_CMB; other map units go through maria's calibration graph")
         if frame not in ("ra/dec", "az/el"):
             raise NotImplementedError(f"frame '{frame}': only 'ra/dec' and 'az/el' are built")
         data = np.asarray(data, np.float32)

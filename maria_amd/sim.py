@@ -3,8 +3,8 @@
 Mirrors ``maria.sim.Simulation`` (sim/simulation.py:66-272) and the atmosphere
 mixin (sim/atmosphere.py:24-84) for what BASELINE.json's north star covers:
 ``Simulation(instrument, plans, site, atmosphere="2d", atmosphere_kwargs=...)``
-and ``.run(units)`` returning one ``TOD`` per plan.  The CMB, map and noise mixins
-and unit conversions other than pW are follow-on rows and say so.
+and ``.run(units)`` returning one ``TOD`` per plan, with the map, CMB and noise mixins
+(SURVEY 8(f)); units other than pW and K_RJ are not built and say so.
 """
 
 from __future__ import annotations
@@ -122,7 +122,12 @@ class Simulation:
         cross-detector term), so a shard's TOD equals the same rows of the unsharded run.
         ``hwp``: a maria_amd.hwp.HWP, a continuously rotating ideal half-wave plate in front of the detectors: the
         ``map`` field becomes S_I + S_c cos 4 chi + S_s sin 4 chi (atmosphere and noise are not modulated),
-        and ``TOD.demodulate`` takes it apart again.  None: no plate, and the bits of every run are what they were."""
+        and ``TOD.demodulate`` takes it apart again.  None: no plate, and the bits of every run are what they were.
+        ``cmb``: a maria_amd.cmb.CMB (any ``ProjectionMap`` with ``units="K_CMB"``) or ``"generate"`` -- then
+        ``cmb_kwargs`` holds ``resolution`` (degrees a pixel; required), ``spectrum`` (default ``cmb.toy_spectrum()``),
+        ``seed`` (required in a sharded run), and optionally ``center`` / ``width`` / ``frame`` (default: one patch around
+        the pointing of all plans).  The field is ``tod.data["cmb"]``, sampled through the Planck derivative in each band,
+        beside ``"map"`` and on all of its routes, the plate included.  None: no such field, the same bits."""
         if hwp is not None:
             from .hwp import HWP
 
@@ -130,7 +135,17 @@ class Simulation:
                 raise TypeError("'hwp' must be a maria_amd.hwp.HWP")
         self.hwp = hwp
         if cmb is not None:
-            raise NotImplementedError("the CMB mixin is a follow-on row (SURVEY 8(f))")
+            from .map import ProjectionMap
+
+            if isinstance(cmb, str):
+                if cmb != "generate":
+                    raise NotImplementedError("reading a CMB map from a file stays with maria's io; pass a maria_amd.cmb.CMB or 'generate'")
+                if cmb_kwargs.get("resolution") is None:
+                    raise NotImplementedError("cmb='generate' needs cmb_kwargs['resolution'] (degrees a pixel): choosing the "
+                                              "pixel size from the beams is not built")
+            elif not isinstance(cmb, ProjectionMap) or cmb.units != "K_CMB":
+                raise TypeError("'cmb' must be a maria_amd.cmb.CMB, a ProjectionMap with units='K_CMB', or 'generate'")
+        self.cmb, self.cmb_kwargs = cmb, dict(cmb_kwargs)
         if isinstance(map, str):
             raise NotImplementedError("reading a map from a file stays with maria's io; pass a maria_amd.map.ProjectionMap")
         if map is not None:
@@ -171,6 +186,8 @@ class Simulation:
                 raise ValueError("a sharded run needs an explicit noise_seed: the correlated noise modes are common to all shards")
             if gain_seed is None and any(getattr(b, "gain_error", 0.0) for b in bands):
                 raise ValueError("a sharded run needs an explicit gain_seed: every rank draws the whole gain vector and keeps its rows")
+            if isinstance(cmb, str) and self.cmb_kwargs.get("seed") is None:
+                raise ValueError("a sharded run needs an explicit cmb_kwargs['seed']: every rank draws the one sky and samples its rows")
         self._gain_rng = np.random.default_rng(gain_seed)
         self.noise_kwargs = dict(noise_kwargs)
         self._noise_seed = int(noise_seed if noise_seed is not None else np.random.SeedSequence().entropy % (1 << 62))
@@ -182,9 +199,46 @@ class Simulation:
             if hasattr(obs, "atmosphere"):
                 # only the map mixin reads the coarse pwv (sim/map.py:117-135): without it the sampler and
                 # the TOD writer run pipelined in one call and the pwv is made if somebody asks for it
-                obs.atmosphere.keep_pwv = self.map is not None
+                obs.atmosphere.keep_pwv = self.map is not None or self.cmb is not None
                 obs.atmosphere.initialize(obs)
             self.obs_list.append(obs)
+        if isinstance(self.cmb, str):
+            self.cmb = self._generate_cmb()
+
+    def _generate_cmb(self):
+        """``cmb="generate"``: one patch for all plans, drawn on this Simulation's device.  Without ``center`` /
+        ``width`` in ``cmb_kwargs`` it is centred on the mean boresight direction in the map's frame and reaches the
+        farthest boresight sample + the focal plane's radius + 3 beam FWHM (+ a pixel) on every side: the map offsets
+        are angular distances from the centre along the tangent plane's directions, so no sample falls outside."""
+        from .cmb import CMB
+        from .instrument import compute_angular_fwhm
+
+        kw = dict(self.cmb_kwargs)
+        frame = kw.pop("frame", "ra/dec")
+        resolution = float(kw.pop("resolution"))
+        center, width = kw.pop("center", None), kw.pop("width", None)
+        if center is None or width is None:
+            vecs = []
+            for obs in self.obs_list:
+                az, el = obs.boresight._baz, obs.boresight._bel
+                v = np.stack([np.cos(az) * np.cos(el), np.sin(az) * np.cos(el), np.sin(el)], axis=-1)
+                if frame == "ra/dec":
+                    v = np.einsum("ti,tij->tj", v, sky_transform_stack(obs.coords.t, obs.site.latitude, obs.site.longitude))
+                vecs.append(v)
+            v = np.concatenate(vecs)
+            if center is None:
+                c = v.mean(axis=0)
+                c /= np.linalg.norm(c)
+                center = (float(np.degrees(np.arctan2(c[1], c[0]) % (2 * np.pi))), float(np.degrees(np.arcsin(c[2]))))
+            if width is None:
+                cphi, cth = np.radians(center[0]), np.radians(center[1])
+                c = np.array([np.cos(cphi) * np.cos(cth), np.sin(cphi) * np.cos(cth), np.sin(cth)])
+                reach = float(np.arccos(np.clip(v @ c, -1.0, 1.0)).max())
+                dets = self.instrument.dets
+                fwhm = max(float(compute_angular_fwhm(fwhm_0=dets.primary_size.mean(), z=np.inf, nu=b.center)) for b in dets.bands)
+                half = reach + float(np.hypot(*np.asarray(dets.offsets, float).T).max()) + 3.0 * fwhm
+                width = float(np.degrees(2.0 * half)) + 2.0 * resolution
+        return CMB.generate(center=center, width=width, resolution=resolution, frame=frame, device=self.device, **kw)
 
     def _rows(self, n_det):
         """[lo, hi) of this process's detector rows (all of them without a shard)."""
@@ -284,17 +338,23 @@ class Simulation:
         ctx.set_stream(torch.cuda.current_stream(device))
         return ctx, device
 
-    def _sample_maps(self, obs, rows=None, krj=None, gain=None, stokes_rows=None):
+    def _sample_maps(self, obs, rows=None, krj=None, gain=None, stokes_rows=None, sky=None):
         """sim/map.py:76-172 on the device: one ``mrx_map_sample`` per band, [D, T] pW
         (``rows = (lo, hi)``: only this shard's detector rows).  ``krj`` (``DevicePath.krj_row_tables()``): the field in
         K_RJ instead, ``gain`` [D] multiplied in, both on the sampler's own store (``mrx_map_sample_krj``: the bits of
         the pW field times the gain, converted by ``DevicePath.to_krj``, without the two passes over the field).
-        ``stokes_rows``: [rows, 4] (I, Q, U, V) weights of this call in place of the detectors' cached Mueller rows."""
+        ``stokes_rows``: [rows, 4] (I, Q, U, V) weights of this call in place of the detectors' cached Mueller rows.
+        ``sky``: the map to sample, ``self.map`` (None) or ``self.cmb``, each with a cache slot of its own on ``obs``; a
+        map in K_CMB has the Planck derivative ``cmb.kcmb_weight`` under both band integrals."""
         import torch
 
         from . import map as mmap
+        from .cmb import kcmb_weight
         from .instrument import compute_angular_fwhm
 
+        sky = self.map if sky is None else sky
+        slot = "_cmb_cache" if sky is self.cmb else "_map_cache"
+        thermodynamic = sky.units == "K_CMB"
         lo, hi = rows or (0, obs.instrument.dets.n)
         dets = obs.instrument.dets.subset(np.arange(lo, hi))
         offsets = obs.coords.offsets[lo:hi]
@@ -310,8 +370,8 @@ class Simulation:
         # (the map OBJECT is kept and compared with `is`, as are the things the cached tensors were made from -- its data
         # array and the weather's temperature: an id() of a freed map can come back, and an edit in place keeps the id)
         key = (str(device), lo, hi)
-        made_from = (self.map, self.map.data, None if atm is None else float(atm.weather.temperature[0]))
-        cache = getattr(obs, "_map_cache", None)
+        made_from = (sky, sky.data, None if atm is None else float(atm.weather.temperature[0]))
+        cache = getattr(obs, slot, None)
         if (cache is None or cache.get("key") != key or cache["made_from"][0] is not made_from[0]
                 or cache["made_from"][1] is not made_from[1] or cache["made_from"][2] != made_from[2]):
             f32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float32)).to(device)  # noqa: E731
@@ -321,8 +381,8 @@ class Simulation:
             if atm is not None:
                 cache["steps_per_tile"] = mmap.steps_per_tile(obs.coords.t, atm._device_path().dta)
             cache["transform"] = (f64(sky_transform_stack(obs.coords.t, obs.site.latitude, obs.site.longitude).reshape(T, 9))
-                                  if self.map.frame == "ra/dec" else None)
-            mueller_rows = mmap.mueller_row(dets.gamma)[:, ["IQUV".index(s) for s in self.map.stokes]]
+                                  if sky.frame == "ra/dec" else None)
+            mueller_rows = mmap.mueller_row(dets.gamma)[:, ["IQUV".index(s) for s in sky.stokes]]
             covered = np.zeros(dets.n, bool)
             for b, band in enumerate(dets.bands):
                 idx = np.nonzero(dets.band_index == b)[0]
@@ -330,9 +390,9 @@ class Simulation:
                     continue
                 # ideally one beam per channel; the reference smooths once per band (map.py:101-104)
                 fwhm = float(compute_angular_fwhm(fwhm_0=dets.primary_size.mean(), z=np.inf, nu=band.center))
-                smoothed = self.map.smooth(fwhm, ctx=ctx, device=device)  # [S, C, eta, xi]
+                smoothed = sky.smooth(fwhm, ctx=ctx, device=device)  # [S, C, eta, xi]
                 channels, tables, scalars = [], [], []
-                for c, (nu_min, nu_max) in enumerate(self.map.nu_bin_bounds):
+                for c, (nu_min, nu_max) in enumerate(sky.nu_bin_bounds):
                     if band.nu.max() < nu_min or nu_max < band.nu.min():  # map.py:112-113
                         continue
                     channels.append(c)
@@ -340,11 +400,13 @@ class Simulation:
                         sp = atm.spectrum
                         mask = (sp.side_nu >= nu_min) & (sp.side_nu < nu_max)
                         nu = sp.side_nu[mask]
-                        grid = np.trapezoid(band.passband(nu) * np.exp(-sp._opacity[..., mask]), x=nu, axis=-1)
+                        response = band.passband(nu) * kcmb_weight(nu) if thermodynamic else band.passband(nu)  # sim/cmb.py:48
+                        grid = np.trapezoid(response * np.exp(-sp._opacity[..., mask]), x=nu, axis=-1)
                         tables.append(mmap.collapse_temperature(grid, sp.side_base_temperature, atm.weather.temperature[0]))
                     else:  # band/band.py:246-248
                         nu = band.nu[(band.nu >= nu_min) & (band.nu < nu_max)]
-                        scalars.append(float(np.trapezoid(band.passband(nu), x=nu)))
+                        response = band.passband(nu) * kcmb_weight(nu) if thermodynamic else band.passband(nu)
+                        scalars.append(float(np.trapezoid(response, x=nu)))
                 if not channels:
                     logger.warning(f"No load from map for band {band.name}")
                     continue
@@ -360,7 +422,7 @@ class Simulation:
                     entry.update(scalars=scalars)
                 cache["bands"][b] = entry
             cache["all_rows"] = bool(covered.all())
-            obs._map_cache = cache
+            setattr(obs, slot, cache)
         # rows of bands that see no channel of the map stay zero (sim/map.py:112-113); where every row is written
         # nothing is cleared first (a [D, T] fill is 9.6 GB at the headline size)
         out = (torch.empty if cache["all_rows"] else torch.zeros)((dets.n, T), dtype=torch.float32, device=device)
@@ -383,9 +445,9 @@ class Simulation:
             dst = out[int(idx[0]) : int(idx[-1]) + 1] if e["contiguous"] else torch.empty((len(idx), T), dtype=torch.float32, device=device)
             stokes = e["stokes"]
             if stokes_rows is not None:
-                picked = np.asarray(stokes_rows, np.float64)[idx][:, ["IQUV".index(s) for s in self.map.stokes]]
+                picked = np.asarray(stokes_rows, np.float64)[idx][:, ["IQUV".index(s) for s in sky.stokes]]
                 stokes = torch.as_tensor(np.ascontiguousarray(picked)).to(device)
-            mmap.sample_map(ctx, e["values"], self.map.eta, self.map.xi, self.map.center, cache["az"], cache["el"],
+            mmap.sample_map(ctx, e["values"], sky.eta, sky.xi, sky.center, cache["az"], cache["el"],
                             e["offsets"], stokes, out=dst, transform=cache["transform"],
                             bilinear=bool(self.map_kwargs["bilinear_sampling"]), device=device, sync=False, **kw)
             if not e["contiguous"]:
@@ -453,7 +515,7 @@ class Simulation:
         lagged = tau is not None
         units_out = units
         # A half-wave plate modulates optical power too: the same precedent, the map field made in pW
-        modulated = self.hwp is not None and self.map is not None
+        modulated = self.hwp is not None and (self.map is not None or self.cmb is not None)
         if lagged or modulated:
             units = "pW"
         if hi <= lo:
@@ -463,7 +525,8 @@ class Simulation:
                 metadata.update(atmosphere=True, pwv=float(np.round(obs.atmosphere.weather.pwv, 3)),
                                 base_temperature=float(np.round(obs.atmosphere.weather.temperature[0], 3)))
                 obs.atmosphere._realisation += 1
-            names = [n for n, on in (("atmosphere", has_atm), ("map", self.map is not None), ("noise", self.noise)) if on]
+            names = [n for n, on in (("atmosphere", has_atm), ("map", self.map is not None), ("cmb", self.cmb is not None),
+                                            ("noise", self.noise)) if on]
             empty = torch.empty((0, len(obs.coords.t)), dtype=torch.float32, device=device)
             obs.loading = {n: (empty.clone() if self.device_output else empty.cpu().numpy()) for n in names}
             tod = TOD(data=obs.loading, dets=dets, coords=obs.boresight.broadcast(obs.coords.offsets[lo:hi]), units=units, metadata=metadata)
@@ -485,25 +548,33 @@ class Simulation:
         # The map field: in pW, gain and TOD.to("K_RJ") applied below -- or, in the default units with an atmosphere to
         # calibrate by and no noise that wants the loadings in pW first, written in K_RJ with the gain by the sampler
         # itself (mrx_map_sample_krj; not with the literal pointing chain, which that entry refuses)
-        map_loading, map_done = None, False
-        if self.map is not None:
+        # The CMB field (``cmb=``) is a second map and takes the same routes, beside the ``map`` field.
+        sky_loading, sky_done = {"map": None, "cmb": None}, {"map": False, "cmb": False}
+        for name, sky in (("map", self.map), ("cmb", self.cmb)):
+            if sky is None:
+                continue
             if (units == "K_RJ" and has_atm and not loading_nep
                     and not obs.atmosphere._device_path().ctx.get_option(_lib.OPT_POINTING_CHAIN)):
                 self._set_calibration(obs, metadata)
                 d_gain_rows = torch.as_tensor(gain.astype(np.float32), device=device) if has_gain else None
-                map_loading = self._sample_maps(obs, rows, krj=obs.atmosphere._device_path().krj_row_tables(), gain=d_gain_rows)
-                map_done = True
+                sky_loading[name] = self._sample_maps(obs, rows, krj=obs.atmosphere._device_path().krj_row_tables(), gain=d_gain_rows,
+                                                      sky=sky)
+                sky_done[name] = True
             elif modulated:
-                map_loading = self._sample_hwp(obs, rows, dets)  # pW
+                sky_loading[name] = self._sample_hwp(obs, rows, dets, sky)  # pW
             else:
-                map_loading = self._sample_maps(obs, rows)  # pW
+                sky_loading[name] = self._sample_maps(obs, rows, sky=sky)  # pW
+        map_loading, map_done = sky_loading["map"], sky_done["map"]
+        cmb_loading, cmb_done = sky_loading["cmb"], sky_done["cmb"]
         noise = None
         if self.noise:
             total = None
             if loading_nep:  # noise.py:35-37 sums every loading field, in pW
-                fields = [f for f in (loading, map_loading) if f is not None]
+                fields = [f for f in (loading, map_loading, cmb_loading) if f is not None]
                 if fields:
                     total = fields[0] if len(fields) == 1 else fields[0] + fields[1]
+                    for f in fields[2:]:
+                        total = total + f
                 else:
                     total = torch.zeros((dets.n, len(obs.coords.t)), dtype=torch.float32, device=device)
             # in the default units the noise leaves its generator in K_RJ (mrx_noise_generate_krj)
@@ -516,6 +587,8 @@ class Simulation:
             d_gain = torch.as_tensor(gain.astype(np.float32), device=device)[:, None]
             if map_loading is not None and not map_done:
                 map_loading *= d_gain
+            if cmb_loading is not None and not cmb_done:
+                cmb_loading *= d_gain
             if loading is not None and loading_nep:
                 loading *= d_gain
         if units == "K_RJ" and has_atm:
@@ -526,16 +599,18 @@ class Simulation:
                 path.to_krj(loading)
             if map_loading is not None and not map_done:  # (the noise was written in K_RJ)
                 path.to_krj(map_loading)
+            if cmb_loading is not None and not cmb_done:
+                path.to_krj(cmb_loading)
         elif units == "K_RJ":
             den = torch.as_tensor(self._band_denominators(all_dets)[lo:hi].astype(np.float32), device=device)[:, None]
-            for field in (map_loading, noise):
+            for field in (map_loading, cmb_loading, noise):
                 if field is not None:
                     field /= den
         if lagged:  # the noise is the law of the readout's output and stays as drawn
-            optical = [n for n, f in (("atmosphere", loading), ("map", map_loading)) if f is not None]
-            self._apply_time_constants(obs, [f for f in (loading, map_loading) if f is not None], tau)
+            optical = [n for n, f in (("atmosphere", loading), ("map", map_loading), ("cmb", cmb_loading)) if f is not None]
+            self._apply_time_constants(obs, [f for f in (loading, map_loading, cmb_loading) if f is not None], tau)
             metadata["time_constants"] = {"applied": True, "fields": optical, "init": "steady"}
-        for name, field in (("atmosphere", loading), ("map", map_loading), ("noise", noise)):
+        for name, field in (("atmosphere", loading), ("map", map_loading), ("cmb", cmb_loading), ("noise", noise)):
             if field is not None:
                 obs.loading[name] = field if self.device_output else field.cpu().numpy()
         coords = obs.coords if rows is None else obs.boresight.broadcast(obs.coords.offsets[lo:hi])
@@ -546,23 +621,25 @@ class Simulation:
             obs.loading = tod.data
         return tod
 
-    def _sample_hwp(self, obs, rows, dets):
-        """The map field behind the half-wave plate, [D, T] pW: S_I + S_c cos 4 chi + S_s sin 4 chi from three passes of
+    def _sample_hwp(self, obs, rows, dets, sky=None):
+        """The field of the map ``sky`` (``self.map`` where None) behind the half-wave plate, [D, T] pW: S_I + S_c cos 4 chi +
+        S_s sin 4 chi from three passes of
         the sampler -- the detectors' I weights alone, the Q / U weights of angle -gamma, those of pi / 4 - gamma --
         combined in place by ``mrx_tod_hwp_modulate``.  A map without Q and U has S_c = S_s = 0: one pass, no launch."""
         from . import hwp as mhwp
         from . import map as mmap
 
+        sky = self.map if sky is None else sky
         rows_i = np.zeros((dets.n, 4))
         rows_i[:, 0] = mmap.mueller_row(dets.gamma)[:, 0]
-        out = self._sample_maps(obs, rows, stokes_rows=rows_i)
-        if not set(self.map.stokes) & {"Q", "U"}:
+        out = self._sample_maps(obs, rows, stokes_rows=rows_i, sky=sky)
+        if not set(sky.stokes) & {"Q", "U"}:
             return out
         fields = []
         for g in (-dets.gamma, np.pi / 4 - dets.gamma):
             w = mmap.mueller_row(g)
             w[:, 0] = w[:, 3] = 0.0
-            fields.append(self._sample_maps(obs, rows, stokes_rows=w))
+            fields.append(self._sample_maps(obs, rows, stokes_rows=w, sky=sky))
         ctx, _ = self._context(obs)
         return mhwp.modulate(out, fields[0], fields[1], mhwp.carrier(self.hwp.angle(obs.coords.t)), out=out, ctx=ctx)
 
