@@ -32,13 +32,15 @@ namespace {
 struct CalDet {
   float a_re;  // sin(r) cos(p)
   float a_im;  // cos(r)
+  float a_q;   // sin(r) sin(p): the component across the elevation circle (det_elevation's steep branch)
   int band;
   float scale;
   float dy, sdy, cdy;  // vertical offset and its sine / cosine
   // el_det - el_bore as a linear function of el_bore around the tile's middle boresight
   // elevation (it does not depend on the azimuth): el_det(s) = eb + dm + slope (eb - ebm).
-  // Curvature over a tile's elevation range (~0.02 rad) is below 1e-7 rad.  exact = 1 near the
-  // zenith, where the detector elevation is not smooth in eb: every sample takes the full formula.
+  // The line drops the curvature r^2 sec^2(el) tan(el) x^2 / 2 (kModelCurvature: rows it would cost more than 5e-7 rad
+  // are exact; measured on the rows that keep the model: 7.6e-7 rad against float64, rounding included).  exact = 1 too near
+  // the zenith, where the detector elevation is not smooth in eb: every sample takes the full formula.
   float dm, slope, ebm;
   int exact;
   // lin = 1: over the tile's whole boresight range the row stays inside ONE cell of the table's elevation axis (a cell
@@ -56,9 +58,10 @@ struct CalDet {
 // detector elevation (transforms.py:20-28): im = sin(el) as the chain computes
 // it, then el = asin(im) by one Newton step from el0 = el_bore + dy, whose
 // sine and cosine follow from the angle-addition formulas (no inverse
-// trigonometry per sample); |el - el0| <= r^2 tan(el)/2 ~ 3e-4 rad, so the
-// second-order step is exact to float32 rounding.  eb: boresight elevation,
-// ca / sa: cos / sin of (eb - pi/2).
+// trigonometry per sample); el - el0 = dl1 ~ r^2 tan(el) / 2 (3e-4 rad at r = 1 deg,
+// 1.7e-2 at 8 deg) and the step drops dl1^3 (tan^2 / 2 + 1 / 6): 6e-8 rad at r = 2 deg,
+// 7e-7 at 3 deg, 1.7e-5 at 5 deg below the steepness threshold -- kNewtonBudget sends
+// those to the arc sine.  eb: boresight elevation, ca / sa: cos / sin of (eb - pi/2).
 // sin(el_det) as the float32 chain forms it (transforms.py:20-28): two products and a sum, each rounded.  ca / sa: cos / sin
 // of (boresight elevation - pi/2).  One definition for every kernel that divides by den(el_det) -- here, coarse_krj_kernel
 // and the one-launch sampler (mrx_synth.hip), whose fields are compared bit for bit.
@@ -66,6 +69,8 @@ __device__ __forceinline__ float det_sin_elevation(float a_re, float a_im, float
   MRX_KRJ_FP
   return a_re * sa + a_im * ca;
 }
+
+constexpr float kNewtonBudget = 2.0e-7f;  // rad: what the second-order step may drop before det_elevation takes asinf
 
 __device__ __forceinline__ float det_elevation(const CalDet& c, float eb, float ca, float sa) {
   MRX_KRJ_FP
@@ -75,15 +80,31 @@ __device__ __forceinline__ float det_elevation(const CalDet& c, float eb, float 
   const float rc0 = __builtin_amdgcn_rcpf(c0);
   const float dl1 = (im - s0) * rc0;
   float el = fmaf(dl1, 1.0f + 0.5f * dl1 * s0 * rc0, eb + c.dy);
-  // within ~15 deg of the zenith the expansion loses accuracy: take asin there
-  const bool steep = !(c0 > 0.25f);
+  // within ~15 deg of the zenith the expansion loses accuracy: take asin there -- and wherever the step's dropped
+  // third-order term, dl1^3 (tan^2(el0) / 2 + 1 / 6), passes kNewtonBudget (offsets of some degrees: dl1 ~ r^2 tan(el) / 2)
+  const float t0 = s0 * rc0;
+  const bool steep = !(c0 > 0.25f) || fabsf(dl1 * dl1 * dl1) * fmaf(0.5f * t0, t0, 1.0f / 6.0f) > kNewtonBudget;
   if (__builtin_amdgcn_ballot_w64(steep) != 0)
-    if (steep) el = asinf(im);
+    if (steep) {
+      // (not asinf(im): an ulp of im is 6e-8 / cos(el) of elevation -- 1.5e-5 rad at 89.7 deg, 2e-4 at the zenith.  The
+      // angle from both components of the unit vector keeps the float32 rounding of the elevation itself
+      // -- above 45 deg the arc sine of cos(el) -- with ONE call of asinf for both halves, for the registers' sake)
+      const float re = fmaf(c.a_re, ca, -(c.a_im * sa));  // cos(el) cos(az_det - az_bore)
+      const float cq = sqrtf(fmaf(re, re, c.a_q * c.a_q));  // cos(el)
+      const bool high = fabsf(im) > 0.70710678f;
+      const float a = asinf(high ? cq : im);
+      el = high ? copysignf(1.57079632679489662f - a, im) : a;
+    }
   return el;
 }
 
 // the linear model of CalDet around the boresight elevation ebm (see CalDet)
 constexpr float kModelHalfRange = 2.0e-2f;  // wide enough that float32 rounding of the differences stays below 1e-7 rad over a tile
+// The model drops the curvature of el_det - el_bore in el_bore: r^2 sec^2(el) tan(el) x^2 / 2 at x = el_bore - ebm (1.1e-7 rad
+// at r = 0.5 deg, el = 60 deg, x = 0.02; 1.1e-6 at r = 1 deg, el = 68 deg; 4.4e-6 at r = 2 deg, el = 68 deg).  Its own three
+// points give the second derivative; a row whose estimate at the end of the tile's range passes kModelCurvature takes the
+// full formula per sample (krj_stage_rows) -- half of the division's 1e-6 rad, the rest is the Newton step's and rounding.
+constexpr float kModelCurvature = 5.0e-7f;
 
 // (cos, sin) of (ebm - pi/2) and of that angle -+ kModelHalfRange: ONE cosine and sine (the accurate ones) and the
 // angle-addition formulas with the constants cos / sin(0.02) -- the model's three points used to cost six calls of the
@@ -107,7 +128,9 @@ __device__ __forceinline__ BoreTrig bore_trig(float ebm) {
   return b;
 }
 
-__device__ __forceinline__ void set_elevation_model(CalDet& c, float ebm, const BoreTrig& b) {
+// Returns |d^2 (el_det - el_bore) / d el_bore^2| at ebm from the second difference of the three points (float32 rounding of
+// the differences: 3e-4 / rad, 6e-8 rad over a tile's +-0.02).
+__device__ __forceinline__ float set_elevation_model(CalDet& c, float ebm, const BoreTrig& b) {
   MRX_KRJ_FP
   constexpr float h = kModelHalfRange;
   float e[3];
@@ -122,6 +145,7 @@ __device__ __forceinline__ void set_elevation_model(CalDet& c, float ebm, const 
   c.dm = e[1];
   c.slope = (e[2] - e[0]) * (0.5f / h);
   c.exact = steep ? 1 : 0;
+  return fabsf((e[0] - e[1]) + (e[2] - e[1])) * (1.0f / (h * h));
 }
 
 // The row's den as one linear function of x = el_bore - ebm over the tile (CalDet::lin).  [lo, hi]: the tile's boresight
@@ -181,6 +205,7 @@ __device__ __forceinline__ CalDet make_cal_det(float dx, float dy, int band, flo
   CalDet c;
   if (r2 < 0.09f) {
     c.a_re = -dy * sinc_small(r2);
+    c.a_q = -dx * sinc_small(r2);
     c.a_im = cos_small(r2);
     c.sdy = dy * sinc_small(y2);
     c.cdy = cos_small(y2);
@@ -188,6 +213,7 @@ __device__ __forceinline__ CalDet make_cal_det(float dx, float dy, int band, flo
     const float r = sqrtf(r2);
     const float p = atan2f(-dx, -dy);
     c.a_re = sinf(r) * cosf(p);
+    c.a_q = sinf(r) * sinf(p);
     c.a_im = cosf(r);
     c.sdy = sinf(dy);
     c.cdy = cosf(dy);
@@ -239,8 +265,10 @@ struct KrjSamples {
 // Round 6, two forms:
 //  * the usual row (CalDet::lin): den is linear in the boresight elevation over the whole tile, with at most one kink --
 //    its value at the thread's first and last sample, two reciprocals, the inner two samples on the chord between them
-//    (the elevation is linear in the sample index to ~5e-8 rad over four samples -- 10 ms of scanning, over which den
-//    itself moves by ~3e-6 of its value; a kink inside those 10 ms is missed by 1e-8 of den);
+//    (the elevation is linear in the sample index to 1e-6 rad over four samples -- the gate of KrjSamples::curved; 5e-8 in
+//    10 ms of the usual scanning, over which den itself moves by ~3e-6 of its value; a kink inside those four samples is
+//    missed by at most 2/9 of the slope's jump x the elevation the four samples span: 1e-8 of den on the smooth tables of
+//    am, 1.2e-5 on the test's zigzag whose slope jumps by 1 / rad);
 //  * every other row -- near the zenith (CalDet::exact), off the axis (NaN, as jax fills), a tile that sweeps more than two
 //    cells, a workgroup whose boresight is not linear over a thread's four samples (KrjSamples::curved: 20 Hz, a 0.1 deg
 //    daisy at 0.8 deg/s) -- one sample at a time at its own boresight elevation through den_lookup.  That loop is not
@@ -352,10 +380,12 @@ __device__ __forceinline__ void krj_stage_rows(CalDet* cdet, float* red, const f
     if ((int)threadIdx.x < nd) {
       const int d = d0 + threadIdx.x;
       CalDet c = make_cal_det(dxs[d], dys[d], min(max(band[d], 0), n_bands - 1), scale ? scale[d] : 1.0f);
-      set_elevation_model(c, 0.5f * (lo + hi), bore_trig(0.5f * (lo + hi)));
+      const float curv = set_elevation_model(c, 0.5f * (lo + hi), bore_trig(0.5f * (lo + hi)));
       // the model is a finite difference over ebm +- 0.02 rad: a tile whose boresight sweeps
-      // farther (slow sample rates, fast elevation slews) takes the full formula per sample
+      // farther (slow sample rates, fast elevation slews) takes the full formula per sample,
+      // and so does a row whose curvature the line misses by more than kModelCurvature at |x| = (hi - lo) / 2
       if (!(hi - lo <= 2.0f * kModelHalfRange)) c.exact = 1;
+      if (!(curv * (hi - lo) * (hi - lo) * 0.125f <= kModelCurvature)) c.exact = 1;
       set_linear_den(c, lo, hi, cells + c.band * (n_el - 1), n_el, cells[0].x, cells[0].z);
       cdet[threadIdx.x] = c;
       exact = c.exact != 0;
