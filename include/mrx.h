@@ -54,7 +54,8 @@ typedef enum mrx_status {
                                   reference raises RuntimeError "introduced nans"
                                   (atmosphere/atmosphere.py:368-369)            */
 #define MRX_FLAG_TABLE_OOB 2u  /* (pwv, el) left the emission table: jax fill
-                                  value NaN (band/band.py:283-286)              */
+                                  value NaN (band/band.py:283-286); not raised for
+                                  a sample whose pwv is NaN because it left a screen */
 #define MRX_FLAG_NAN 4u        /* a NaN reached the output                      */
 #define MRX_FLAG_HANDOVER 8u   /* mrx_atm_synthesize: a writer gave up waiting for the sampler (its bound of
                                   ~seconds; the call's TOD is then invalid)     */

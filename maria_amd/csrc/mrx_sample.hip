@@ -156,7 +156,7 @@ __device__ __forceinline__ float band_loading(const mrx_table_dev& tb, const flo
   }
   if ((!kCubicPath || !tb.cubic) && (cp_.oob || cl.oob || tb.t_oob)) {
     val = __builtin_nanf("");
-    if (in_t) iflags |= MRX_FLAG_TABLE_OOB;
+    if (in_t && pwv == pwv) iflags |= MRX_FLAG_TABLE_OOB;  // (a NaN pwv is a line of sight off a screen: MRX_FLAG_SCREEN_OOB alone)
   }
   float out = m00 * val;
   if (kCubicPath && tb.cubic) {
@@ -182,7 +182,7 @@ __device__ __forceinline__ float band_loading(const mrx_table_dev& tb, const flo
     }
     const bool inside = xd >= X[0] && xd <= X[tb.n_pwv - 1] && yd >= Y[0] && yd <= Y[tb.n_el - 1];
     out = inside ? (float)((double)m00 * acc) : __builtin_nanf("");
-    if (!inside && in_t) iflags |= MRX_FLAG_TABLE_OOB;
+    if (!inside && in_t && pwv == pwv) iflags |= MRX_FLAG_TABLE_OOB;
   }
   if (out != out && in_t) iflags |= MRX_FLAG_NAN;
   return out;

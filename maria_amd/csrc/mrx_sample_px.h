@@ -486,7 +486,8 @@ __device__ __forceinline__ void px_sample_items(
         const double pwv = off ? (double)__builtin_nanf("") : pwv0 + (double)fl[tt];
         bool table_oob;
         const float out = band_loading_px(tb, tdata, (float)pwv, theta[tt], m00, table_oob);
-        if (t < Ta) iflags |= (off ? MRX_FLAG_SCREEN_OOB : 0u) | (table_oob ? MRX_FLAG_TABLE_OOB : 0u) | (out != out ? MRX_FLAG_NAN : 0u);
+        // (a sample off a screen carries a NaN pwv into the lookup: that is the screen's flag alone, not the table's)
+        if (t < Ta) iflags |= (off ? MRX_FLAG_SCREEN_OOB : table_oob ? MRX_FLAG_TABLE_OOB : 0u) | (out != out ? MRX_FLAG_NAN : 0u);
         // what is stored: the loading itself, or what the caller's hook makes of it (K_RJ on the coarse grid)
         const float kept = hooks.value(out, bore[it + tt], t, (int)row0 + dd, live && t < Ta);
         if (kWriteThrough) {
