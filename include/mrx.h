@@ -572,6 +572,27 @@ int mrx_cmb_work_floats(int ny, int nx, int n_ell, size_t* floats);
 int mrx_cmb_generate(mrx_ctx* ctx, uint64_t seed, uint32_t stream, int ny, int nx, double res, const float* table,
                      int n_ell, const mrx_screen_desc* fields, float* d_work, size_t work_floats);
 
+/* Band powers of two maps from their half-plane modes: the binned sums behind TT, EE, BB, TE, TB, EB.
+ * d_a1, d_a2: [3][ny][nx/2 + 1] complex128 (re, im interleaved), the modes of T, Q, U in numpy.fft.rfft2's layout
+ * (rows fy as fftfreq orders them, columns fx = 0 .. nx/2); d_a2 == d_a1 gives the auto spectra.  ny and nx are even
+ * and at least 8, not necessarily powers of two; `res` is the pixel size in radians.  Per cell, all in float64:
+ *     k = 2 pi (fx / (nx res), fy / (ny res)),   l^2 = kx^2 + ky^2,
+ *     cos 2phi = (kx^2 - ky^2) / l^2,   sin 2phi = 2 kx ky / l^2,
+ *     E = Q cos 2phi + U sin 2phi,   B = -Q sin 2phi + U cos 2phi
+ * -- the convention of mrx_cmb_generate above (x the column axis, y the row axis, phi = atan2(ky, kx)), inverted, and of
+ * tests/cmb_ref.py's modes_of.  A cell is dropped when k = 0, when it lies on either Nyquist line (fx = nx/2 or
+ * |fy| = ny/2: sin 2phi is odd there, see mrx_cmb_generate) or when l is outside [edges[0], edges[n_bins]).  A kept cell
+ * lies in bin b when edges[b]^2 <= l^2 < edges[b+1]^2 and has the weight w = 2 for 0 < fx < nx/2 (its mirror carries the
+ * same real parts) and w = 1 in the column fx = 0.  `edges` is a HOST array of n_bins + 1 finite, strictly ascending
+ * values >= 0, n_bins in 1 .. 1024.  d_sums [n_bins][8] receives per bin
+ *     sum w,  sum w l,  then sum w XY for XY = TT, EE, BB, TE, TB, EB,   XY = (Re(a1_X conj a2_Y) + Re(a1_Y conj a2_X)) / 2.
+ * No floating-point atomics: the order of every sum is a function of (ny, nx, edges) alone, so two calls give the same
+ * bits.  d_work: mrx_band_power_work_bytes bytes, 16-byte aligned like d_a1 and d_a2; its contents on entry do not
+ * matter.  The call uploads the edges and waits for that copy. */
+int mrx_band_power_work_bytes(int ny, int nx, int n_bins, size_t* bytes);
+int mrx_map_band_powers(mrx_ctx* ctx, const double* d_a1, const double* d_a2, int ny, int nx, double res,
+                        const double* edges, int n_bins, double* d_sums, void* d_work, size_t work_bytes);
+
 /* Covariance-matched amplitudes (circulant embedding) for the generators above.  The power law is
  * the continuous transform of the Matern covariance cut at the grid's Nyquist wavenumber; for rough
  * fields (nu = 1/3 in three dimensions, atmosphere/atmosphere.py:249) most of the one-pixel structure

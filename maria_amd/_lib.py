@@ -209,6 +209,8 @@ SIGNATURES = {
     "mrx_screen_psd_sum": (_i, [_vp, _i, _i, _d, _d, _d, _d, C.POINTER(_d)]),
     "mrx_cmb_work_floats": (_i, [_i, _i, _i, C.POINTER(_sz)]),
     "mrx_cmb_generate": (_i, [_vp, C.c_uint64, C.c_uint32, _i, _i, _d, _vp, _i, C.POINTER(MrxScreenDesc), _vp, _sz]),
+    "mrx_band_power_work_bytes": (_i, [_i, _i, _i, C.POINTER(_sz)]),
+    "mrx_map_band_powers": (_i, [_vp, _vp, _vp, _i, _i, _d, C.POINTER(_d), _i, _vp, _vp, _sz]),
     "mrx_map_sample": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _sz]),
     "mrx_map_sample_krj": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _sz]),
     "mrx_bin_map": (_i, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
